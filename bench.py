@@ -22,6 +22,10 @@ on the launch stream inside one eager step; FLOPs / time against the FP32-MFMA p
 on one stream), `kernels` (stand-alone timings of the hand-written kernels against their rooflines; `traffic` = HBM bytes per
 call from the committed rocprofv3 --pmc passes, profiles/r0*_pmc_kernels.json), `cpu_baseline` (same step, same batch, on the
 host cores with the CPU oracle, bounded sample).  tools/make_profiles.sh regenerates profiles/r03_* with the same commands.
+
+`--steps K` times exactly K steps (`--repeats R`: R timings of K steps each, the line reports their median).  `--dump-outputs DIR`
+writes what the timed step computed in its last step as DIR/<name>.npy (see dump_outputs); the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -823,13 +827,47 @@ def timed_repeats(step, fence, steps, repeats, reduce_max=None):
     return sorted(out)
 
 
+DUMP_CAP = 1 << 22      # elements per dumped vector (16 MiB of f32): a longer one is written as a fixed, seeded sample of its entries
+
+
+def _dump_sample(v):
+    if v.numel() <= DUMP_CAP:
+        return v
+    idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_CAP].sort().values
+    return v[idx]
+
+
+def dump_outputs(tr, out_dir):
+    """--dump-outputs: what the timed path computed in its LAST step, as the caller of the step driver receives it -- the loss step()
+    returned (`loss`), the metric beside it (`metric`: accuracy of the classification steps), the gradient of that step (`grads`) and
+    the trainable parameters after its update (`params`), both in named_parameters() order, flattened and concatenated, and the model's
+    floating-point buffers (`buffers`: BatchNorm statistics, state_dict() order).  f32 .npy files, at most 3 x DUMP_CAP + 2 floats."""
+    import numpy as np
+    ts, model = tr.ts, tr.model
+    if ts.loss.is_cuda:
+        torch.cuda.synchronize(ts.loss.device)
+    params = [p for p in model.parameters() if p.requires_grad]
+    names = {n for n, _ in model.named_parameters()}
+    bufs = [v for k, v in model.state_dict().items() if k not in names and v.is_floating_point()]
+    with torch.no_grad():
+        out = {"loss": ts.loss.reshape(1), "metric": ts.flat.scalars[1:2],
+               "params": torch.cat([p.reshape(-1) for p in params]),
+               "grads": torch.cat([(torch.zeros_like(p) if p.grad is None else p.grad).reshape(-1) for p in params])}
+        if bufs:
+            out["buffers"] = torch.cat([v.reshape(-1).float() for v in bufs])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), _dump_sample(v.detach().float().cpu()).numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=32, help="clouds per GPU")
-    ap.add_argument("--repeats", type=int, default=3, help="timings of --steps steps each; the line reports their median (min / max beside it)")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timings of --steps steps each; the line reports their median (min / max beside it).  Timed steps = repeats x steps")
     ap.add_argument("--workload", default="cls", choices=["cls", "cls_aux", "stage2", "pretask", "pretrain", "seg"],
                     help="cls = the headline workload (default); the others are secondary recipes, see RecipeTrainer")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -843,6 +881,9 @@ def main():
     ap.add_argument("--selftest-launch", action="store_true",
                     help="ranks only rendezvous, barrier and reduce a dummy time, rank 0 prints the JSON skeleton: checks the "
                          "--gpus N launcher and the process-group plumbing on a host without a GPU (tests/test_host.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, metric, gradient, updated parameters, BatchNorm "
+                         "statistics) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
     if args.detail:
         global DETAIL_PATH
@@ -917,6 +958,8 @@ def main():
     times = timed_repeats(tr.step, fence, args.steps, args.repeats, reduce_max)
     elapsed = times[len(times) // 2]
     timing = {"repeats": args.repeats, "ms_per_step_min": 1000.0 * times[0] / args.steps, "ms_per_step_max": 1000.0 * times[-1] / args.steps}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, args.dump_outputs)              # (before anything below runs another step on the timed driver)
 
     if rank == 0 and args.workload != "cls":
         # secondary recipe: throughput + the roofline of its dominant kernel family (the exact-f32 MFMA Linear launches: forward, data

@@ -22,15 +22,18 @@ def _free_port():
     return p
 
 
-def _setup_model():
+def _setup_model(install_oracle=True):
+    """install_oracle: put the CPU oracle's grouping into the model's op table for good -- in a spawned rank only.  The test process takes
+    the `oracle_ops` fixture instead, which puts the HIP entry points back afterwards: the GPU tests of the same session run on them."""
     import oracle
     from models import build_model_from_cfg, upp_layers
     from upp_hip import functional as HF
     from upp_hip.train import freeze_for_peft
     from utils.config import builtin_cfg
-    ops = oracle.torch_ops()
-    upp_layers.OPS.update(ops)
-    HF.fps_gather = ops["fps_gather"]
+    if install_oracle:
+        ops = oracle.torch_ops()
+        upp_layers.OPS.update(ops)
+        HF.fps_gather = ops["fps_gather"]
     torch.manual_seed(0)
     cfg = builtin_cfg('unify_modelnet_cls').model
     # gather_idx=False reproduces the reference's stride-64-into-stride-74 indexing, which reads rows of
@@ -81,7 +84,7 @@ def _worker(rank, world, port, out_dir):
 
 
 @pytest.mark.timeout(600)
-def test_two_rank_gloo_step_matches_single_process(tmp_path):
+def test_two_rank_gloo_step_matches_single_process(tmp_path, oracle_ops):
     from conftest import ROOT, PKG
     os.environ["UPP_TEST_PATHS"] = os.pathsep.join([os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests"), PKG])
     port = _free_port()
@@ -91,7 +94,7 @@ def test_two_rank_gloo_step_matches_single_process(tmp_path):
     assert torch.equal(r0["p"], r1["p"]), "ranks diverged after the optimizer step"
 
     from upp_hip.train import TrainStep
-    model = _setup_model()
+    model = _setup_model(install_oracle=False)
     pts, labels = _data()
     ts = TrainStep(model, (4, 1096, 3), use_graph=False)
     assert not ts.distributed

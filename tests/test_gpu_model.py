@@ -274,3 +274,32 @@ def test_auxiliary_reconstruction_losses_on_the_completion_prompters_points(mode
     assert torch.isfinite(x.grad).all() and x.grad.abs().sum().item() > 0
     d1, d2, _, _ = O.chamfer_fwd(rb.cpu().numpy(), gt.cpu().numpy())
     np.testing.assert_allclose(cd.item(), (np.sqrt(d1).mean() + np.sqrt(d2).mean()) / 2, rtol=1e-5)
+
+
+def test_bench_dump_outputs_are_the_same_in_two_runs_with_the_same_arguments(tmp_path):
+    """`bench.py --dump-outputs DIR`: the headline step's last timed step (loss, metric, gradient, updated parameters, BatchNorm
+    statistics) as f32 arrays; the inputs are seeded and the step driver is deterministic, so two runs write the same bits."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "UPP_FORCE_DIST"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
+                              "--no-cpu-baseline", "--no-stage-report", "--detail", str(tmp_path / "detail.json"), "--dump-outputs", str(d)],
+                             env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert rec["steps"] == 3 and rec["repeats"] == 1 and rec["ms_per_step"] > 0
+        dumps.append({n: np.load(d / (n + ".npy")) for n in ("loss", "metric", "params", "grads", "buffers")})
+    a, b = dumps
+    assert a["params"].shape == (619176,) and a["grads"].shape == (619176,)
+    for n in a:
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all(), n
+        assert np.array_equal(a[n], b[n]), n
+    assert np.abs(a["grads"]).max() > 0

@@ -322,3 +322,31 @@ def test_bench_timed_repeats_times_exactly_steps_per_repeat():
     calls, fences = [], []
     ts = bench.timed_repeats(lambda: calls.append(1), lambda: fences.append(len(calls)), steps=7, repeats=3)
     assert len(calls) == 21 and fences == [0, 7, 7, 14, 14, 21] and ts == sorted(ts) and len(ts) == 3
+
+
+def test_bench_dump_outputs_writes_the_last_steps_arrays_as_f32(tmp_path, monkeypatch):
+    """--dump-outputs: loss, metric, gradient, updated parameters (trainable ones only, named_parameters order) and float buffers as f32
+    .npy files; a vector over DUMP_CAP entries is written as the same seeded sample every time."""
+    import types
+    import numpy as np
+    bench = _load_bench()
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(3, 5), torch.nn.BatchNorm1d(5), torch.nn.Linear(5, 2))
+    model[0].weight.requires_grad_(False)
+    model(torch.randn(4, 3)).sum().backward()
+    flat = types.SimpleNamespace(scalars=torch.tensor([1.5, 0.25]))
+    tr = types.SimpleNamespace(model=model, ts=types.SimpleNamespace(loss=torch.tensor(1.5), flat=flat))
+    bench.dump_outputs(tr, str(tmp_path / "a"))
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("loss", "metric", "params", "grads", "buffers")}
+    assert all(v.dtype == np.float32 for v in got.values())
+    trainable = [p for p in model.parameters() if p.requires_grad]
+    assert got["loss"].tolist() == [1.5] and got["metric"].tolist() == [0.25]
+    np.testing.assert_array_equal(got["params"], torch.cat([p.detach().reshape(-1) for p in trainable]).numpy())
+    np.testing.assert_array_equal(got["grads"], torch.cat([p.grad.reshape(-1) for p in trainable]).numpy())
+    bn = model[1]
+    np.testing.assert_array_equal(got["buffers"], torch.cat([bn.running_mean, bn.running_var]).numpy())
+    monkeypatch.setattr(bench, "DUMP_CAP", 7)
+    bench.dump_outputs(tr, str(tmp_path / "b"))
+    bench.dump_outputs(tr, str(tmp_path / "c"))
+    b, c = np.load(tmp_path / "b" / "params.npy"), np.load(tmp_path / "c" / "params.npy")
+    assert b.shape == (7,) and np.array_equal(b, c) and set(b.tolist()) <= set(got["params"].tolist())
