@@ -371,6 +371,14 @@ def enable_sync_bn(on=True):
     SYNC_BN = bool(on)
 
 
+def _drop_salt(C):
+    """Salt of the fused dropout's mask hash (HF.bn_rows_train): the channel count on rank 0 or without a process group, the rank mixed in
+    on every other rank -- DDP ranks drop different elements, as the reference's per-rank seeds (main.py: seed + local_rank) make them."""
+    import torch.distributed as dist
+    rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+    return (int(C) + rank * 0x85EBCA6B) & 0xFFFFFFFF
+
+
 def sync_bn_active(training=True):
     import torch.distributed as dist
     return SYNC_BN and training and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
@@ -439,7 +447,7 @@ def _bn_rows(x, bn, training, relu=False, drop=None):
                  and bn.num_batches_tracked is not None and bn.momentum is not None and not _no_grad_needed(x, bn.weight, bn.bias)
                  and not sync_bn_active(True) and not drop.inplace)
         if fused:
-            return HF.bn_rows_train(x, bn, relu, drop_p=p, salt=x.shape[1], bump_pending=_pending_counters is not None)
+            return HF.bn_rows_train(x, bn, relu, drop_p=p, salt=_drop_salt(x.shape[1]), bump_pending=_pending_counters is not None)
         return drop(_bn_rows(x, bn, training, relu))
     if POOL_TRACE is not None and relu and x.dim() == 2 and not sync_bn_active(training or bn.running_mean is None):
         # test instrument: the BatchNorm on our kernels (or torch, on the host), the ReLU as a recorded / replayed gate

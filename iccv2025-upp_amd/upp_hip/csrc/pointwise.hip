@@ -126,8 +126,8 @@ __global__ __launch_bounds__(64 * kBnWaves) void bn_finalize_rows_kernel(const f
 
 // Dropout behind BatchNorm + ReLU (round 6; reference models/Point_MAE_unify_segment.py:424-427 `Conv1d, BatchNorm1d, ReLU, Dropout(0.5)`):
 // the mask of element i is a counter-based hash of (seed, i) -- recomputed by the backward kernels, never stored, no uniform tensor --
-// with seed = the BatchNorm layer's own num_batches_tracked (a device scalar the step bumps once per forward, inside the captured graph)
-// mixed with a per-site salt.  thresh = p * 2^32 (0: no dropout); kept values are scaled by 1 / (1 - p) as torch.nn.Dropout does.  The
+// with seed = the BatchNorm layer's num_batches_tracked for that forward (a device scalar the step bumps once per forward, inside the captured
+// graph; the caller hands forward and backward one snapshot of it) mixed with a salt (the channel count, and the rank on ranks > 0).  thresh = p * 2^32 (0: no dropout); kept values are scaled by 1 / (1 - p) as torch.nn.Dropout does.  The
 // stream is this library's own (lowbias32 mixer), not torch's Philox: dropout is a stochastic regulariser, parity tests run it at p = 0.
 struct BnDrop { const long long *seed; long long seed_add; unsigned salt, thresh; float scale; };
 __device__ __forceinline__ unsigned drop_seed(const BnDrop &d) {

@@ -1146,18 +1146,23 @@ class _BnRowsTrain(Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps, relu, drop_p=0.0, seed=None, salt=0, bump_pending=False):
         x = x.contiguous()
-        # the mask is a hash of the counter's value for THIS forward: when the host bumps its counters at the end of the forward
-        # (upp_layers.end_forward) the forward reads the old value + 1 and the backward, which runs behind the bump, the new value
-        drop = (drop_p, seed, 1 if bump_pending else 0, salt) if drop_p > 0.0 else None
+        # the mask is a hash of the counter's value for THIS forward (the old value + 1 when the host bumps its counters at the end of the
+        # forward, upp_layers.end_forward), taken here into a tensor of its own that forward and backward both read: the live counter
+        # may move any number of times before the backward runs (another forward of the layer, reset_running_stats, load_state_dict)
+        drop = snap = None
+        if drop_p > 0.0:
+            snap = seed + (1 if bump_pending else 0)           # one element-wise launch: capturable, no memset
+            drop = (drop_p, snap, 0, salt)
         y, mean, rstd = ops.bn_rows_fwd(x, gamma, beta, running_mean, running_var, momentum, eps, True, relu, want_stats=True, drop=drop)
-        ctx.save_for_backward(x, mean, rstd, gamma, beta)
-        ctx.relu, ctx.drop = relu, (None if drop is None else (drop_p, seed, 0, salt))
+        ctx.save_for_backward(x, mean, rstd, gamma, beta, snap)
+        ctx.relu, ctx.drop = relu, (None if drop is None else (drop_p, salt))
         return y
 
     @staticmethod
     def backward(ctx, g):
-        x, mean, rstd, gamma, beta = ctx.saved_tensors
-        g_x, g_gamma, g_beta = ops.bn_rows_bwd(x, g.contiguous(), mean, rstd, gamma, beta, ctx.relu, want_gx=ctx.needs_input_grad[0], drop=ctx.drop)
+        x, mean, rstd, gamma, beta, snap = ctx.saved_tensors
+        drop = None if ctx.drop is None else (ctx.drop[0], snap, 0, ctx.drop[1])
+        g_x, g_gamma, g_beta = ops.bn_rows_bwd(x, g.contiguous(), mean, rstd, gamma, beta, ctx.relu, want_gx=ctx.needs_input_grad[0], drop=drop)
         return (g_x, g_gamma if ctx.needs_input_grad[1] else None, g_beta if ctx.needs_input_grad[2] else None,
                 None, None, None, None, None, None, None, None, None)
 
@@ -1165,7 +1170,9 @@ class _BnRowsTrain(Function):
 def bn_rows_train(x, bn, relu=False, drop_p=0.0, salt=0, bump_pending=False):
     """Differentiable training-mode BatchNorm(+ReLU) over the rows of a channels-last (R,C) matrix; drop_p > 0: nn.Dropout(drop_p) on the
     output in the same passes, its masks a hash of (bn.num_batches_tracked, salt, element) -- the caller bumps the counter once per forward
-    (upp_layers.bump_counter, as nn.BatchNorm1d does); bump_pending: that bump has been queued for the end of the forward, not applied."""
+    (upp_layers.bump_counter, as nn.BatchNorm1d does); bump_pending: that bump has been queued for the end of the forward, not applied.
+    The forward snapshots the counter value it hashes and the backward uses that snapshot, so any number of forwards, a reset or a
+    load_state_dict may run between a forward and its backward."""
     momentum = 0.0 if bn.momentum is None else bn.momentum
     if drop_p > 0.0:
         return _BnRowsTrain.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, momentum, bn.eps, relu, float(drop_p),

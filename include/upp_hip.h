@@ -345,10 +345,12 @@ int upp_prop_weights_bwd(const float *c1, const float *c2, const int32_t *idx8, 
  *   upp_bn_rows_drop_fwd / _bwd (round 6): the training-mode pair with nn.Dropout(p) applied to the output in the same passes (the
  *                     segmentation head's `Conv1d, BatchNorm1d, ReLU, Dropout(0.5)`, reference models/Point_MAE_unify_segment.py:424-427):
  *                     y = dropout(relu?(bn(x))), kept values scaled by 1 / (1 - p).  The mask of element i is a counter-based hash of
- *                     (*seed + seed_add, salt, i) recomputed by the backward (nothing is stored; no uniform tensor is read): `seed` is a
- *                     DEVICE int64 the caller changes once per forward -- the layer's own num_batches_tracked -- so steps differ; seed_add
- *                     lets forward and backward of ONE step agree when the counter moves between them (a host that bumps its counters at
- *                     the end of the forward hands the forward 1 and the backward 0).  0 <= p < 1 (p = 0: the plain pair).
+ *                     (*seed + seed_add, salt, i) recomputed by the backward (no mask is stored; no uniform tensor is read): `seed` is
+ *                     a DEVICE int64 whose value changes once per forward -- derived from the layer's own num_batches_tracked -- so steps
+ *                     differ.  Backward and forward must be handed the same value of *seed + seed_add: the Python layer snapshots
+ *                     counter + 1 (a host that bumps its counters at the end of the forward) or the counter into a tensor of its own
+ *                     and passes it to both with seed_add 0, so the live counter may move any number of times in between.
+ *                     0 <= p < 1 (p = 0: the plain pair).
  *                     The stream of masks is this library's (not torch's Philox).
  *   upp_sqdist_topk : dist / idx (B,N,k) = the k nearest of the S points src[b] for every query q[b,n], by the reference's
  *                     square_distance form d = |a|^2 + |b|^2 - 2 a.b (models/modules.py:13-32), ascending (d, index):

@@ -66,6 +66,27 @@ def test_batch_counters_count_every_call_of_a_shared_module():
     assert int(b) == 2
 
 
+def test_dropout_salt_differs_per_rank(monkeypatch):
+    """The fused dropout's mask salt (upp_layers._drop_salt): the channel count alone without a process group and on rank 0 (so one-GPU
+    masks stay what they were), a different salt on every other rank -- and none that is the counter-driven seed of rank 0 a few steps
+    away (the kernel hashes counter * 0x9E3779B1 + salt: a salt step of a multiple of that constant would replay rank 0's masks)."""
+    import torch.distributed as dist
+    from models import upp_layers as L
+    for C in (128, 300, 512):
+        assert L._drop_salt(C) == C
+        monkeypatch.setattr(dist, "is_initialized", lambda: True)
+        salts = []
+        for r in range(8):
+            monkeypatch.setattr(dist, "get_rank", lambda r=r: r)
+            salts.append(L._drop_salt(C))
+        monkeypatch.undo()
+        assert salts[0] == C and len(set(salts)) == 8 and all(0 <= s < 2 ** 32 for s in salts)
+        inv = pow(0x9E3779B1, -1, 2 ** 32)
+        for s in salts[1:]:
+            shift = ((s - C) * inv) % 2 ** 32                     # the counter step whose seed this salt reproduces
+            assert min(shift, 2 ** 32 - shift) > 2 ** 24
+
+
 def test_bench_gpus_flag_launches_that_many_ranks(tmp_path):
     """`python bench.py --gpus 2` alone must start 2 ranks (torch.distributed.run child, 127.0.0.1 rendezvous), rank 0 prints ONE
     JSON line with n_gpus == 2, and a WORLD_SIZE that contradicts --gpus is refused.  --selftest-launch keeps the GPU out of it."""
