@@ -133,6 +133,8 @@ SIGNATURES = {
     "upp_linear_wgrad_splits": (_c_i, [_c_i, _c_i, _c_i]),
     "upp_linear_wgrad_f32": (_c_i, [_c_f, ctypes.c_longlong, _c_f, ctypes.c_longlong, _c_f, _c_i, _c_i, _c_i, _c_f]),
     "upp_adamw_flat": (_c_i, [_c_f] * 4 + [ctypes.c_longlong] * 2 + [_c_f] * 2 + [ctypes.c_float] * 6 + [_c_f]),
+    "upp_vote_points": (_c_i, [_c_f] * 5 + [_c_i] * 4 + [_c_f]),
+    "upp_vote_reduce": (_c_i, [_c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_f, _c_f, _c_f]),
 }
 
 _lib = None

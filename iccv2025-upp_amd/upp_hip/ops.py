@@ -387,13 +387,16 @@ class _WeightPlanes:
             return planes
         return e[1]
 
-    def refresh_trainable(self):
+    def refresh_trainable(self, owners=None):
+        """owners: a set of id()s of parameters -- only their images (an evaluation graph refreshes the weights of ITS model)."""
         import ctypes
         jobs = []
         for key, e in list(self.trainable.items()):
             owner = e[0]()
             if owner is None:
                 del self.trainable[key]
+            elif owners is not None and id(owner) not in owners:
+                continue
             else:
                 jobs.append((torch.as_strided(owner.detach(), e[3][0], e[3][1], e[3][2]), e[1], e[2]))
         if not jobs:
@@ -1246,6 +1249,48 @@ def ce_acc(logits, labels):
     dlogits = torch.empty_like(logits)
     _call(logits.device, "upp_ce_acc", _abi.ptr(logits), _abi.ptr(labels), _abi.ptr(out2), _abi.ptr(dlogits), B, C)
     return out2, dlogits
+
+
+def vote_points(superset, pick, scale=None, shift=None, out=None):
+    """superset (B,S,3) f32, pick (V,N) int32 indices into [0,S), scale / shift (V,B,3) f32 or None -> (V*B, N, 3) vote-major:
+    row v*B + b = superset[b, pick[v]] * scale[v,b] + shift[v,b] (upp_vote_points; bit-identical to misc.scale_translate's arithmetic)."""
+    _need(superset, "superset", torch.float32, 3, 3)
+    _need(pick, "pick", torch.int32, 2)
+    B, S, _ = superset.shape
+    V, N = pick.shape
+    for t, name in ((scale, "scale"), (shift, "shift")):
+        if t is not None:
+            _need(t, name, torch.float32, 3, 3)
+            if tuple(t.shape) != (V, B, 3):
+                raise RuntimeError(f"{name} must be ({V}, {B}, 3), got {tuple(t.shape)}")
+            _same_device(superset, t)
+    _same_device(superset, pick)
+    if out is None:
+        out = torch.empty((V * B, N, 3), dtype=torch.float32, device=superset.device)
+    else:
+        _need(out, "out", torch.float32, 3, 3)
+        if tuple(out.shape) != (V * B, N, 3):
+            raise RuntimeError(f"out must be ({V * B}, {N}, 3), got {tuple(out.shape)}")
+    _call(superset.device, "upp_vote_points", _abi.ptr(superset), _abi.ptr(pick), _abi.ptr(scale), _abi.ptr(shift), _abi.ptr(out),
+          B, S, N, V)
+    return out
+
+
+def vote_reduce(logits, labels, votes, n_valid, pred, counters):
+    """logits (votes*B, C) f32 vote-major, labels (B) int64 -> pred (B) int64 = first arg-max of the mean over the votes (written in
+    place); counters (2) int64 += (correct rows among the first n_valid, n_valid) (upp_vote_reduce: one workgroup, no memset)."""
+    _need(logits, "logits", torch.float32, 2)
+    _need(labels, "labels", torch.int64, 1)
+    _need(pred, "pred", torch.int64, 1)
+    _need(counters, "counters", torch.int64, 1)
+    _same_device(logits, labels, pred, counters)
+    B, V = labels.shape[0], int(votes)
+    if V < 1 or logits.shape[0] != V * B or pred.shape[0] != B or counters.shape[0] != 2:
+        raise RuntimeError(f"vote_reduce: logits {tuple(logits.shape)}, labels ({B},), pred {tuple(pred.shape)}, counters "
+                           f"{tuple(counters.shape)} do not fit {V} votes")
+    _call(logits.device, "upp_vote_reduce", _abi.ptr(logits), _abi.ptr(labels), V, B, logits.shape[1], int(n_valid), _abi.ptr(pred),
+          _abi.ptr(counters))
+    return pred, counters
 
 
 def bn_relu_drop_fwd(z, gamma, beta, running_mean, running_var, momentum, eps, training, u, p):

@@ -580,6 +580,21 @@ int upp_argsort_rows(const float *key, int B, int N, int descending, int64_t *or
 int upp_group_max_fwd(const float *x, int R, int k, int C, float *out, unsigned char *amax, void *stream);
 int upp_group_max_bwd(const float *g, const unsigned char *amax, int R, int k, int C, float *g_x, void *stream);
 
+/* ---- vote-batched evaluation (upp_hip/infer.py EvalStep; reference tools/runner_module.py:427-490 `test_vote`, :383-413 `validate`) ----
+ * upp_vote_points: out (V*B, N, 3), vote-major (row v*B + b) = superset[b][pick[v][i]] * scale[v][b] + shift[v][b] -- the V random
+ *   subsets of the FPS-ordered superset (B,S,3), one pick (V,N) int32 per vote shared by the batch, each scale/translate-augmented
+ *   (misc.scale_translate) in ONE launch.  scale / shift (V,B,3) may each be NULL (no multiply / no add: a plain gather).  The multiply
+ *   and the add round separately, as torch's `pc * s + t` does: bit-identical to it.  A pick outside [0,S) yields a NaN point.
+ * upp_vote_reduce: pred (B) int64 = the first arg-max over c of (sum_{v=0..V-1} logits[v*B + b][c]) / V (the sum in v order, then one
+ *   division; NaN ranks above everything, as torch.max), and counters (2) int64 += (number of b < n_valid with pred[b] == labels[b],
+ *   n_valid).  logits (V*B, C), labels (B) int64, 0 <= n_valid <= B (rows beyond n_valid: padding, predicted but not counted).  One
+ *   workgroup: deterministic, no atomics, no memset (a captured graph keeps working from its second replay on).
+ * Limits: V*B < 2^31; UPP_E_RANGE for n_valid outside [0,B]. */
+int upp_vote_points(const float *superset, const int32_t *pick, const float *scale, const float *shift, float *out,
+                    int B, int S, int N, int V, void *stream);
+int upp_vote_reduce(const float *logits, const int64_t *labels, int V, int B, int C, int n_valid, int64_t *pred,
+                    int64_t *counters, void *stream);
+
 /* ---- token-matrix Linear (exact f32 on the matrix cores) -------------------------------------
  * Replaces the nn.Linear layers of the Transformer blocks and their data gradients: Attention.qkv / .proj
  * (reference models/Point_MAE_pretask_dev.py:178,181 called :186,:194) and Mlp.fc1 / .fc2 (:158,:160 called
