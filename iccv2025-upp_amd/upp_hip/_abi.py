@@ -135,6 +135,8 @@ SIGNATURES = {
     "upp_adamw_flat": (_c_i, [_c_f] * 4 + [ctypes.c_longlong] * 2 + [_c_f] * 2 + [ctypes.c_float] * 6 + [_c_f]),
     "upp_vote_points": (_c_i, [_c_f] * 5 + [_c_i] * 4 + [_c_f]),
     "upp_vote_reduce": (_c_i, [_c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_f, _c_f, _c_f]),
+    "upp_seg_iou_counts": (_c_i, [_c_f, ctypes.c_longlong] + [_c_f] * 3 + [_c_i] * 5 + [_c_f] * 3),
+    "upp_seg_iou_accumulate": (_c_i, [_c_f] * 4 + [_c_i] * 5 + [_c_f] * 8),
 }
 
 _lib = None

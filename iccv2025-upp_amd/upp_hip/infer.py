@@ -17,7 +17,10 @@ and the shift from the default generator (evaluate.test_vote calls its transform
 Weights change between evaluations (training, load_state_dict, FlatAdamW re-pointing parameters into its flat buffer).  prepare()
 compares every parameter's and buffer's address, version and requires_grad with the capture-time snapshot: a moved version refreshes
 the derived weight caches in place (functional.refresh_caches: same buffers, the graph stays valid), a moved address or a changed
-requires_grad recaptures.  The bf16 plane images of the model's trainable weights are re-split by the graph's first launch."""
+requires_grad recaptures.  The bf16 plane images of the model's trainable weights are re-split by the graph's first launch.
+
+SegEvalStep does the same for the eval forward of a part-segmentation model (the reference's tools/runner_unify_seg.py:301-367): one
+graph per (B, N), the metric kernels (ops.seg_iou_update) after each replay."""
 import weakref
 
 import torch
@@ -234,4 +237,82 @@ class EvalStep:
         step = steps.get(key)
         if step is None:
             step = steps[key] = cls(model, batch_shape, npoints, **kw)
+        return step
+
+
+class SegEvalStep(EvalStep):
+    """The eval-mode forward of a part-segmentation model (Point_MAE_unify_seg) for a fixed (B, N, 3) batch as one HIP graph, plus the
+    metric launches (ops.seg_iou_update) after each replay with the batch's real row count.  The reference's protocol
+    (tools/runner_unify_seg.py:301-367): model(points, one-hot label, completion_prompt=False, denoise=False, point_num=N), the label
+    points being the points.  Static inputs: `pts` (B, N, 3) and `onehot` (B, num_classes), filled outside the graph; `target` (B, N)
+    int64 and `pred` (B, N) int64 serve the metric.  A ragged last batch is padded (pad_batch), which needs a forward that works per
+    sample: a model whose forward reads across samples (mixes_samples) is refused.  The weights are tracked as EvalStep does
+    (prepare(): a moved version refreshes the derived caches in place, a moved address or requires_grad recaptures)."""
+
+    def __init__(self, model, batch_shape, num_classes=16, use_graph=True):
+        self._model = weakref.ref(model)
+        self.device = next(model.parameters()).device
+        if self.device.type != 'cuda':
+            raise RuntimeError("SegEvalStep runs the HIP kernels: the model must live on a HIP device")
+        if mixes_samples(model):
+            raise ValueError("SegEvalStep pads a ragged batch, which needs a forward that works per sample; this model's reads across "
+                             "the samples of its batch (gather_idx = false)")
+        B, N, c = (int(x) for x in batch_shape)
+        if c != 3:
+            raise ValueError("batch_shape must be (B, N, 3)")
+        self.B, self.N, self.num_classes = B, N, int(num_classes)
+        self.use_graph = bool(use_graph)
+        dev = self.device
+        self.pts = torch.zeros((B, N, 3), device=dev)
+        self.labels = torch.zeros(B, dtype=torch.long, device=dev)
+        self.onehot = torch.zeros((B, self.num_classes), device=dev)
+        self._classes = torch.arange(self.num_classes, device=dev)
+        self.target = torch.zeros((B, N), dtype=torch.long, device=dev)
+        self.pred = torch.zeros((B, N), dtype=torch.long, device=dev)
+        self.logp = None
+        self._graph = None
+        self._snap = None
+        self._owners = self._trainable()
+        HF.refresh_caches(model)
+
+    def _evaluate(self):
+        was = ops.PLANES.managed
+        ops.PLANES.managed = True
+        try:
+            with torch.no_grad():
+                ops.PLANES.refresh_trainable(self._owners)     # (the graph's first launch: the model's trainable weights, split)
+                self.logp = self.model(self.pts, self.onehot, completion_prompt=False, denoise=False, point_num=self.N)
+        finally:
+            ops.PLANES.managed = was
+
+    def run(self, points, label, target, metric):
+        """One batch of n <= B shapes: points (n, N, 3), label (n,) or (n, 1), target (n, N) -> pred (n, N) int64 (a view of the
+        static `pred`), the metric (utils.evaluate.SegMetric) updated with the n real shapes."""
+        n = points.shape[0]
+        if tuple(points.shape[1:]) != (self.N, 3):
+            raise ValueError("points %s do not fit a step of (%d, %d, 3)" % (tuple(points.shape), self.B, self.N))
+        if tuple(target.shape) != (n, self.N):
+            raise ValueError("target %s does not fit points %s" % (tuple(target.shape), tuple(points.shape)))
+        pad_batch(points, self.B, out=self.pts)
+        pad_batch(label.reshape(-1), self.B, out=self.labels)
+        pad_batch(target, self.B, out=self.target)
+        self.onehot.copy_(self.labels.view(-1, 1) == self._classes)
+        with _eval_mode(self.model):
+            if self.use_graph:
+                if self._graph is None:
+                    self._capture()
+                self._graph.replay()
+            else:
+                self._evaluate()
+        metric.update(self.logp, self.target, n_valid=n, pred=self.pred)
+        return self.pred[:n]
+
+    @classmethod
+    def cached(cls, model, batch_shape, num_classes=16, **kw):
+        """One step per model and (B, N, num_classes, use_graph)."""
+        steps = _STEPS.setdefault(model, {})
+        key = ('seg', tuple(int(x) for x in batch_shape), int(num_classes)) + tuple(sorted(kw.items()))
+        step = steps.get(key)
+        if step is None:
+            step = steps[key] = cls(model, batch_shape, num_classes, **kw)
         return step

@@ -1293,6 +1293,82 @@ def vote_reduce(logits, labels, votes, n_valid, pred, counters):
     return pred, counters
 
 
+class SegAccumulator:
+    """Device sums of a part-segmentation evaluation (upp_seg_iou_accumulate adds into them): counters (3) int64 = (correct points, seen
+    points, invalid shapes), part_seen / part_correct (P) int64, cat_sum (C) f64 and cat_cnt (C) int64 = the shape IoUs per category and
+    their count.  shape_iou (B) f64 / shape_cat (B) int32 hold the last update's shapes.  The int32 scratch of upp_seg_iou_counts is
+    zeroed once here and re-zeroed by every accumulate launch, so an update issues kernel launches only."""
+
+    def __init__(self, num_part, num_classes, device):
+        dev = torch.device(device)
+        if dev.type != 'cuda':
+            raise RuntimeError("SegAccumulator lives on a HIP (cuda) device; upp_hip has no CPU path")
+        self.P, self.C, self.device = int(num_part), int(num_classes), dev
+        self.counters = torch.zeros(3, dtype=torch.int64, device=dev)
+        self.part_seen = torch.zeros(self.P, dtype=torch.int64, device=dev)
+        self.part_correct = torch.zeros(self.P, dtype=torch.int64, device=dev)
+        self.cat_sum = torch.zeros(self.C, dtype=torch.float64, device=dev)
+        self.cat_cnt = torch.zeros(self.C, dtype=torch.int64, device=dev)
+        self.scratch = self.shape_iou = self.shape_cat = None
+        self.batch = 0
+
+    def zero_(self):
+        for t in (self.counters, self.part_seen, self.part_correct, self.cat_sum, self.cat_cnt):
+            t.zero_()
+        return self
+
+    def reserve(self, batch):
+        """Room for updates of up to `batch` shapes (a larger batch reallocates the scratch, zeroed)."""
+        if batch > self.batch:
+            self.scratch = torch.zeros(3 * batch * self.P + 2 * self.P + 1, dtype=torch.int32, device=self.device)
+            self.shape_iou = torch.empty(batch, dtype=torch.float64, device=self.device)
+            self.shape_cat = torch.empty(batch, dtype=torch.int32, device=self.device)
+            self.batch = batch
+        return self
+
+
+def seg_iou_update(logp, target, part_cat, cat_range, acc, n_valid=None, pred=None):
+    """The part-segmentation metrics of shapes [0, n_valid) of one batch, added into `acc` (a SegAccumulator) in two launches
+    (upp_seg_iou_counts, upp_seg_iou_accumulate).  logp (B, N, P) f32 whose rows may be strided (stride(1) >= P, a view of a padded head
+    output), target (B, N) int64, part_cat (P) int32, cat_range (C, 2) int32.  pred: None or (B, N) int64, written with the in-category
+    arg-max of every row (padding rows included).  -> acc.shape_iou[:n_valid] (the IoU of each shape, f64)."""
+    if not isinstance(logp, torch.Tensor) or not logp.is_cuda:
+        raise RuntimeError("logp must be a HIP (cuda) tensor; upp_hip has no CPU path")
+    if logp.dtype != torch.float32 or logp.dim() != 3:
+        raise RuntimeError(f"logp must be a 3-D float32 tensor, got {logp.dtype} {tuple(logp.shape)}")
+    B, N, P = logp.shape
+    ld = logp.stride(1)
+    if logp.stride(2) != 1 or ld < P or logp.stride(0) != N * ld:
+        raise RuntimeError(f"logp rows must be unit-stride with a common row stride >= {P}, got strides {logp.stride()}")
+    _need(target, "target", torch.int64, 2)
+    _need(part_cat, "part_cat", torch.int32, 1)
+    _need(cat_range, "cat_range", torch.int32, 2, 2)
+    if not isinstance(acc, SegAccumulator):
+        raise TypeError("acc must be a SegAccumulator")
+    _same_device(logp, target, part_cat, cat_range, acc.counters)
+    C = cat_range.shape[0]
+    if tuple(target.shape) != (B, N):
+        raise RuntimeError(f"target must be ({B}, {N}), got {tuple(target.shape)}")
+    if part_cat.shape[0] != P or acc.P != P or acc.C != C:
+        raise RuntimeError(f"seg_iou_update: logp has {P} parts; the table ({part_cat.shape[0]} parts, {C} categories) and the "
+                           f"accumulator ({acc.P}, {acc.C}) must agree")
+    if pred is not None:
+        _need(pred, "pred", torch.int64, 2)
+        _same_device(logp, pred)
+        if tuple(pred.shape) != (B, N):
+            raise RuntimeError(f"pred must be ({B}, {N}), got {tuple(pred.shape)}")
+    n_valid = B if n_valid is None else int(n_valid)
+    if not 0 <= n_valid <= B:
+        raise RuntimeError(f"n_valid {n_valid} outside [0, {B}]")
+    acc.reserve(B)
+    _call(logp.device, "upp_seg_iou_counts", _abi.ptr(logp), ld, _abi.ptr(target), _abi.ptr(part_cat), _abi.ptr(cat_range), B, N, P, C,
+          n_valid, _abi.ptr(pred), _abi.ptr(acc.scratch))
+    _call(logp.device, "upp_seg_iou_accumulate", _abi.ptr(acc.scratch), _abi.ptr(target), _abi.ptr(part_cat), _abi.ptr(cat_range), B,
+          N, P, C, n_valid, _abi.ptr(acc.shape_iou), _abi.ptr(acc.shape_cat), _abi.ptr(acc.cat_sum), _abi.ptr(acc.cat_cnt),
+          _abi.ptr(acc.part_seen), _abi.ptr(acc.part_correct), _abi.ptr(acc.counters))
+    return acc.shape_iou[:n_valid]
+
+
 def bn_relu_drop_fwd(z, gamma, beta, running_mean, running_var, momentum, eps, training, u, p):
     _need(z, "z", torch.float32, ndim=2)
     R, C = z.shape

@@ -595,6 +595,27 @@ int upp_vote_points(const float *superset, const int32_t *pick, const float *sca
 int upp_vote_reduce(const float *logits, const int64_t *labels, int V, int B, int C, int n_valid, int64_t *pred,
                     int64_t *counters, void *stream);
 
+/* ---- part-segmentation metrics (utils/evaluate.py SegMetric; reference tools/runner_unify_seg.py:301-367 `validate`) ----
+ * The part table is data: part_cat (P) int32 = the category of part l; cat_range (C, 2) int32 = [lo, n) of category c's contiguous parts.
+ * upp_seg_iou_counts: logp (B, N, >= P) f32 with row stride ld >= P (element (b, n, l) at (b*N + n)*ld + l), target (B, N) int64.  The
+ *   category of shape b is part_cat[target[b][0]]; pred[b][n] = lo + the first arg-max of logp[b][n][lo .. lo+n) (np.argmax: equal
+ *   values -> the lower index, a NaN wins, the first NaN first); -1 for a shape whose target[b][0] is outside [0, P).  pred (B, N) int64
+ *   may be NULL.  Shapes b < n_valid add their integer histograms into scratch (int32, 3 B P + 2 P + 1, zero on entry): per shape and
+ *   part the intersection / predicted / target counts, per part the seen / correct counts, the correct points.  Integer atomics only:
+ *   deterministic.  Shapes b >= n_valid (padding) get pred only.
+ * upp_seg_iou_accumulate: one workgroup, after upp_seg_iou_counts with the same (scratch, target, table, B, N, P, C, n_valid).
+ *   shape_iou (B) f64 = per shape b < n_valid the mean over its category's parts of IoU_l = |T_l & P_l| / |T_l | P_l| (1.0 when the
+ *   part is in neither): a sequential float64 sum in part order, then one division (np.mean of fewer than 8 values, bit for bit);
+ *   shape_cat (B) int32 its category (-1, IoU NaN: an invalid shape).  cat_sum (C) f64 += the IoUs per category in shape order, cat_cnt
+ *   (C) int64 += the shape counts, part_seen / part_correct (P) int64 += the part counters, counters (3) int64 += (correct points,
+ *   n_valid * N, invalid shapes).  Then the scratch is zeroed by the kernel (no memset node in a captured evaluation).
+ * Limits: P <= 1024, C <= 256, B <= 65535, B*N < 2^31; UPP_E_RANGE for n_valid outside [0, B]. */
+int upp_seg_iou_counts(const float *logp, long long ld, const int64_t *target, const int32_t *part_cat, const int32_t *cat_range,
+                       int B, int N, int P, int C, int n_valid, int64_t *pred, int32_t *scratch, void *stream);
+int upp_seg_iou_accumulate(int32_t *scratch, const int64_t *target, const int32_t *part_cat, const int32_t *cat_range, int B, int N,
+                           int P, int C, int n_valid, double *shape_iou, int32_t *shape_cat, double *cat_sum, int64_t *cat_cnt,
+                           int64_t *part_seen, int64_t *part_correct, int64_t *counters, void *stream);
+
 /* ---- token-matrix Linear (exact f32 on the matrix cores) -------------------------------------
  * Replaces the nn.Linear layers of the Transformer blocks and their data gradients: Attention.qkv / .proj
  * (reference models/Point_MAE_pretask_dev.py:178,181 called :186,:194) and Mlp.fc1 / .fc2 (:158,:160 called
