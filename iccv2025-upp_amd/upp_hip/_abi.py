@@ -137,6 +137,9 @@ SIGNATURES = {
     "upp_vote_reduce": (_c_i, [_c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_f, _c_f, _c_f]),
     "upp_seg_iou_counts": (_c_i, [_c_f, ctypes.c_longlong] + [_c_f] * 3 + [_c_i] * 5 + [_c_f] * 3),
     "upp_seg_iou_accumulate": (_c_i, [_c_f] * 4 + [_c_i] * 5 + [_c_f] * 8),
+    "upp_completion_cloud_metrics": (_c_i, [_c_f] * 6 + [_c_i] * 3 + [ctypes.c_double, _c_i] + [_c_f] * 3),
+    "upp_completion_masked_cd": (_c_i, [_c_f] * 2 + [_c_i] * 3 + [_c_f] * 3),
+    "upp_completion_accumulate": (_c_i, [_c_f] * 3 + [_c_i] * 4 + [_c_f] * 5),
 }
 
 _lib = None

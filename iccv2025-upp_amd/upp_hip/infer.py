@@ -20,7 +20,11 @@ the derived weight caches in place (functional.refresh_caches: same buffers, the
 requires_grad recaptures.  The bf16 plane images of the model's trainable weights are re-split by the graph's first launch.
 
 SegEvalStep does the same for the eval forward of a part-segmentation model (the reference's tools/runner_unify_seg.py:301-367): one
-graph per (B, N), the metric kernels (ops.seg_iou_update) after each replay."""
+graph per (B, N), the metric kernels (ops.seg_iou_update) after each replay.
+
+CompletionEvalStep does it for the pre-task `validate` of a completion model (the reference's tools/runner_pretask.py:314-426): one
+graph per (B, N, V) holds the crop, the FPS launches, the forward, both Chamfer searches and the per-cloud metric kernels; the
+accumulation (ops.completion_accumulate) follows each replay."""
 import weakref
 
 import torch
@@ -315,4 +319,93 @@ class SegEvalStep(EvalStep):
         step = steps.get(key)
         if step is None:
             step = steps[key] = cls(model, batch_shape, num_classes, **kw)
+        return step
+
+
+class CompletionEvalStep(EvalStep):
+    """The pre-task evaluation of a fixed (B, N, 3) batch of complete clouds from V viewpoints as one HIP graph
+    (utils.evaluate.completion_outputs: the crop distances, upp_argsort_rows, the gathers, the three FPS launches, the eval forward, the
+    concatenations; then ops.completion_cloud_metrics: two upp_chamfer_fwd and the per-cloud metric kernels into the step's own rows).
+    After each replay ops.completion_accumulate adds the rows of the batch's real clouds into the metric's sums: its row count n_valid
+    changes with a smaller batch, which run() pads (pad_batch) -- so a model whose forward reads across samples (mixes_samples) is
+    refused.  (validate_completion_captured gives a ragged last batch a step of its own size instead, to stay bit-identical to the eager
+    protocol.)  Static input: `gt` (B, N, 3) and `category` (B,) int64, filled outside the graph.  The weights are tracked as EvalStep
+    does (prepare(): a moved version refreshes the derived caches in place, a moved address or requires_grad recaptures)."""
+
+    def __init__(self, model, batch_shape, mode='easy', in_detail=False, npoints=1024, threshold=0.01, max_clouds=None, use_graph=True):
+        from utils import evaluate
+        self._model = weakref.ref(model)
+        self.device = next(model.parameters()).device
+        if self.device.type != 'cuda':
+            raise RuntimeError("CompletionEvalStep runs the HIP kernels: the model must live on a HIP device")
+        if mixes_samples(model):
+            raise ValueError("CompletionEvalStep pads a ragged batch, which needs a forward that works per sample; this model's reads "
+                             "across the samples of its batch (gather_idx = false)")
+        B, N, c = (int(x) for x in batch_shape)
+        if c != 3:
+            raise ValueError("batch_shape must be (B, N, 3)")
+        self.B, self.N, self.npoints = B, N, int(npoints)
+        self.num_crop = evaluate.crop_count(N, mode)
+        if N - self.num_crop < self.npoints:
+            raise ValueError("%s mode keeps %d of %d points, fewer than the %d the model takes" % (mode, N - self.num_crop, N, npoints))
+        self.detail, self.threshold, self.max_clouds = bool(in_detail), float(threshold), max_clouds
+        self.use_graph = bool(use_graph)
+        dev = self.device
+        self.centers = torch.tensor(evaluate.viewpoints(self.detail), dtype=torch.float32, device=dev)
+        self.V = self.centers.shape[0]
+        self.gt = torch.zeros((B, N, 3), device=dev)
+        self.category = torch.zeros(B, dtype=torch.long, device=dev)
+        self.rows = ops.CompletionAccumulator(1, dev).reserve(self.V * B)
+        self.coarse = self.dense = None
+        self._graph = None
+        self._snap = None
+        self._owners = self._trainable()
+        HF.refresh_caches(model)
+
+    def _evaluate(self):
+        from utils import evaluate
+        was = ops.PLANES.managed
+        ops.PLANES.managed = True
+        try:
+            with torch.no_grad():
+                ops.PLANES.refresh_trainable(self._owners)     # (the graph's first launch: the model's trainable weights, split)
+                self.coarse, self.dense = evaluate.completion_outputs(self.model, self.gt, self.centers, self.num_crop, self.npoints,
+                                                                      self.max_clouds)
+                ops.completion_cloud_metrics(self.coarse, self.dense, self.gt, self.rows, self.detail, self.threshold)
+        finally:
+            ops.PLANES.managed = was
+
+    def run(self, gt, category, metric):
+        """One batch of n <= B complete clouds gt (n, N, 3) and their categories (n,) (None: losses only; ignored unless in_detail) ->
+        the metric (utils.evaluate.CompletionMetric) updated with the n real clouds."""
+        n = gt.shape[0]
+        if tuple(gt.shape[1:]) != (self.N, 3):
+            raise ValueError("gt %s does not fit a step of (%d, %d, 3)" % (tuple(gt.shape), self.B, self.N))
+        if metric.threshold != self.threshold:
+            raise ValueError("the metric's threshold %r is not the step's %r" % (metric.threshold, self.threshold))
+        cat = None
+        if self.detail and category is not None:
+            category = torch.as_tensor(category).reshape(-1)
+            if category.shape[0] != n or category.dtype.is_floating_point:
+                raise ValueError("category must be (%d,) integers" % n)
+            cat = pad_batch(category.to(self.device, torch.long), self.B, out=self.category)
+        pad_batch(gt, self.B, out=self.gt)
+        with _eval_mode(self.model):
+            if self.use_graph:
+                if self._graph is None:
+                    self._capture()
+                self._graph.replay()
+            else:
+                self._evaluate()
+        ops.completion_accumulate(metric.device_sums(self.device), self.V, self.B, cat, n, rows=self.rows)
+        return metric
+
+    @classmethod
+    def cached(cls, model, batch_shape, **kw):
+        """One step per model and (B, N, mode, in_detail, npoints, threshold, ...)."""
+        steps = _STEPS.setdefault(model, {})
+        key = ('completion', tuple(int(x) for x in batch_shape)) + tuple(sorted(kw.items()))
+        step = steps.get(key)
+        if step is None:
+            step = steps[key] = cls(model, batch_shape, **kw)
         return step

@@ -1369,6 +1369,124 @@ def seg_iou_update(logp, target, part_cat, cat_range, acc, n_valid=None, pred=No
     return acc.shape_iou[:n_valid]
 
 
+class CompletionAccumulator:
+    """Device sums of a point-completion evaluation (upp_completion_accumulate adds into them): loss_sum (4) f64 = 1000 x the sparse
+    CD-L1, sparse CD-L2, dense CD-L1, dense CD-L2 summed over (cloud, viewpoint) pairs; counters (2) int64 = (pairs, pairs of a cloud
+    whose category is outside [0, C)); cat_sum (C, 3) f64 = per category the sums of F-Score, 1000 CDL1 and 1000 CDL2, cat_cnt (C) int64
+    their count.  The per-(cloud, viewpoint) rows of the last update -- sparse / dense (R, 8) f64 and sparse_counts / dense_counts (R, 4)
+    int32, include/upp_hip.h upp_completion_cloud_metrics -- are reserved per row count; every launch writes them whole, so an update
+    issues kernel launches only (no memset)."""
+
+    def __init__(self, num_categories, device):
+        dev = torch.device(device)
+        if dev.type != 'cuda':
+            raise RuntimeError("CompletionAccumulator lives on a HIP (cuda) device; upp_hip has no CPU path")
+        self.C, self.device = int(num_categories), dev
+        if self.C < 1:
+            raise ValueError("num_categories must be positive")
+        self.loss_sum = torch.zeros(4, dtype=torch.float64, device=dev)
+        self.counters = torch.zeros(2, dtype=torch.int64, device=dev)
+        self.cat_sum = torch.zeros((self.C, 3), dtype=torch.float64, device=dev)
+        self.cat_cnt = torch.zeros(self.C, dtype=torch.int64, device=dev)
+        self.sparse = self.dense = self.sparse_counts = self.dense_counts = None
+        self.rows = 0
+
+    def zero_(self):
+        for t in (self.loss_sum, self.counters, self.cat_sum, self.cat_cnt):
+            t.zero_()
+        return self
+
+    def reserve(self, rows):
+        """Room for updates of up to `rows` (cloud, viewpoint) pairs (a larger count reallocates)."""
+        if rows > self.rows:
+            dev = self.device
+            self.sparse = torch.empty((rows, 8), dtype=torch.float64, device=dev)
+            self.dense = torch.empty((rows, 8), dtype=torch.float64, device=dev)
+            self.sparse_counts = torch.empty((rows, 4), dtype=torch.int32, device=dev)
+            self.dense_counts = torch.empty((rows, 4), dtype=torch.int32, device=dev)
+            self.rows = rows
+        return self
+
+
+def _completion_inputs(coarse, dense, gt, acc):
+    _need(coarse, "coarse", torch.float32, 3, 3)
+    _need(dense, "dense", torch.float32, 3, 3)
+    _need(gt, "gt", torch.float32, 3, 3)
+    if not isinstance(acc, CompletionAccumulator):
+        raise TypeError("acc must be a CompletionAccumulator")
+    _same_device(coarse, dense, gt, acc.loss_sum)
+    R, B = coarse.shape[0], gt.shape[0]
+    if dense.shape[0] != R or B < 1 or R < B or R % B:
+        raise RuntimeError(f"coarse {tuple(coarse.shape)} and dense {tuple(dense.shape)} must hold V x {B} clouds, viewpoint-major, "
+                           f"for gt {tuple(gt.shape)}")
+    if min(coarse.shape[1], dense.shape[1], gt.shape[1]) < 1:
+        raise RuntimeError("every cloud needs at least one point")
+    return R, B, R // B
+
+
+def completion_cloud_metrics(coarse, dense, gt, acc, detail, th=0.01):
+    """The per-(cloud, viewpoint) rows of one viewpoint-expanded batch, all on the device: coarse (V B, nc, 3) and dense (V B, nd, 3) f32
+    against gt (B, N, 3), row v B + b against gt[b].  upp_chamfer_fwd on both pairs, upp_completion_cloud_metrics on each (F-Score and
+    the zero-sum flag on the dense pair when `detail`), then upp_completion_masked_cd (its workgroups return at once unless a pair holds
+    a zero-sum point).  -> (V, B); the rows are acc.sparse / acc.dense[:V B]."""
+    R, B, V = _completion_inputs(coarse, dense, gt, acc)
+    th = float(th)
+    if not (th > 0.0 and th != float('inf')):
+        raise RuntimeError(f"th must be positive and finite, got {th}")
+    target = gt if V == 1 else gt.repeat(V, 1, 1)
+    acc.reserve(R)
+    dev = gt.device
+    for pts, stats, counts, det in ((coarse, acc.sparse, acc.sparse_counts, 0), (dense, acc.dense, acc.dense_counts, int(bool(detail)))):
+        d1, d2, i1, i2 = chamfer_fwd(pts, target)
+        n, m = pts.shape[1], target.shape[1]
+        _call(dev, "upp_completion_cloud_metrics", _abi.ptr(pts), _abi.ptr(target), _abi.ptr(d1), _abi.ptr(i1), _abi.ptr(d2), _abi.ptr(i2),
+              R, n, m, th, det, _abi.ptr(stats), _abi.ptr(counts))
+        if det:
+            _call(dev, "upp_completion_masked_cd", _abi.ptr(pts), _abi.ptr(target), R, n, m, _abi.ptr(counts), _abi.ptr(stats))
+    return V, B
+
+
+def completion_accumulate(acc, V, B, category=None, n_valid=None, rows=None):
+    """Add the rows of clouds [0, n_valid) of the last completion_cloud_metrics(V B rows) into acc, in the reference's order (cloud, then
+    viewpoint).  category: None (losses only) or (B,) int64 on acc's device, the detail metrics then go to its categories.  rows: the
+    CompletionAccumulator whose sparse / dense rows are read (default acc; a captured step keeps its own)."""
+    rows = acc if rows is None else rows
+    if not isinstance(acc, CompletionAccumulator) or not isinstance(rows, CompletionAccumulator):
+        raise TypeError("acc and rows must be CompletionAccumulators")
+    V, B = int(V), int(B)
+    if V < 1 or B < 1 or V * B > rows.rows:
+        raise RuntimeError(f"{V} x {B} rows: not what the accumulator holds ({rows.rows} reserved)")
+    _same_device(acc.loss_sum, rows.loss_sum)
+    n_valid = B if n_valid is None else int(n_valid)
+    if not 0 <= n_valid <= B:
+        raise RuntimeError(f"n_valid {n_valid} outside [0, {B}]")
+    if category is not None:
+        _need(category, "category", torch.int64, 1)
+        _same_device(category, acc.loss_sum)
+        if category.shape[0] != B:
+            raise RuntimeError(f"category must be ({B},), got {tuple(category.shape)}")
+    _call(acc.device, "upp_completion_accumulate", _abi.ptr(rows.sparse), _abi.ptr(rows.dense), _abi.ptr(category), V, B, acc.C, n_valid,
+          _abi.ptr(acc.loss_sum), _abi.ptr(acc.counters), _abi.ptr(acc.cat_sum), _abi.ptr(acc.cat_cnt))
+    return acc
+
+
+def completion_update(coarse, dense, gt, acc, category=None, n_valid=None, th=0.01):
+    """One viewpoint-expanded batch into acc (a CompletionAccumulator): completion_cloud_metrics (detail = a category is given), then
+    completion_accumulate over clouds [0, n_valid).  Every tensor is checked (f32 contiguous (.., .., 3) clouds on one device, int64
+    categories) before the first launch.  -> acc."""
+    R, B, V = _completion_inputs(coarse, dense, gt, acc)
+    n_valid = B if n_valid is None else int(n_valid)
+    if not 0 <= n_valid <= B:
+        raise RuntimeError(f"n_valid {n_valid} outside [0, {B}]")
+    if category is not None:
+        _need(category, "category", torch.int64, 1)
+        _same_device(category, gt)
+        if category.shape[0] != B:
+            raise RuntimeError(f"category must be ({B},), got {tuple(category.shape)}")
+    completion_cloud_metrics(coarse, dense, gt, acc, category is not None, th)
+    return completion_accumulate(acc, V, B, category, n_valid)
+
+
 def bn_relu_drop_fwd(z, gamma, beta, running_mean, running_var, momentum, eps, training, u, p):
     _need(z, "z", torch.float32, ndim=2)
     R, C = z.shape

@@ -333,3 +333,304 @@ def validate_seg_captured(model, batches, num_part=50, num_classes=16, distribut
         model.train(was)
     out = metric.compute(distributed)
     return (out, torch.cat(preds) if preds else torch.empty((0, 0), dtype=torch.long)) if return_predictions else out
+
+
+# ------------------------------------------------------------------ point completion (reference tools/runner_pretask.py:314-426)
+# The viewpoints of the reference's `validate` (not normalised), in its order; in_detail=False uses the first one only.
+VIEWPOINTS = ((1., 1., 1.), (1., 1., -1.), (1., -1., 1.), (-1., 1., 1.), (-1., -1., 1.), (-1., 1., -1.), (1., -1., -1.), (-1., -1., -1.))
+CROP_RATIO = {'easy': 1 / 4, 'median': 1 / 2, 'hard': 3 / 4}        # (the reference spells the middle mode 'median')
+CENTERS = 128                                                       # misc.fps(partial, 128): the visible half of the coarse output
+
+
+def crop_count(num_points, mode):
+    """The points removed from a cloud of num_points in `mode`: int(N * ratio), as the reference computes num_crop."""
+    if mode not in CROP_RATIO:
+        raise ValueError("mode must be one of %s, got %r" % (sorted(CROP_RATIO), mode))
+    return int(num_points * CROP_RATIO[mode])
+
+
+def viewpoints(in_detail):
+    return VIEWPOINTS if in_detail else VIEWPOINTS[:1]
+
+
+class _CompletionHostSums:
+    """CompletionMetric's sums on the CPU: the fields of upp_hip.ops.CompletionAccumulator."""
+
+    def __init__(self, C):
+        self.loss_sum = torch.zeros(4, dtype=torch.float64)
+        self.counters = torch.zeros(2, dtype=torch.int64)
+        self.cat_sum = torch.zeros((C, 3), dtype=torch.float64)
+        self.cat_cnt = torch.zeros(C, dtype=torch.int64)
+
+
+def _nn64(a, b, chunk=512):
+    """a (n, 3), b (m, 3) float64 -> (squared distance to the nearest point of b, its index: the first among equal minima)."""
+    d_out, i_out = [], []
+    for s in range(0, a.shape[0], chunk):
+        q = a[s:s + chunk]
+        dx, dy, dz = (q[:, None, k] - b[None, :, k] for k in range(3))
+        d, i = ((dx * dx + dy * dy) + dz * dz).min(1)
+        d_out.append(d)
+        i_out.append(i)
+    return torch.cat(d_out), torch.cat(i_out)
+
+
+def _zero_sum(p):
+    """(n, 3) f32 -> (n,) bool: the f32 coordinate sum (x + y) + z is exactly 0 (the reference's torch.sum(xyz, dim=2).ne(0))."""
+    p = p.float()
+    return (p[:, 0] + p[:, 1]) + p[:, 2] == 0
+
+
+def _completion_row_host(x1, x2, detail, th):
+    """One cloud pair on the CPU, in float64: the 8 values of a upp_completion_cloud_metrics row (with the masked CDs)."""
+    a, b = x1.double(), x2.double()
+    d1, _ = _nn64(a, b)
+    d2, _ = _nn64(b, a)
+    md1, md2 = float(d1.mean()), float(d2.mean())
+    mq1, mq2 = float(d1.sqrt().mean()), float(d2.sqrt().mean())
+    f, cdl1, cdl2 = 0.0, (mq1 + mq2) / 2.0, md1 + md2
+    if detail:
+        precision = float(int((d1.sqrt() < th).sum())) / float(a.shape[0])
+        recall = float(int((d2.sqrt() < th).sum())) / float(b.shape[0])
+        f = 2 * recall * precision / (recall + precision) if recall + precision else 0.
+        z1, z2 = _zero_sum(x1), _zero_sum(x2)
+        if bool(z1.any()) or bool(z2.any()):
+            a, b = a[~z1], b[~z2]
+            if a.shape[0] == 0 or b.shape[0] == 0:
+                cdl1 = cdl2 = float('nan')
+            else:
+                e1, _ = _nn64(a, b)
+                e2, _ = _nn64(b, a)
+                cdl1 = (float(e1.sqrt().mean()) + float(e2.sqrt().mean())) / 2.0
+                cdl2 = float(e1.mean()) + float(e2.mean())
+    return md1, md2, mq1, mq2, f, cdl1, cdl2
+
+
+def _completion_update_host(coarse, dense, gt, sums, category, n_valid, th):
+    """upp_completion_cloud_metrics + upp_completion_accumulate in float64 on the CPU, in the same order (cloud, then viewpoint)."""
+    B = gt.shape[0]
+    V = coarse.shape[0] // B
+    loss = sums.loss_sum.tolist()
+    counters = sums.counters.tolist()
+    cs, cc = sums.cat_sum.tolist(), sums.cat_cnt.tolist()
+    C = len(cc)
+    cats = None if category is None else category.tolist()
+    for b in range(n_valid):
+        for v in range(V):
+            r = v * B + b
+            sp = _completion_row_host(coarse[r], gt[b], False, th)
+            de = _completion_row_host(dense[r], gt[b], cats is not None, th)
+            for k, (row, l1) in enumerate(((sp, True), (sp, False), (de, True), (de, False))):
+                loss[k] += ((row[2] + row[3]) / 2.0 if l1 else row[0] + row[1]) * 1000.0
+            counters[0] += 1
+            if cats is None:
+                continue
+            c = cats[b]
+            if not 0 <= c < C:
+                counters[1] += 1
+                continue
+            cs[c] = [cs[c][0] + de[4], cs[c][1] + de[5] * 1000.0, cs[c][2] + de[6] * 1000.0]
+            cc[c] += 1
+    sums.loss_sum.copy_(torch.tensor(loss, dtype=torch.float64))
+    sums.counters.copy_(torch.tensor(counters, dtype=torch.int64))
+    sums.cat_sum.copy_(torch.tensor(cs, dtype=torch.float64).view(C, 3))
+    sums.cat_cnt.copy_(torch.tensor(cc, dtype=torch.int64))
+
+
+class CompletionMetric:
+    """The point-completion metrics of the reference's pre-task `validate` (tools/runner_pretask.py:314-426; utils/metrics.py:48-111),
+    accumulated batch by batch.
+
+    update(coarse (V B, nc, 3), dense (V B, nd, 3), gt (B, N, 3), category=None, n_valid=None): viewpoint-expanded batches, row v B + b
+    being cloud b seen from viewpoint v; clouds [0, n_valid) count.  For every (cloud, viewpoint) pair: the losses ChamferDistanceL1 /
+    L2 (ignore_zeros=False) of (coarse, gt) and (dense, gt), x 1000; with a category (B,) int also the detail metrics of (dense, gt)
+    under that category: F-Score@threshold, CDL1 and CDL2 (x 1000, ignore_zeros: every point whose f32 coordinate sum (x + y) + z is 0
+    is removed from both clouds first; a cloud left empty gives NaN).  category=None: losses only (the reference's in_detail=False).
+    HIP tensors run the metric kernels (upp_hip.ops.completion_update: no per-point value leaves the device); CPU tensors the same rules
+    in float64 torch.
+
+    compute(distributed=False) -> {'sparse_cd_l1', 'sparse_cd_l2', 'dense_cd_l1', 'dense_cd_l2' (means over the pairs; dense_cd_l2 is
+    the reference's CD_Metric), 'f_score', 'cd_l1', 'cd_l2' (the unweighted mean over the seen categories of their per-category means:
+    test_metrics.update(v.avg())), 'category_metrics': {name or id: {'f_score', 'cd_l1', 'cd_l2', 'count'}} of the seen categories}.
+    distributed: the sums and counts are all-reduced before any division.
+
+    Deliberate deviations from the reference:
+      * the sums are float64, added in the reference's order (batch by batch, cloud-major, then viewpoint); the reference sums f32 CDs
+        and Python floats (about 1e-7 relative apart);
+      * the F-Score distance: the reference's comes from open3d (a float64 KD-tree over the f32 coordinates).  Here a point's partner
+        is its Chamfer nearest neighbour as upp_chamfer_fwd picks it (the lowest index among equal f32 minima), the distance to it is
+        recomputed in float64 from the f32 coordinates, and the point counts when sqrt(d64) < threshold.  This differs from a float64
+        nearest-neighbour search only where two candidates tie within f32 rounding and lie on opposite sides of the threshold.  (The
+        CPU path searches in float64 directly.)"""
+
+    def __init__(self, num_categories=1, threshold=0.01, names=None):
+        self.num_categories, self.threshold = int(num_categories), float(threshold)
+        if self.num_categories < 1:
+            raise ValueError("num_categories must be positive")
+        if not (self.threshold > 0.0 and self.threshold != float('inf')):
+            raise ValueError("threshold must be positive and finite, got %r" % (threshold,))
+        self.names = None if names is None else list(names)
+        if self.names is not None and len(self.names) != self.num_categories:
+            raise ValueError("%d names for %d categories" % (len(self.names), self.num_categories))
+        self.sums = None
+
+    def _check(self, coarse, dense, gt, category, n_valid):
+        for name, t in (('coarse', coarse), ('dense', dense), ('gt', gt)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[2] != 3 or t.shape[1] < 1:
+                raise ValueError("%s must be a (rows, points, 3) tensor, got %s" % (name, getattr(t, 'shape', type(t))))
+        B, R = gt.shape[0], coarse.shape[0]
+        if B < 1 or R < B or R % B or dense.shape[0] != R:
+            raise ValueError("coarse %s and dense %s must hold V x %d clouds for gt %s" % (tuple(coarse.shape), tuple(dense.shape), B,
+                                                                                     tuple(gt.shape)))
+        if not (coarse.device == dense.device == gt.device):
+            raise ValueError("coarse, dense and gt must be on one device")
+        n_valid = B if n_valid is None else int(n_valid)
+        if not 0 <= n_valid <= B:
+            raise ValueError("n_valid %d outside [0, %d]" % (n_valid, B))
+        if category is not None:
+            category = torch.as_tensor(category).reshape(-1)
+            if category.shape[0] != B or category.dtype.is_floating_point or category.dtype == torch.bool:
+                raise ValueError("category must be (%d,) integers, got %s %s" % (B, category.dtype, tuple(category.shape)))
+            category = category.to(gt.device, torch.long).contiguous()
+        return category, n_valid
+
+    def device_sums(self, device):
+        """The upp_hip.ops.CompletionAccumulator the updates of a HIP device add into (made on first use)."""
+        from upp_hip import ops
+        if self.sums is None:
+            self.sums = ops.CompletionAccumulator(self.num_categories, device)
+        elif not isinstance(self.sums, ops.CompletionAccumulator) or self.sums.device != torch.device(device):
+            raise RuntimeError("CompletionMetric: all updates must come from one device")
+        return self.sums
+
+    def update(self, coarse, dense, gt, category=None, n_valid=None):
+        category, n_valid = self._check(coarse, dense, gt, category, n_valid)
+        coarse, dense, gt = (t.detach().contiguous() for t in (coarse, dense, gt))
+        if gt.is_cuda:
+            from upp_hip import ops
+            ops.completion_update(coarse, dense, gt, self.device_sums(gt.device), category, n_valid, self.threshold)
+            return self
+        if self.sums is None:
+            self.sums = _CompletionHostSums(self.num_categories)
+        elif not isinstance(self.sums, _CompletionHostSums):
+            raise RuntimeError("CompletionMetric: all updates must come from one device")
+        _completion_update_host(coarse.float(), dense.float(), gt.float(), self.sums, category, n_valid, self.threshold)
+        return self
+
+    def compute(self, distributed=False):
+        import numpy as np
+        s = self.sums if self.sums is not None else _CompletionHostSums(self.num_categories)
+        ints = torch.cat([s.counters, s.cat_cnt])
+        reals = torch.cat([s.loss_sum, s.cat_sum.reshape(-1)])
+        if distributed:
+            torch.distributed.all_reduce(ints)
+            torch.distributed.all_reduce(reals)
+        ints, reals = ints.cpu().numpy(), reals.cpu().numpy()
+        (pairs, invalid), cat_cnt = ints[:2], ints[2:]
+        loss_sum, cat_sum = reals[:4], reals[4:].reshape(-1, 3)
+        if invalid:
+            raise ValueError("%d (cloud, viewpoint) pair(s) have a category outside [0, %d)" % (invalid, self.num_categories))
+        seen = np.flatnonzero(cat_cnt)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            losses = loss_sum / np.float64(pairs)
+            means = cat_sum[seen] / cat_cnt[seen, None].astype(np.float64)
+        overall = means.sum(0) / np.float64(len(seen)) if len(seen) else np.full(3, np.nan)
+        out = {k: float(v) for k, v in zip(('sparse_cd_l1', 'sparse_cd_l2', 'dense_cd_l1', 'dense_cd_l2'), losses)}
+        out.update(f_score=float(overall[0]), cd_l1=float(overall[1]), cd_l2=float(overall[2]))
+        out['category_metrics'] = {(self.names[c] if self.names is not None else int(c)):
+                                   {'f_score': float(m[0]), 'cd_l1': float(m[1]), 'cd_l2': float(m[2]), 'count': int(cat_cnt[c])}
+                                   for c, m in zip(seen, means)}
+        return out
+
+
+def completion_outputs(model, gt, centers, num_crop, npoints=1024, max_clouds=None):
+    """The completion of every (cloud, viewpoint) pair of one batch as ONE viewpoint-major V B batch (row v B + b): gt (B, N, 3),
+    centers (V, 3) -> (coarse (V B, 128 + n_pred, 3), dense (V B, npoints + n_rebuild, 3)).  The reference's steps 1-5 per pair
+    (tools/runner_pretask.py:366-373): crop num_crop points nearest the viewpoint and FPS the kept part to npoints, FPS it again
+    (npoints of npoints: a re-ordering from index 0 that the model's grouping sees), FPS 128 centres, the eval forward, the two
+    concatenations.  The forwards take at most max_clouds clouds each (whole viewpoints, infer.plan_chunks)."""
+    from upp_hip.infer import plan_chunks
+    B, N = gt.shape[0], gt.shape[1]
+    V = centers.shape[0]
+    rep = gt if V == 1 else gt.repeat(V, 1, 1)
+    ctr = centers.view(V, 1, 1, 3).expand(V, B, 1, 3).reshape(V * B, 1, 3)
+    partial, _ = misc.seprate_point_cloud(rep, N, num_crop, sample_points=npoints, centers=ctr, keep_crop=False)
+    partial = misc.fps(partial, npoints)[0]
+    partial_center = misc.fps(partial, CENTERS)[0]
+    preds, rebuilds = [], []
+    for v0, v1 in plan_chunks(V, B, max_clouds):
+        pred_center, rebuild = model(partial[v0 * B:v1 * B], train_with_gaussian=False, predict_center_num=16)
+        preds.append(pred_center)
+        rebuilds.append(rebuild)
+    pred_center = preds[0] if len(preds) == 1 else torch.cat(preds)
+    rebuild = rebuilds[0] if len(rebuilds) == 1 else torch.cat(rebuilds)
+    return torch.cat([partial_center, pred_center], dim=1), torch.cat([partial, rebuild], dim=1)
+
+
+def _completion_args(gt, mode, npoints):
+    N = gt.shape[1]
+    num_crop = crop_count(N, mode)
+    if N - num_crop < npoints:
+        raise ValueError("%s mode keeps %d of %d points, fewer than the %d the model takes" % (mode, N - num_crop, N, npoints))
+    return num_crop
+
+
+@torch.no_grad()
+def validate_completion(model, batches, mode='easy', in_detail=False, npoints=1024, distributed=False, threshold=0.01, num_categories=None,
+                        names=None, max_clouds=None):
+    """batches: iterable of (gt (B, N, 3), category (B,) int).  The reference's pre-task `validate` (tools/runner_pretask.py:314-426)
+    with every viewpoint of a batch cropped and completed as one viewpoint-major batch (completion_outputs) and the metrics on the device
+    (CompletionMetric; in_detail adds the per-category F-Score / CDL1 / CDL2 over the eight viewpoints).  num_categories: default the
+    largest category seen + 1 -- which needs the categories on the host -- or len(names).  The model's training flag is restored.
+    -> CompletionMetric.compute(distributed)."""
+    batches = list(batches)
+    metric = CompletionMetric(_num_categories(batches, num_categories, names, in_detail), threshold, names)
+    was = model.training
+    model.eval()
+    try:
+        for gt, category in batches:
+            gt = gt.contiguous()
+            centers = torch.tensor(viewpoints(in_detail), dtype=torch.float32, device=gt.device)
+            coarse, dense = completion_outputs(model, gt, centers, _completion_args(gt, mode, npoints), npoints, max_clouds)
+            metric.update(coarse, dense, gt, category if in_detail else None)
+    finally:
+        model.train(was)
+    return metric.compute(distributed)
+
+
+def _num_categories(batches, num_categories, names, in_detail):
+    if num_categories is not None:
+        return int(num_categories)
+    if names is not None:
+        return len(names)
+    if not in_detail or not batches:
+        return 1
+    return max(int(torch.as_tensor(c).max()) for _, c in batches) + 1
+
+
+@torch.no_grad()
+def validate_completion_captured(model, batches, mode='easy', in_detail=False, npoints=1024, distributed=False, threshold=0.01,
+                                 num_categories=None, names=None, max_clouds=None):
+    """`validate_completion` with each batch one HIP-graph replay (upp_hip.infer.CompletionEvalStep, one per (B, N, V)) and the
+    accumulation launch after it.  Same arguments and results, bit for bit: a ragged last batch runs a graph of its own size rather than
+    a padded one, because the forward's GEMM tiling follows the row count (a padded forward equals it only to f32 rounding)."""
+    from upp_hip.infer import CompletionEvalStep
+    batches = list(batches)
+    metric = CompletionMetric(_num_categories(batches, num_categories, names, in_detail), threshold, names)
+    was = model.training
+    model.eval()
+    steps, step = [], None
+    try:
+        for gt, category in batches:
+            n, N = gt.shape[0], gt.shape[1]
+            _completion_args(gt, mode, npoints)
+            if step is None or step.B != n or step.N != N:
+                step = CompletionEvalStep.cached(model, (n, N, 3), mode=mode, in_detail=bool(in_detail), npoints=int(npoints),
+                                                 threshold=float(threshold), max_clouds=max_clouds)
+                if step not in steps:
+                    step.prepare()
+                    steps.append(step)
+            step.run(gt.contiguous(), category if in_detail else None, metric)
+    finally:
+        model.train(was)
+    return metric.compute(distributed)

@@ -39,14 +39,15 @@ def gaussian_noise(shape, loc=0., scale=0.2, shell_radius=0.9, device=None, gene
 
 
 def seprate_point_cloud(xyz, num_points, crop, fixed_points=None, padding_zeros=False, sample_points=1024,
-                        incomplete_shape=True, centers=None, generator=None):
+                        incomplete_shape=True, centers=None, generator=None, keep_crop=True):
     """Online cropping of reference utils/misc.py:205-256, batched on the device.
 
     The reference loops over the batch in Python (randn centre -> distance argsort -> slice -> one single-cloud FPS
     launch for the kept part and one for the cropped part, 2*B launches of up to 1023 rounds each).  All samples have
     the same sizes, so here the whole batch is ONE argsort, two gathers and two batched FPS launches.
     Returns (input_data (B, min(n-crop, sample_points), 3), crop_data (B, min(crop, sample_points), 3)).
-    `centers` (B,1,3) overrides the random viewpoints (the reference's `fixed_points`, one per sample)."""
+    `centers` (B,1,3) overrides the random viewpoints (the reference's `fixed_points`, one per sample).  keep_crop=False: crop_data is
+    None and neither its gather nor its FPS is launched (a caller that only uses the kept part)."""
     B, n, c = xyz.shape
     assert n == num_points and c == 3
     if crop == num_points:
@@ -64,7 +65,7 @@ def seprate_point_cloud(xyz, num_points, crop, fixed_points=None, padding_zeros=
     dist = torch.norm(centers - xyz, p=2, dim=-1)                                   # (B, n)
     order = _F.argsort_rows(dist)                     # (rank-counting kernel on the device, torch.argsort on the host)
     take = lambda idx: torch.gather(xyz, 1, idx.unsqueeze(-1).expand(-1, -1, 3)).contiguous()
-    crop_data = take(order[:, :num_crop])
+    crop_data = take(order[:, :num_crop]) if keep_crop else None
     if padding_zeros:
         input_data = xyz.clone()
         input_data.scatter_(1, order[:, :num_crop].unsqueeze(-1).expand(-1, -1, 3), 0.0)
@@ -73,6 +74,8 @@ def seprate_point_cloud(xyz, num_points, crop, fixed_points=None, padding_zeros=
     force = isinstance(crop, (list, tuple))
     if (incomplete_shape or force) and input_data.shape[1] > sample_points:
         input_data = fps(input_data, sample_points)[0]
+    if not keep_crop:
+        return input_data.contiguous(), None
     if (incomplete_shape or force) and crop_data.shape[1] > sample_points:
         crop_data = fps(crop_data, sample_points)[0]
     return input_data.contiguous(), crop_data.contiguous()

@@ -616,6 +616,34 @@ int upp_seg_iou_accumulate(int32_t *scratch, const int64_t *target, const int32_
                            int P, int C, int n_valid, double *shape_iou, int32_t *shape_cat, double *cat_sum, int64_t *cat_cnt,
                            int64_t *part_seen, int64_t *part_correct, int64_t *counters, void *stream);
 
+/* ---- point-completion metrics (utils/evaluate.py CompletionMetric; reference tools/runner_pretask.py:314-426 `validate`,
+ * utils/metrics.py:48-111 `Metrics.get`) ----
+ * upp_completion_cloud_metrics: one workgroup per cloud pair b < B of xyz1 (B, n, 3) / xyz2 (B, m, 3) f32, with dist1 / idx1 (B, n) and
+ *   dist2 / idx2 (B, m) of upp_chamfer_fwd on the same pair.  stats (B, 8) f64 = (mean d1, mean d2, mean sqrt d1, mean sqrt d2, F,
+ *   CDL1, CDL2, 0): float64 sums in a fixed tree (bit-identical from run to run), one division each; CDL1 = (mean sqrt d1 + mean sqrt
+ *   d2) / 2 and CDL2 = mean d1 + mean d2 (upp_completion_masked_cd replaces them for a flagged pair).  counts (B, 4) int32 =
+ *   (precision count, recall count, has a zero-sum point, 0).  detail = 1: a point of xyz1 counts for the precision when the float64
+ *   Euclidean distance to its Chamfer partner idx1 (recomputed from the f32 coordinates) is < th, a point of xyz2 likewise for the
+ *   recall; F = 2 r p / (r + p) with p = count / n, r = count / m (0 when r + p = 0); the flag is set when a point of either cloud has
+ *   the f32 sum (x + y) + z == 0.  detail = 0: F, the counts and the flag are 0.  th > 0 and finite.
+ * upp_completion_masked_cd: after upp_completion_cloud_metrics with the same (xyz1, xyz2, B, n, m, counts, stats).  For every pair whose
+ *   flag is set, CDL1 / CDL2 of stats are recomputed with every zero-sum point removed from both clouds first (a nearest-neighbour
+ *   search on upp_chamfer_fwd's f32 arithmetic; the ignore_zeros rule of the reference's Chamfer modules at batch size 1); NaN when
+ *   either cloud is left without points.  A workgroup whose flag is 0 reads it on the device and returns.
+ * upp_completion_accumulate: one workgroup.  sparse / dense (V B, 8) f64 are stats rows, viewpoint-major (row v B + b).  For b <
+ *   n_valid, then v < V, sequentially in float64: loss_sum (4) += 1000 x (sparse CDL1-form, sparse CDL2-form, dense CDL1-form, dense
+ *   CDL2-form) of the unmasked means; counters (2) int64 += (n_valid V, V x the clouds whose category is outside [0, C)).  category (B)
+ *   int64 may be NULL (no detail metrics); otherwise cat_sum (C, 3) f64 += (F, 1000 CDL1, 1000 CDL2) of the dense rows of category c
+ *   and cat_cnt (C) int64 += their count.  The stats rows are written whole by every cloud-metrics launch: no scratch, no memset.
+ * Limits: B (V B for accumulate) <= 2^20 rows, n, m <= 2^22, V <= 64, C <= 4096; UPP_E_RANGE for n_valid outside [0, B]. */
+int upp_completion_cloud_metrics(const float *xyz1, const float *xyz2, const float *dist1, const int32_t *idx1, const float *dist2,
+                                 const int32_t *idx2, int B, int n, int m, double th, int detail, double *stats, int32_t *counts,
+                                 void *stream);
+int upp_completion_masked_cd(const float *xyz1, const float *xyz2, int B, int n, int m, const int32_t *counts, double *stats,
+                             void *stream);
+int upp_completion_accumulate(const double *sparse, const double *dense, const int64_t *category, int V, int B, int C, int n_valid,
+                              double *loss_sum, int64_t *counters, double *cat_sum, int64_t *cat_cnt, void *stream);
+
 /* ---- token-matrix Linear (exact f32 on the matrix cores) -------------------------------------
  * Replaces the nn.Linear layers of the Transformer blocks and their data gradients: Attention.qkv / .proj
  * (reference models/Point_MAE_pretask_dev.py:178,181 called :186,:194) and Mlp.fc1 / .fc2 (:158,:160 called
