@@ -1,10 +1,12 @@
 """Evaluation loops of the reference classification runner (tools/runner_module.py:370-490), on device:
 `validate` = one pass, arg-max accuracy; `test_vote` = the 10x voting protocol (FPS to a 1200-point superset once,
 then `times` random 1024-subsets, each scale/translate-augmented; logits averaged before the arg-max)."""
+import contextlib
+
 import torch
 
 from utils import dist_utils, misc
-from upp_hip import functional as HF
+from upp_hip import functional as HF, infer
 
 
 def _accuracy(pred, label, distributed):
@@ -31,13 +33,12 @@ def validate(model, batches, npoints, noisy=False, distributed=False):
 def test_vote(model, batches, npoints, times=10, transform=misc.scale_translate, distributed=False, generator=None):
     """runner_module.py:427-490.  The random subsets are drawn on the device (torch.randperm) instead of
     np.random.choice on the host: same distribution, no host round trip per vote."""
-    superset = {1024: 1200, 4096: 4800, 8192: 8192}
-    if npoints not in superset:
+    if npoints not in infer.SUPERSET:
         raise NotImplementedError()
     model.eval()
     preds, labels = [], []
     for points_raw, label in batches:
-        point_all = min(superset[npoints], points_raw.size(1))
+        point_all = min(infer.SUPERSET[npoints], points_raw.size(1))
         raw, _ = HF.fps_gather(points_raw.contiguous(), point_all)                # (B, point_all, 3) FPS-ordered superset
         votes = []
         for _ in range(times):
@@ -51,28 +52,49 @@ def test_vote(model, batches, npoints, times=10, transform=misc.scale_translate,
     return _accuracy(preds, labels, distributed)
 
 
-# ------------------------------------------------------------------ the same protocols, captured (upp_hip.infer.EvalStep)
+# ------------------------------------------------------------------ the same protocols, captured (upp_hip.infer)
+@contextlib.contextmanager
+def _evaluating(model):
+    """model.eval() inside (every sub-module, whatever the top-level flag was), the model's training flag again after."""
+    was = model.training
+    model.eval()
+    try:
+        yield
+    finally:
+        model.train(was)
+
+
+def _run_steps(model, batches, make, fits, run, first=None):
+    """The loop of the captured protocols, the model in eval mode meanwhile.  Per batch, whose first member holds n clouds of N points:
+    the step in use while fits(step, n, N), else make(n, N) (the cached step of that shape); a step met for the first time in this call
+    is brought up to date with the model's weights (prepare()) and passed to `first`; then run(step, batch).  -> the steps used, in
+    the order they were first met."""
+    steps, step = [], None
+    with _evaluating(model):
+        for batch in batches:
+            n, N = batch[0].shape[0], batch[0].shape[1]
+            if step is None or not fits(step, n, N):
+                step = make(n, N)
+                if step not in steps:
+                    step.prepare()
+                    if first is not None:
+                        first(step)
+                    steps.append(step)
+            run(step, batch)
+    return steps
+
+
 def _run_captured(model, batches, npoints, kw, generator, distributed, return_predictions):
     """One EvalStep per (B, N_raw) of the batches (a batch smaller than the step in use is padded into it); the accuracy is
     `_accuracy`'s expression over the device counters (correct, total), all-reduced outside the graph when distributed."""
-    from upp_hip.infer import EvalStep
-    was = model.training
-    model.eval()
-    steps, step, preds = [], None, []
-    try:
-        for points, label in batches:
-            n, n_raw = points.shape[0], points.shape[1]
-            if step is None or step.B < n or step.n_raw != n_raw:
-                step = EvalStep.cached(model, (n, n_raw, 3), npoints, **kw)
-                if step not in steps:
-                    step.prepare()
-                    step.counters.zero_()
-                    steps.append(step)
-            pred = step.run(points.contiguous(), label.view(-1), generator=generator)
-            if return_predictions:
-                preds.append(pred.clone())
-    finally:
-        model.train(was)
+    preds = []
+
+    def run(step, batch):
+        pred = step.run(batch[0].contiguous(), batch[1].view(-1), generator=generator)
+        if return_predictions:
+            preds.append(pred.clone())
+    steps = _run_steps(model, batches, lambda n, N: infer.EvalStep.cached(model, (n, N, 3), npoints, **kw),
+                       lambda s, n, N: s.B >= n and s.n_raw == N, run, first=lambda s: s.counters.zero_())
     if not steps:
         return _accuracy([], [], distributed)
     counters = steps[0].counters.clone()
@@ -102,12 +124,11 @@ def test_vote_captured(model, batches, npoints, times=10, transform=misc.scale_t
     (upp_hip.infer.mixes_samples: the reference's propagation indexing with gather_idx = false), one vote per forward, which is what
     keeps the logits those of test_vote; a larger max_clouds then batches votes at the price of that equality.
     `transform`: misc.scale_translate (with its default ranges) or None; another callable cannot run inside the kernel."""
-    superset = {1024: 1200, 4096: 4800, 8192: 8192}
-    if npoints not in superset:
+    if npoints not in infer.SUPERSET:
         raise NotImplementedError()
     if transform is not None and transform is not misc.scale_translate:
         raise NotImplementedError("test_vote_captured applies misc.scale_translate (or no transform) on the device")
-    kw = dict(votes=int(times), transform=transform is not None, superset=superset[npoints], max_clouds=max_clouds)
+    kw = dict(votes=int(times), transform=transform is not None, superset=infer.SUPERSET[npoints], max_clouds=max_clouds)
     return _run_captured(model, batches, npoints, kw, generator, distributed, return_predictions)
 
 
@@ -289,10 +310,8 @@ def validate_seg(model, batches, num_part=50, num_classes=16, distributed=False,
     completion_prompt=False, denoise=False, point_num=N) into a SegMetric -> its compute(distributed) dict; with return_predictions also
     this rank's predictions (n, N) int64, in batch order.  The model's training flag is restored afterwards."""
     metric = SegMetric(num_part, num_classes, classes)
-    was = model.training
-    model.eval()
     preds = []
-    try:
+    with _evaluating(model):
         for points, label, target in batches:
             points, label, target = _seg_batch(points, label, target)
             logp = model(points, one_hot(label.to(points.device), num_classes), completion_prompt=False, denoise=False,
@@ -301,8 +320,6 @@ def validate_seg(model, batches, num_part=50, num_classes=16, distributed=False,
             metric.update(logp, target, pred=pred)
             if return_predictions:
                 preds.append(pred)
-    finally:
-        model.train(was)
     out = metric.compute(distributed)
     return (out, torch.cat(preds) if preds else torch.empty((0, 0), dtype=torch.long)) if return_predictions else out
 
@@ -312,25 +329,16 @@ def validate_seg_captured(model, batches, num_part=50, num_classes=16, distribut
                           classes=SHAPENET_PART):
     """`validate_seg` with each batch's forward one HIP-graph replay (upp_hip.infer.SegEvalStep, one per (B, N); a smaller batch is
     padded into the step in use) and the metric on the device.  Same arguments and results."""
-    from upp_hip.infer import SegEvalStep
     metric = SegMetric(num_part, num_classes, classes)
-    was = model.training
-    model.eval()
-    steps, step, preds = [], None, []
-    try:
-        for points, label, target in batches:
-            points, label, target = _seg_batch(points, label, target)
-            n, N = points.shape[0], points.shape[1]
-            if step is None or step.B < n or step.N != N:
-                step = SegEvalStep.cached(model, (n, N, 3), num_classes)
-                if step not in steps:
-                    step.prepare()
-                    steps.append(step)
-            pred = step.run(points, label.to(step.device), target.to(step.device), metric)
-            if return_predictions:
-                preds.append(pred.clone())
-    finally:
-        model.train(was)
+    preds = []
+
+    def run(step, batch):
+        points, label, target = _seg_batch(*batch)
+        pred = step.run(points, label.to(step.device), target.to(step.device), metric)
+        if return_predictions:
+            preds.append(pred.clone())
+    _run_steps(model, batches, lambda n, N: infer.SegEvalStep.cached(model, (n, N, 3), num_classes),
+               lambda s, n, N: s.B >= n and s.N == N, run)
     out = metric.compute(distributed)
     return (out, torch.cat(preds) if preds else torch.empty((0, 0), dtype=torch.long)) if return_predictions else out
 
@@ -549,7 +557,6 @@ def completion_outputs(model, gt, centers, num_crop, npoints=1024, max_clouds=No
     (tools/runner_pretask.py:366-373): crop num_crop points nearest the viewpoint and FPS the kept part to npoints, FPS it again
     (npoints of npoints: a re-ordering from index 0 that the model's grouping sees), FPS 128 centres, the eval forward, the two
     concatenations.  The forwards take at most max_clouds clouds each (whole viewpoints, infer.plan_chunks)."""
-    from upp_hip.infer import plan_chunks
     B, N = gt.shape[0], gt.shape[1]
     V = centers.shape[0]
     rep = gt if V == 1 else gt.repeat(V, 1, 1)
@@ -558,7 +565,7 @@ def completion_outputs(model, gt, centers, num_crop, npoints=1024, max_clouds=No
     partial = misc.fps(partial, npoints)[0]
     partial_center = misc.fps(partial, CENTERS)[0]
     preds, rebuilds = [], []
-    for v0, v1 in plan_chunks(V, B, max_clouds):
+    for v0, v1 in infer.plan_chunks(V, B, max_clouds):
         pred_center, rebuild = model(partial[v0 * B:v1 * B], train_with_gaussian=False, predict_center_num=16)
         preds.append(pred_center)
         rebuilds.append(rebuild)
@@ -567,8 +574,8 @@ def completion_outputs(model, gt, centers, num_crop, npoints=1024, max_clouds=No
     return torch.cat([partial_center, pred_center], dim=1), torch.cat([partial, rebuild], dim=1)
 
 
-def _completion_args(gt, mode, npoints):
-    N = gt.shape[1]
+def _num_crop(N, mode, npoints):
+    """crop_count(N, mode), refusing a mode that leaves fewer points than the model takes."""
     num_crop = crop_count(N, mode)
     if N - num_crop < npoints:
         raise ValueError("%s mode keeps %d of %d points, fewer than the %d the model takes" % (mode, N - num_crop, N, npoints))
@@ -585,16 +592,12 @@ def validate_completion(model, batches, mode='easy', in_detail=False, npoints=10
     -> CompletionMetric.compute(distributed)."""
     batches = list(batches)
     metric = CompletionMetric(_num_categories(batches, num_categories, names, in_detail), threshold, names)
-    was = model.training
-    model.eval()
-    try:
+    with _evaluating(model):
         for gt, category in batches:
             gt = gt.contiguous()
             centers = torch.tensor(viewpoints(in_detail), dtype=torch.float32, device=gt.device)
-            coarse, dense = completion_outputs(model, gt, centers, _completion_args(gt, mode, npoints), npoints, max_clouds)
+            coarse, dense = completion_outputs(model, gt, centers, _num_crop(gt.shape[1], mode, npoints), npoints, max_clouds)
             metric.update(coarse, dense, gt, category if in_detail else None)
-    finally:
-        model.train(was)
     return metric.compute(distributed)
 
 
@@ -614,23 +617,10 @@ def validate_completion_captured(model, batches, mode='easy', in_detail=False, n
     """`validate_completion` with each batch one HIP-graph replay (upp_hip.infer.CompletionEvalStep, one per (B, N, V)) and the
     accumulation launch after it.  Same arguments and results, bit for bit: a ragged last batch runs a graph of its own size rather than
     a padded one, because the forward's GEMM tiling follows the row count (a padded forward equals it only to f32 rounding)."""
-    from upp_hip.infer import CompletionEvalStep
     batches = list(batches)
     metric = CompletionMetric(_num_categories(batches, num_categories, names, in_detail), threshold, names)
-    was = model.training
-    model.eval()
-    steps, step = [], None
-    try:
-        for gt, category in batches:
-            n, N = gt.shape[0], gt.shape[1]
-            _completion_args(gt, mode, npoints)
-            if step is None or step.B != n or step.N != N:
-                step = CompletionEvalStep.cached(model, (n, N, 3), mode=mode, in_detail=bool(in_detail), npoints=int(npoints),
-                                                 threshold=float(threshold), max_clouds=max_clouds)
-                if step not in steps:
-                    step.prepare()
-                    steps.append(step)
-            step.run(gt.contiguous(), category if in_detail else None, metric)
-    finally:
-        model.train(was)
+    kw = dict(mode=mode, in_detail=bool(in_detail), npoints=int(npoints), threshold=float(threshold), max_clouds=max_clouds)
+    _run_steps(model, batches, lambda n, N: infer.CompletionEvalStep.cached(model, (n, N, 3), **kw),
+               lambda s, n, N: s.B == n and s.N == N,            # (never padded: see above)
+               lambda s, b: s.run(b[0].contiguous(), b[1] if in_detail else None, metric))
     return metric.compute(distributed)
