@@ -22,6 +22,10 @@ SIGNATURES = {
     "upp_get_option": (_c_i, [_c_i]),
     "upp_fps": (_c_i, [_c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_f]),
     "upp_fps_ex": (_c_i, [_c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_f]),
+    "upp_fps_ragged": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_f]),
+    "upp_fps_ragged_slots": (_c_i, [_c_i, _c_i]),
+    "upp_cloud_norm_ragged": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_f]),
+    "upp_cloud_norm_ragged_f32": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_f]),
     "upp_gather_fwd": (_c_i, [_c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_f]),
     "upp_gather_bwd": (_c_i, [_c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_f]),
     "upp_knn": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_f]),

@@ -34,6 +34,7 @@
 // threads" whose bit-reversed ids are v = g*U .. g*U + U-1, slot s = u*Q + q
 // holding point k = bitrev(v) + T*q:  rank(k) = v*Q + q = g*(U*Q) + s.
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
@@ -68,24 +69,64 @@ struct FpsGeom {
     int U;         // virtual threads per lane = max(1, T / L)
 };
 
+// The ragged form (upp_fps_ragged): the clouds of a batch lie back to back in one (T, 3) array, cloud b is rows offsets[b] ... offsets[b+1]-1.
+// The tie order depends on the cloud's OWN length through T, Q and U (rank = g U Q + s, above), so a workgroup derives them from n_b; W and
+// S are the launch's (chosen for max_len, see fps_ragged_slots): a cloud with fewer than 64 W virtual threads leaves the surplus lanes -- whole
+// waves, too -- without a valid slot (tmp = -1: never a candidate), and the lanes that do hold points keep rank order.
+struct FpsRagged {
+    const int64_t *offsets;
+    int max_len, M;
+};
+
+// The reference's block size for an n-point cloud, n <= 32768: min(512, 2^floor(log2 n)) -- the integer form of fps_block_size() below
+// (equal for every n of the range: tests/test_ragged_host.py).
+__host__ __device__ __forceinline__ int fps_block_size_int(int n) {
+    const int l = 31 - __builtin_clz((unsigned)n);
+    return l >= 9 ? 512 : 1 << l;
+}
+
 // CPW clouds per workgroup (round 5): the W waves of cloud blockIdx.x * CPW + c are waves c W ... c W + W - 1, with their own LDS region;
 // the per-round barrier spans the workgroup (every cloud runs the same M - 1 rounds).  Nothing else changes -- a cloud's waves never
 // look at another cloud's records -- so the indices are those of CPW = 1.  Why: 32 clouds on 32 CUs keep a one-round GEMM of the other
 // stream (228 workgroups on 256 CUs) from fitting, and every such GEMM then runs two rounds for as long as FPS is resident (back-end
 // chain 3.26 -> 3.61 ms beside 0.8 ms of FPS: tools/micro/fps_beside_backend.py); 8 CUs leave room.
-template <int S, int W, bool USE_LDS, int CPW = 1>
+template <int S, int W, bool USE_LDS, int CPW = 1, class G = FpsGeom>
 __global__ __launch_bounds__(64 * W * CPW) void fps_kernel(const float *__restrict__ xyz, int32_t *__restrict__ idx,
-                                                           float *__restrict__ centers, FpsGeom g) {
+                                                           float *__restrict__ centers, G ga) {
     static_assert(S % 2 == 0, "slots are processed in packed pairs");
     static_assert(CPW == 1 || USE_LDS, "several clouds per workgroup: the LDS form only");
+    constexpr bool RAGGED = std::is_same<G, FpsRagged>::value;
+    static_assert(CPW == 1 || !RAGGED, "the ragged form: one cloud per workgroup (a workgroup may leave early)");
     constexpr int L = 64 * W;
     extern __shared__ float lds_all[];  // per cloud: 2*W*2 words of wave records, a [3*N] copy of the cloud, then the M winners
-    const int N = g.N, M = g.M;
     const int cslot = CPW > 1 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x / L) : 0;
     const int tid = (int)threadIdx.x - cslot * L;
     const int b = blockIdx.x * CPW + cslot;
+    FpsGeom g;
+    const float *p;
+    if constexpr (RAGGED) {
+        const long long first = ga.offsets[b];
+        long long n = ga.offsets[b + 1] - first;
+        n = n > ga.max_len ? ga.max_len : n;              // a wrong promise of the caller: never past the slots and the LDS of this launch
+        g.M = ga.M;
+        if (n < 1) {                                      // (the Python layer refuses an empty cloud; here it only must not read: all zeros)
+            for (int j = tid; j < g.M; j += L) idx[(size_t)b * g.M + j] = 0;
+            if (centers)
+                for (int e = tid; e < 3 * g.M; e += L) centers[(size_t)b * g.M * 3 + e] = 0.0f;
+            return;
+        }
+        g.N = (int)n;
+        g.T = fps_block_size_int(g.N);
+        g.log2T = 31 - __builtin_clz((unsigned)g.T);
+        g.Q = (g.N + g.T - 1) >> g.log2T;
+        g.U = g.T / L > 0 ? g.T / L : 1;
+        p = xyz + first * 3;
+    } else {
+        g = ga;
+        p = xyz + (size_t)b * g.N * 3;
+    }
+    const int N = g.N, M = g.M;
     float *lds = lds_all + (size_t)cslot * (size_t)((4 * W + 3 * N + M + 3) / 4 * 4);
-    const float *p = xyz + (size_t)b * N * 3;
     uint32_t *rec = reinterpret_cast<uint32_t *>(lds);
     float *cloud = lds + 4 * W;
     int *won = reinterpret_cast<int *>(cloud + 3 * N);
@@ -299,9 +340,14 @@ int fps_block_size(int n) {
 
 constexpr int kFpsLdsBytes = 160 * 1024 - 256;  // cloud copy + winner list + wave records must fit the CU's LDS
 
-template <int S, int W>
-int launch(const float *xyz, int32_t *idx, float *centers, int B, const FpsGeom &g, int form, hipStream_t st) {
-    const size_t lds_bytes = (size_t)(4 * W + 3 * g.N + g.M) * 4;
+inline int fps_points_host(const FpsGeom &g) { return g.N; }
+inline int fps_points_host(const FpsRagged &g) { return g.max_len; }
+
+template <int S, int W, class G>
+int launch(const float *xyz, int32_t *idx, float *centers, int B, const G &g, int form, hipStream_t st) {
+    constexpr bool RAGGED = std::is_same<G, FpsRagged>::value;
+    const int NP = fps_points_host(g);                   // the longest cloud of the launch: sizes the LDS copy
+    const size_t lds_bytes = (size_t)(4 * W + 3 * NP + g.M) * 4;
 #ifdef UPP_FPS_DIAG_NOLDS
     if (false) {
 #else
@@ -310,14 +356,14 @@ int launch(const float *xyz, int32_t *idx, float *centers, int B, const FpsGeom 
         if (lds_bytes > 64 * 1024) {
             static std::atomic<bool> raised{false};  // one attribute call per instantiation
             if (!raised) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fps_kernel<S, W, true>),
+                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fps_kernel<S, W, true, 1, G>),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, kFpsLdsBytes);
                 if (e != hipSuccess) return (int)e;
                 raised = true;
             }
         }
         // clouds per workgroup: as many of {4, 2} as divide B and fit 1,024 threads and the LDS (W = 4, the shapes of the recipes: S <= 8)
-        if constexpr (W == 4 && S <= 8) {
+        if constexpr (W == 4 && S <= 8 && !RAGGED) {
             const size_t stride = (size_t)((4 * W + 3 * g.N + g.M + 3) / 4 * 4) * 4;
             const int want = (form & 0xF) ? (form & 0xF) : 1;                          // (the caller's form: upp_fps_ex `waves` bits 8-12; default one cloud per workgroup)
             const bool excl = (form & 0xF) && (form & 0x10) != 0;
@@ -342,15 +388,15 @@ int launch(const float *xyz, int32_t *idx, float *centers, int B, const FpsGeom 
                 return upp_launch_status();
             }
         }
-        hipLaunchKernelGGL((fps_kernel<S, W, true>), dim3(B), dim3(64 * W), lds_bytes, st, xyz, idx, centers, g);
+        hipLaunchKernelGGL((fps_kernel<S, W, true, 1, G>), dim3(B), dim3(64 * W), lds_bytes, st, xyz, idx, centers, g);
     } else {
-        hipLaunchKernelGGL((fps_kernel<S, W, false>), dim3(B), dim3(64 * W), (size_t)(4 * W) * 4, st, xyz, idx, centers, g);
+        hipLaunchKernelGGL((fps_kernel<S, W, false, 1, G>), dim3(B), dim3(64 * W), (size_t)(4 * W) * 4, st, xyz, idx, centers, g);
     }
     return upp_launch_status();
 }
 
-template <int W>
-int dispatch_s(int slots, const float *xyz, int32_t *idx, float *centers, int B, const FpsGeom &g, int form, hipStream_t st) {
+template <int W, class G>
+int dispatch_s(int slots, const float *xyz, int32_t *idx, float *centers, int B, const G &g, int form, hipStream_t st) {
     if (slots <= 2) return launch<2, W>(xyz, idx, centers, B, g, form, st);
     if (slots <= 4) return launch<4, W>(xyz, idx, centers, B, g, form, st);
     if (slots <= 6) return launch<6, W>(xyz, idx, centers, B, g, form, st);
@@ -365,7 +411,52 @@ int dispatch_s(int slots, const float *xyz, int32_t *idx, float *centers, int B,
     return UPP_E_RANGE;
 }
 
+// Slots per lane that a ragged launch of W waves per cloud needs: the maximum of U(n) Q(n) over EVERY length 1 <= n <= max_len, not the value
+// at max_len -- U Q is not monotone in n (n = 511: T = 256, Q = 2; n = 512: T = 512, Q = 1).  Inside one block size T = 2^k it does not
+// decrease with n, so the candidates are the last length of every block size that max_len reaches.
+int fps_ragged_slots(int max_len, int W) {
+    const int L = 64 * W;
+    int best = 0;
+    for (int k = 0; k <= 9 && (1 << k) <= max_len; ++k) {
+        const int T = 1 << k;
+        const int last = (k == 9 || 2 * T - 1 > max_len) ? max_len : 2 * T - 1;
+        const int U = T / L > 0 ? T / L : 1, Q = (last + T - 1) / T;
+        if (U * Q > best) best = U * Q;
+    }
+    return best;
+}
+
+// waves per cloud of a ragged launch: the dense default for max_len, widened until 64 slots per lane hold every length
+int fps_ragged_waves(int max_len) {
+    int W = max_len <= 128 ? 1 : (max_len <= 512 ? 2 : 4);
+    while (W < 8 && fps_ragged_slots(max_len, W) > 64) W <<= 1;
+    return W;
+}
+
 }  // namespace
+
+extern "C" int upp_fps_ragged_slots(int max_len, int waves) {
+    if (max_len < 1 || (waves != 0 && waves != 1 && waves != 2 && waves != 4 && waves != 8)) return UPP_E_BADARG;
+    if (max_len > 32768) return UPP_E_RANGE;
+    return fps_ragged_slots(max_len, waves ? waves : fps_ragged_waves(max_len));
+}
+
+extern "C" int upp_fps_ragged(const float *xyz, const int64_t *offsets, int32_t *idx, float *centers, int B, int max_len, int M, void *stream) {
+    if (!xyz || !offsets || !idx || B < 0 || max_len < 1 || M < 1) return UPP_E_BADARG;
+    if (max_len > 32768) return UPP_E_RANGE;
+    if (B == 0) return 0;
+    FpsRagged g;
+    g.offsets = offsets; g.max_len = max_len; g.M = M;
+    const int W = fps_ragged_waves(max_len);
+    const int slots = fps_ragged_slots(max_len, W);
+    hipStream_t st = (hipStream_t)stream;
+    switch (W) {
+        case 1: return dispatch_s<1>(slots, xyz, idx, centers, B, g, 0, st);
+        case 2: return dispatch_s<2>(slots, xyz, idx, centers, B, g, 0, st);
+        case 4: return dispatch_s<4>(slots, xyz, idx, centers, B, g, 0, st);
+        default: return dispatch_s<8>(slots, xyz, idx, centers, B, g, 0, st);
+    }
+}
 
 extern "C" int upp_fps_ex(const float *xyz, int32_t *idx, float *centers, int B, int N, int M, int waves, void *stream) {
     if (!xyz || !idx || B < 0 || N < 1 || M < 1) return UPP_E_BADARG;

@@ -176,6 +176,29 @@ def fps_gather(xyz, npoint):
     return _FpsGather.apply(xyz, int(npoint))
 
 
+def fps_gather_ragged(xyz, offsets, max_len, npoint, lengths=None):
+    """FPS of every cloud of a packed batch (xyz (T,3) f32, offsets (B+1,) int64) -> (centers (B,npoint,3), idx (B,npoint) int32, local to
+    each cloud): one launch, the result of fps_gather(cloud[None], npoint) per cloud.  No gradient (an input path)."""
+    if _torch_cpu(xyz, offsets):
+        from . import torch_cpu
+        ops.ragged_layout((offsets[1:] - offsets[:-1]).tolist(), xyz.shape[0], max_len)
+        return torch_cpu.fps_ragged(xyz, offsets, int(npoint))
+    with torch.no_grad():
+        idx, centers = ops.fps_ragged(xyz, offsets, max_len, int(npoint), want_centers=True, lengths=lengths)
+    return centers, idx
+
+
+def cloud_norm_ragged(xyz, offsets, max_len, want_scale=False, lengths=None):
+    """pc_norm of every cloud of a packed batch (xyz (T,3) f64 or f32) -> (T,3) f32 [, scale (B,) f64]."""
+    if _torch_cpu(xyz, offsets):
+        from . import torch_cpu
+        ops.ragged_layout((offsets[1:] - offsets[:-1]).tolist(), xyz.shape[0], max_len, fps=False)
+        out, scale = torch_cpu.cloud_norm_ragged(xyz, offsets)
+        return (out, scale) if want_scale else out
+    with torch.no_grad():
+        return ops.cloud_norm_ragged(xyz, offsets, max_len, want_scale=want_scale, lengths=lengths)
+
+
 def knn_query(ref, query, k):
     """-> (dist (B,Q,k) f32, idx (B,Q,k) int64); no gradient (the reference wraps it in no_grad)."""
     if _torch_cpu(ref, query):

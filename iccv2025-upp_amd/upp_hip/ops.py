@@ -108,6 +108,99 @@ def fps(xyz, npoint, want_centers=False, waves=0):
     return (idx, centers) if want_centers else idx
 
 
+FPS_MAX_POINTS = 32768          # include/upp_hip.h upp_fps / upp_fps_ragged: 15-bit point ids
+
+
+def ragged_layout(lengths, total=None, max_len=None, fps=True):
+    """Host-side layout of a packed batch: lengths (a sequence or a CPU tensor of B ints) -> (offsets (B+1,) int64 CPU tensor, max_len).
+    Raises -- before anything is launched -- on an empty cloud, on lengths that do not sum to `total`, on a length above the promised
+    `max_len`, and (for the sampling kernel) on max_len > 32768.  Never touches a device."""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.is_cuda:
+            raise RuntimeError("lengths must be known on the host (a sequence or a CPU tensor): reading them from the device would synchronise")
+        lengths = lengths.reshape(-1).tolist()
+    lengths = [int(n) for n in lengths]
+    if any(n < 1 for n in lengths):
+        raise ValueError("ragged batch: cloud %d is empty (every cloud needs at least one point)" % [n < 1 for n in lengths].index(True))
+    longest = max(lengths, default=1)
+    if max_len is None:
+        max_len = longest
+    max_len = int(max_len)
+    if longest > max_len:
+        raise ValueError("ragged batch: a cloud of %d points, max_len = %d" % (longest, max_len))
+    if fps and max_len > FPS_MAX_POINTS:
+        raise ValueError("ragged batch: max_len = %d, furthest point sampling serves clouds of at most %d points" % (max_len, FPS_MAX_POINTS))
+    if total is not None and sum(lengths) != int(total):
+        raise ValueError("ragged batch: the lengths sum to %d, the packed array has %d points" % (sum(lengths), int(total)))
+    offsets = torch.zeros(len(lengths) + 1, dtype=torch.int64)
+    if lengths:
+        offsets[1:] = torch.tensor(lengths, dtype=torch.int64).cumsum(0)
+    return offsets, max_len
+
+
+def _ragged_args(xyz, dtypes, offsets, max_len, lengths, fps):
+    """The checks of the two packed-batch operators.  offsets: a CPU int64 tensor (checked here, then uploaded) or a device tensor (its
+    CONTENT is the caller's promise unless `lengths` -- host -- is given too: reading it back would synchronise).  -> (offsets on the device, B)."""
+    if not isinstance(xyz, torch.Tensor):
+        raise TypeError("xyz must be a torch.Tensor")
+    if not xyz.is_cuda:
+        raise RuntimeError("xyz must be a HIP (cuda) tensor; upp_hip has no CPU path")
+    if xyz.dtype not in dtypes:
+        raise RuntimeError(f"xyz must be {' or '.join(str(d) for d in dtypes)}, got {xyz.dtype}")
+    if not xyz.is_contiguous():
+        raise RuntimeError("xyz must be contiguous")
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise RuntimeError(f"xyz must be a packed (T, 3) array, got {tuple(xyz.shape)}")
+    if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise RuntimeError("offsets must be a 1-D int64 tensor of B + 1 entries")
+    if not offsets.is_contiguous():
+        raise RuntimeError("offsets must be contiguous")
+    max_len = int(max_len)
+    if max_len < 1 or (fps and max_len > FPS_MAX_POINTS):
+        raise ValueError("max_len = %d: must be in [1, %d]" % (max_len, FPS_MAX_POINTS) if fps else "max_len = %d: must be positive" % max_len)
+    B = offsets.numel() - 1
+    if not offsets.is_cuda:
+        if int(offsets[0]) != 0:
+            raise ValueError("offsets must start at 0")
+        lengths = (offsets[1:] - offsets[:-1]).tolist()
+    if lengths is not None:
+        host, _ = ragged_layout(lengths, xyz.shape[0], max_len, fps)
+        if host.numel() != B + 1:
+            raise ValueError("offsets hold %d clouds, lengths %d" % (B, host.numel() - 1))
+    if not offsets.is_cuda:
+        offsets = offsets.to(xyz.device, non_blocking=True)
+    elif offsets.device != xyz.device:
+        raise RuntimeError("all tensors must be on the same device")
+    return offsets, B, max_len
+
+
+def fps_ragged(xyz, offsets, max_len, npoint, want_centers=False, lengths=None):
+    """Furthest point sampling of every cloud of a packed batch in ONE launch (include/upp_hip.h upp_fps_ragged).
+    xyz (T,3) f32: the clouds back to back; offsets (B+1,) int64; max_len >= every length (host int) -> idx (B,npoint) int32, local to
+    each cloud and bit-identical to fps(cloud[None], npoint) [, centers (B,npoint,3)]."""
+    offsets, B, max_len = _ragged_args(xyz, (torch.float32,), offsets, max_len, lengths, True)
+    npoint = int(npoint)
+    if npoint < 1:
+        raise ValueError("npoint must be positive")
+    idx = torch.empty((B, npoint), dtype=torch.int32, device=xyz.device)
+    centers = torch.empty((B, npoint, 3), dtype=torch.float32, device=xyz.device) if want_centers else None
+    if B > 0:
+        _call(xyz.device, "upp_fps_ragged", _abi.ptr(xyz), _abi.ptr(offsets), _abi.ptr(idx), _abi.ptr(centers), B, max_len, npoint)
+    return (idx, centers) if want_centers else idx
+
+
+def cloud_norm_ragged(xyz, offsets, max_len, want_scale=False, lengths=None):
+    """The reference's pc_norm (datasets/RealSensorDataset.py:59-65) of every cloud of a packed batch in ONE launch: xyz (T,3) f64 (or f32:
+    upcast first) -> (T,3) f32 = (float)(p / (2 max |p|)), float64 arithmetic, the bits of the numpy expression [, scale (B,) f64]."""
+    offsets, B, max_len = _ragged_args(xyz, (torch.float64, torch.float32), offsets, max_len, lengths, False)
+    out = torch.empty(xyz.shape, dtype=torch.float32, device=xyz.device)
+    scale = torch.empty((B,), dtype=torch.float64, device=xyz.device) if want_scale else None
+    if B > 0:
+        name = "upp_cloud_norm_ragged" if xyz.dtype == torch.float64 else "upp_cloud_norm_ragged_f32"
+        _call(xyz.device, name, _abi.ptr(xyz), _abi.ptr(offsets), _abi.ptr(out), _abi.ptr(scale), B, max_len)
+    return (out, scale) if want_scale else out
+
+
 def gather_fwd(features, idx):
     _need(features, "features", torch.float32, 3)
     _need(idx, "idx", torch.int32, 2)

@@ -1,7 +1,8 @@
 """Pure-torch grouping operators for CPU tensors -- BASELINE configs[0] ("Point_MAE_unify cls forward, 1 synthetic N = 1024 cloud on
 torch-CPU: utils.misc.fps + torch.cdist kNN fallback -- plumbing, no GPU").  OFF by default: the product's operators have no CPU
 path (`upp_hip.ops` raises on CPU tensors) and a HIP tensor never comes here.  `enable()` -- or UPP_TORCH_CPU=1 in the environment --
-lets the four grouping entry points of upp_hip.functional (fps_gather, knn_query, knn_group, ChamferFunction) serve CPU tensors with the
+lets the grouping entry points of upp_hip.functional (fps_gather, knn_query, knn_group, ChamferFunction, and the packed-batch pair
+fps_gather_ragged / cloud_norm_ragged) serve CPU tensors with the
 torch formulations below, so that a reference user can run the model's forward on a GPU-less host to check plumbing (state-dict
 loading, shapes, config wiring).  Nothing here touches oracle/ (test infrastructure) and nothing here is timed by bench.py.
 
@@ -42,6 +43,31 @@ def fps(xyz, npoint):
         far = torch.where(live, dist, torch.full_like(dist, -1.0)).argmax(-1)      # first maximum: lowest index
     centers = torch.gather(xyz, 1, idx.unsqueeze(-1).expand(-1, -1, 3))
     return centers, idx.to(torch.int32)
+
+
+def fps_ragged(xyz, offsets, npoint):
+    """Packed batch: xyz (T,3) f32 CPU, offsets (B+1,) int64 CPU -> (centres (B,npoint,3), idx (B,npoint) int32 local to each cloud): fps()
+    above, one cloud at a time."""
+    o = offsets.tolist()
+    got = [fps(xyz[o[b]:o[b + 1]].unsqueeze(0), npoint) for b in range(len(o) - 1)]
+    if not got:
+        return torch.empty(0, npoint, 3, dtype=xyz.dtype), torch.empty(0, npoint, dtype=torch.int32)
+    return torch.cat([c for c, _ in got]), torch.cat([i for _, i in got])
+
+
+def cloud_norm_ragged(xyz, offsets):
+    """Packed batch: the reference's pc_norm (datasets/RealSensorDataset.py:59-65) per cloud, its own numpy expression in float64
+    -> ((T,3) f32, scale (B,) f64)."""
+    import numpy as np
+    p = xyz.detach().numpy().astype(np.float64)
+    o = offsets.tolist()
+    out = np.empty(p.shape, dtype=np.float32)
+    scale = np.empty(len(o) - 1, dtype=np.float64)
+    for b in range(len(o) - 1):
+        c = p[o[b]:o[b + 1]]
+        scale[b] = np.max(np.sqrt(np.sum(c ** 2, axis=1))) * 2
+        out[o[b]:o[b + 1]] = c / scale[b]
+    return torch.from_numpy(out), torch.from_numpy(scale)
 
 
 def knn(ref, query, k):

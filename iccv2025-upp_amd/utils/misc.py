@@ -18,6 +18,45 @@ def fps(data, number):
     return fps_data, fps_idx
 
 
+def fps_ragged(clouds_or_packed, lengths, number, normalize=False):
+    """FPS of a batch of clouds of DIFFERENT lengths in one launch -> (points (B,number,3) f32, idx (B,number) int32, local to each cloud):
+    cloud b's rows are those of fps(cloud_b[None], number).
+
+    clouds_or_packed: a sequence of (n_i,3) tensors on one device (lengths may be None), or one packed (T,3) tensor holding the clouds
+    back to back with `lengths` a host sequence / CPU tensor of the B lengths (a data loader knows them: offsets and the longest length
+    are derived on the host, nothing is read back from the device).  normalize=True first applies the reference's pc_norm
+    (datasets/RealSensorDataset.py:59-65: p / (2 max |p|), float64 arithmetic) to every cloud -- float64 or float32 input; without it the
+    input must be float32.  Two launches at the most, no per-cloud loop, no padding (padded zeros would change the tie order)."""
+    from upp_hip import ops
+    if isinstance(clouds_or_packed, (list, tuple)):
+        for c in clouds_or_packed:
+            if not isinstance(c, torch.Tensor) or c.dim() != 2 or c.shape[1] != 3:
+                raise ValueError("fps_ragged: every cloud must be a (n, 3) tensor")
+        if lengths is None:
+            lengths = [c.shape[0] for c in clouds_or_packed]
+        elif [int(n) for n in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)] != [c.shape[0] for c in clouds_or_packed]:
+            raise ValueError("fps_ragged: lengths do not match the clouds")
+        if any(c.shape[0] < 1 for c in clouds_or_packed):
+            raise ValueError("ragged batch: cloud %d is empty (every cloud needs at least one point)" % [c.shape[0] < 1 for c in clouds_or_packed].index(True))
+        packed = torch.cat(list(clouds_or_packed)) if clouds_or_packed else torch.empty(0, 3)
+    else:
+        packed = clouds_or_packed
+    if not isinstance(packed, torch.Tensor) or packed.dim() != 2 or packed.shape[1] != 3:
+        raise ValueError("fps_ragged: a packed (T, 3) tensor or a sequence of (n, 3) tensors is required")
+    if packed.dtype not in ((torch.float64, torch.float32) if normalize else (torch.float32,)):
+        raise RuntimeError("fps_ragged: the points must be %s, got %s" % ("float64 or float32" if normalize else "float32", packed.dtype))
+    if not packed.is_contiguous():
+        raise RuntimeError("fps_ragged: the packed points must be contiguous")
+    if lengths is None:
+        raise ValueError("fps_ragged: a packed tensor needs the lengths of its clouds")
+    offsets, max_len = ops.ragged_layout(lengths, packed.shape[0])
+    if packed.is_cuda:
+        offsets = offsets.to(packed.device, non_blocking=True)
+    if normalize:
+        packed = _F.cloud_norm_ragged(packed, offsets, max_len)
+    return _F.fps_gather_ragged(packed, offsets, max_len, number)
+
+
 def peft_detect(name, targets):
     """reference utils/misc.py:22-26"""
     return any(t in name for t in targets)

@@ -91,6 +91,35 @@ int upp_fps(const float *xyz, int32_t *idx, float *centers,
 int upp_fps_ex(const float *xyz, int32_t *idx, float *centers,
                int B, int N, int M, int waves, void *stream);
 
+/* ---- packed ("ragged") batches: clouds of different lengths --------------------
+ * The clouds of a batch lie back to back in one (T,3) array; cloud b is rows offsets[b] ... offsets[b+1]-1 (offsets: B+1 int64 ON THE
+ * DEVICE, non-decreasing from 0 to T; the Python layer checks them on the host).  max_len is a host promise: every length is in
+ * [1, max_len].  It sizes the launch; a longer cloud is cut to its first max_len points, an empty one yields zeros -- neither reads or
+ * writes outside its rows.  One launch per call, no host synchronisation, nothing is zeroed.
+ *
+ * upp_fps_ragged: furthest point sampling of every cloud of a packed batch in ONE launch.
+ *   idx     (B,M)   int32 out: indices LOCAL to the cloud -- bit for bit what upp_fps returns for that cloud alone (B = 1, N = its length):
+ *           the tie order of the reference kernel depends on N (T = min(512, 2^floor(log2 N))), so each workgroup derives it from its
+ *           own cloud's length.  M > length is legal: once every distance is 0 the winner is point 0.
+ *   centers (B,M,3) f32 out or NULL
+ * Limits: 1 <= M, 1 <= max_len <= 32768.
+ * upp_fps_ragged_slots (host function, no launch): the points one lane must hold so that EVERY length 1 ... max_len fits a launch of `waves`
+ * wavefronts per cloud (1, 2, 4, 8; 0 = the library's choice for max_len) -- the maximum over the lengths, which the longest one need not
+ * attain (511 points: 256 threads x 2; 512 points: 512 x 1). */
+int upp_fps_ragged(const float *xyz, const int64_t *offsets, int32_t *idx, float *centers,
+                   int B, int max_len, int M, void *stream);
+int upp_fps_ragged_slots(int max_len, int waves);
+/* upp_cloud_norm_ragged: the reference's pc_norm (datasets/RealSensorDataset.py:59-65) of every cloud of a packed batch, in float64 as
+ * numpy evaluates it:  scale[b] = 2 sqrt(max_i ((x*x + y*y) + z*z)),  out = (float)(p / scale[b])  -- no contraction, IEEE sqrt and
+ * division: the same bits as the numpy expression.  (Here max_len only caps the rows a workgroup touches; any positive value.)
+ *   xyz   (T,3) f64 (upp_cloud_norm_ragged) or f32 (upp_cloud_norm_ragged_f32: upcast, then the same arithmetic)
+ *   out   (T,3) f32 out
+ *   scale (B,)  f64 out or NULL */
+int upp_cloud_norm_ragged(const double *xyz, const int64_t *offsets, float *out, double *scale,
+                          int B, int max_len, void *stream);
+int upp_cloud_norm_ragged_f32(const float *xyz, const int64_t *offsets, float *out, double *scale,
+                              int B, int max_len, void *stream);
+
 /* ---- gather_operation ---------------------------------------------------------
  * Replaces pointnet2_ops._ext.gather_points / gather_points_grad
  * (sampling_gpu.cu gather_points_kernel / gather_points_grad_kernel; called
