@@ -41,6 +41,12 @@ SIGNATURES = {
     "upp_emd_approxmatch": (_c_i, [_c_f] * 4 + [_c_i] * 3 + [_c_f]),
     "upp_emd_matchcost": (_c_i, [_c_f] * 4 + [_c_i] * 3 + [_c_f]),
     "upp_emd_matchcost_bwd": (_c_i, [_c_f] * 6 + [_c_i] * 3 + [_c_f]),
+    "upp_chamfer_bwd_det": (_c_i, [_c_f] * 8 + [_c_i] * 3 + [_c_f]),
+    "upp_group_bwd_det": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_f]),
+    "upp_gather_bwd_det": (_c_i, [_c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_f]),
+    "upp_fps_gather_bwd_det": (_c_i, [_c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_f]),
+    "upp_emd_matchcost_det_work_bytes": (ctypes.c_longlong, [_c_i, _c_i, _c_i]),
+    "upp_emd_matchcost_det": (_c_i, [_c_f] * 5 + [_c_i] * 3 + [_c_f]),
     "upp_patch_embed_work_floats": (ctypes.c_longlong, [_c_i, _c_i]),
     "upp_patch_embed_fwd": (_c_i, [_c_f, _c_i, _c_i] + [_c_f] * 6 + [_c_f] * 2 + [_c_f] * 6 + [_c_f] * 2 + [_c_i]
                             + [ctypes.c_float, ctypes.c_float, _c_i] + [_c_f, _c_f, _c_f]),

@@ -193,14 +193,12 @@ __global__ __launch_bounds__(256) void emd_match_kernel(const float *__restrict_
     }
 }
 
-// cost[b] += sum_{k,l} d(k,l) * match[l,k]   (emd_kernel.cu:199-242).  lane = k.
-__global__ __launch_bounds__(256) void emd_cost_kernel(const float *__restrict__ xyz1, const float *__restrict__ xyz2,
-                                                       const float *__restrict__ match, float *__restrict__ cost, int n, int m) {
+// p_t = sum_{k in tile t, l} d(k,l) * match[l,k] of one 64-point tile of xyz1 (emd_kernel.cu:199-242), lane = k: the value thread 0 returns.
+__device__ __forceinline__ float emd_cost_tile(const float *__restrict__ xyz1, const float *__restrict__ xyz2, const float *__restrict__ match,
+                                               int n, int m, int tile_x, int b) {
     __shared__ float4 tile[kT];
     __shared__ float part[4];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // scalar: loop counters and LDS offsets in SGPRs
-    int tile_x, b;
-    xcd_cloud_tile(tile_x, b);                            // whole clouds per XCD (common.h)
     const int k = tile_x * 64 + lane;
     const int kc = k < n ? k : n - 1;
     const float *a = xyz1 + ((size_t)b * n + kc) * 3;
@@ -227,7 +225,33 @@ __global__ __launch_bounds__(256) void emd_cost_kernel(const float *__restrict__
     const float ws = wave_sum_f32(s);
     if (lane == 0) part[wave] = ws;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(&cost[b], (part[0] + part[1]) + (part[2] + part[3]));
+    return (part[0] + part[1]) + (part[2] + part[3]);
+}
+
+// cost[b] += p_t, one atomicAdd per tile: the order of the tiles is the hardware's
+__global__ __launch_bounds__(256) void emd_cost_kernel(const float *__restrict__ xyz1, const float *__restrict__ xyz2,
+                                                       const float *__restrict__ match, float *__restrict__ cost, int n, int m) {
+    int tile_x, b;
+    xcd_cloud_tile(tile_x, b);                            // whole clouds per XCD (common.h)
+    const float p = emd_cost_tile(xyz1, xyz2, match, n, m, tile_x, b);
+    if (threadIdx.x == 0) atomicAdd(&cost[b], p);
+}
+
+// The deterministic sibling (upp_emd_matchcost_det): the same p_t stored to work[b][t], then cost[b] = ((+0.0f + p_0) + p_1) + ... in
+// ascending t by one lane per cloud -- ceil(n / 64) dependent additions (16 at n = 1,024).
+__global__ __launch_bounds__(256) void emd_cost_part_kernel(const float *__restrict__ xyz1, const float *__restrict__ xyz2,
+                                                            const float *__restrict__ match, float *__restrict__ work, int n, int m) {
+    int tile_x, b;
+    xcd_cloud_tile(tile_x, b);
+    const float p = emd_cost_tile(xyz1, xyz2, match, n, m, tile_x, b);
+    if (threadIdx.x == 0) work[(size_t)b * gridDim.x + tile_x] = p;
+}
+__global__ __launch_bounds__(64) void emd_cost_sum_kernel(const float *__restrict__ work, float *__restrict__ cost, int B, int tiles) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    float s = 0.0f;
+    for (int t = 0; t < tiles; ++t) s = __fadd_rn(s, work[(size_t)b * tiles + t]);
+    cost[b] = s;
 }
 
 // grad1[b,l] = gc[b] * sum_k 2*match[k,l] * (p1_l - p2_k)   (matchcostgrad1, :332-354).  lane = l.
@@ -340,6 +364,23 @@ extern "C" int upp_emd_matchcost(const float *xyz1, const float *xyz2, const flo
     hipStream_t st = (hipStream_t)stream;
     upp_zero_async(cost, B, st);                                     // (a kernel, not a memset node: common.h)
     hipLaunchKernelGGL(emd_cost_kernel, dim3((n + 63) / 64, B), dim3(256), 0, st, xyz1, xyz2, match, cost, n, m);
+    return upp_launch_status();
+}
+
+extern "C" long long upp_emd_matchcost_det_work_bytes(int B, int n, int m) {
+    if (B < 0 || n < 0 || m < 0) return 0;
+    return (long long)B * (((long long)n + 63) / 64) * (long long)sizeof(float);
+}
+
+extern "C" int upp_emd_matchcost_det(const float *xyz1, const float *xyz2, const float *match, float *cost, float *work, int B, int n, int m,
+                                     void *stream) {
+    if (!xyz1 || !xyz2 || !match || !cost || !work || B < 0 || n < 1 || m < 1) return UPP_E_BADARG;
+    if (B == 0) return 0;
+    if (B > 65535) return UPP_E_RANGE;
+    hipStream_t st = (hipStream_t)stream;
+    const int tiles = (n + 63) / 64;
+    hipLaunchKernelGGL(emd_cost_part_kernel, dim3(tiles, B), dim3(256), 0, st, xyz1, xyz2, match, work, n, m);
+    hipLaunchKernelGGL(emd_cost_sum_kernel, dim3((B + 63) / 64), dim3(64), 0, st, work, cost, B, tiles);
     return upp_launch_status();
 }
 

@@ -7,6 +7,7 @@
 // All four are pure HBM-bound byte movers: flat grid-stride kernels, one
 // element per lane, coalesced on the dense side.
 #include "common.h"
+#include "det_scan.h"
 
 namespace {
 
@@ -97,6 +98,84 @@ __global__ __launch_bounds__(256) void fps_gather_bwd_kernel(const float *__rest
     }
 }
 
+// ---- the deterministic siblings (include/upp_hip.h "deterministic scatter-adds") ------------------------------------------------------
+// out[b][r][0..2] = +0.0f, then + val[b][s][0..2] for every source s with idx[b][s] == r, in ascending s: the xyz gradient of the grouping
+// gather (IdxT = int64, s = g * K + k) and of the FPS centre gather (int32).  One lane per target row, det_scan.h's ordered pull; every
+// row is written (rows that nobody references: +0.0f), so the caller zero-fills nothing.  Indices outside [0, N) are skipped.
+template <typename IdxT>
+__global__ __launch_bounds__(kDetThreads) void rows3_bwd_det_kernel(const float *__restrict__ val, const IdxT *__restrict__ idx,
+                                                                    float *__restrict__ out, int B, int N, long long S) {
+    __shared__ __attribute__((aligned(16))) int32_t keys[kDetChunk];
+    __shared__ float vals[kDetChunk * 3];
+    const int tid = threadIdx.x;
+    const long long tiles = (N + kDetThreads - 1) / kDetThreads, items = (long long)B * tiles;
+    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
+        const long long b = it / tiles, r = (it - b * tiles) * kDetThreads + tid;
+        const int target = r < N ? (int)r : -2;
+        const IdxT *ib = idx + (size_t)b * S;
+        const float *vb = val + (size_t)b * S * 3;
+        float acc[3] = {0.0f, 0.0f, 0.0f};
+        for (long long c0 = 0; c0 < S; c0 += kDetChunk) {
+            const int len = (int)min((long long)kDetChunk, S - c0), len4 = (len + 3) & ~3;
+            __syncthreads();
+#pragma unroll
+            for (int i = tid; i < kDetChunk; i += kDetThreads) {
+                if (i < len) { const IdxT k = ib[c0 + i]; keys[i] = (k >= 0 && k < (IdxT)N) ? (int32_t)k : -1; }
+                else if (i < len4) keys[i] = -1;
+            }
+            stage_floats(vals, vb + (size_t)c0 * 3, len * 3, tid, kDetThreads);
+            __syncthreads();
+            det_pull<3>(keys, vals, len4, target, acc);
+        }
+        if (r < N) {
+            float *o = out + ((size_t)b * N + r) * 3;
+            o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
+        }
+    }
+}
+
+// grad_feat[b][ch][r] = +0.0f, then + grad_out[b][ch][j] for every j with idx[b][j] == r, in ascending j.  A workgroup owns 256 targets of
+// one cloud and kDetCh channels: the key chunk it stages serves all of them.
+constexpr int kDetCh = 4;
+__global__ __launch_bounds__(kDetThreads) void gather_bwd_det_kernel(const float *__restrict__ grad_out, const int32_t *__restrict__ idx,
+                                                                     float *__restrict__ grad_feat, int B, int C, int N, int M) {
+    __shared__ __attribute__((aligned(16))) int32_t keys[kDetChunk];
+    __shared__ float vals[kDetChunk * kDetCh];
+    const int tid = threadIdx.x;
+    const long long tiles = (N + kDetThreads - 1) / kDetThreads, groups = (C + kDetCh - 1) / kDetCh, items = (long long)B * groups * tiles;
+    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
+        const long long b = it / (groups * tiles), rest = it - b * groups * tiles;
+        const int ch0 = (int)(rest / tiles) * kDetCh;
+        const long long r = (rest % tiles) * kDetThreads + tid;
+        const int target = r < N ? (int)r : -2;
+        const int32_t *ib = idx + (size_t)b * M;
+        float acc[kDetCh] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int c0 = 0; c0 < M; c0 += kDetChunk) {
+            const int len = min(kDetChunk, M - c0), len4 = (len + 3) & ~3;
+            __syncthreads();
+#pragma unroll
+            for (int i = tid; i < kDetChunk; i += kDetThreads) {
+                if (i < len) {
+                    const int k = ib[c0 + i];
+                    keys[i] = (k >= 0 && k < N) ? k : -1;
+#pragma unroll
+                    for (int v = 0; v < kDetCh; ++v)
+                        vals[i * kDetCh + v] = ch0 + v < C ? grad_out[((size_t)b * C + ch0 + v) * M + c0 + i] : 0.0f;
+                } else if (i < len4) {
+                    keys[i] = -1;
+                }
+            }
+            __syncthreads();
+            det_pull<kDetCh>(keys, vals, len4, target, acc);
+        }
+        if (r < N) {
+#pragma unroll
+            for (int v = 0; v < kDetCh; ++v)
+                if (ch0 + v < C) grad_feat[((size_t)b * C + ch0 + v) * N + r] = acc[v];
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int upp_gather_fwd(const float *feat, const int32_t *idx, float *out, int B, int C, int N, int M, void *stream) {
@@ -140,5 +219,37 @@ extern "C" int upp_group_bwd(const float *grad_out, const int64_t *idx, float *g
         const long long tc = (long long)B * G * 3;
         hipLaunchKernelGGL(group_bwd_center_kernel, dim3(grid_for(tc)), dim3(kBlock), 0, (hipStream_t)stream, grad_out, grad_center, K, tc);
     }
+    return upp_launch_status();
+}
+
+extern "C" int upp_gather_bwd_det(const float *grad_out, const int32_t *idx, float *grad_feat, int B, int C, int N, int M, void *stream) {
+    if (!grad_out || !idx || !grad_feat || B < 0 || C < 0 || N < 1 || M < 0) return UPP_E_BADARG;
+    if (B == 0 || C == 0) return 0;
+    const long long items = (long long)B * ((C + kDetCh - 1) / kDetCh) * ((N + kDetThreads - 1) / kDetThreads);
+    hipLaunchKernelGGL(gather_bwd_det_kernel, dim3(det_grid(items)), dim3(kDetThreads), 0, (hipStream_t)stream, grad_out, idx, grad_feat, B, C, N, M);
+    return upp_launch_status();
+}
+
+extern "C" int upp_fps_gather_bwd_det(const float *g_centers, const int32_t *idx, float *g_xyz, int B, int N, int M, void *stream) {
+    if (!g_centers || !idx || !g_xyz || B < 0 || N < 1 || M < 0) return UPP_E_BADARG;
+    if (B == 0) return 0;
+    const long long items = (long long)B * ((N + kDetThreads - 1) / kDetThreads);
+    hipLaunchKernelGGL(rows3_bwd_det_kernel<int32_t>, dim3(det_grid(items)), dim3(kDetThreads), 0, (hipStream_t)stream, g_centers, idx, g_xyz, B, N,
+                       (long long)M);
+    return upp_launch_status();
+}
+
+extern "C" int upp_group_bwd_det(const float *grad_out, const int64_t *idx, float *grad_xyz, float *grad_center, int B, int N, int G, int K,
+                                 void *stream) {
+    if (!grad_out || !idx || B < 0 || N < 1 || G < 0 || K < 0) return UPP_E_BADARG;
+    if (B == 0) return 0;
+    if (grad_xyz) {
+        const long long items = (long long)B * ((N + kDetThreads - 1) / kDetThreads);
+        hipLaunchKernelGGL(rows3_bwd_det_kernel<int64_t>, dim3(det_grid(items)), dim3(kDetThreads), 0, (hipStream_t)stream, grad_out, idx, grad_xyz, B, N,
+                           (long long)G * K);
+    }
+    const long long tc = (long long)B * G * 3;
+    if (grad_center && tc > 0 && K > 0)            // (k ascending already: the sibling's kernel, launched as the sibling launches it)
+        hipLaunchKernelGGL(group_bwd_center_kernel, dim3(grid_for(tc)), dim3(kBlock), 0, (hipStream_t)stream, grad_out, grad_center, K, tc);
     return upp_launch_status();
 }

@@ -9,7 +9,6 @@ from torch.autograd import Function
 
 from . import ops
 
-
 class FurthestPointSampling(Function):
     """pointnet2_utils.furthest_point_sample: (B,N,3) f32, npoint -> (B,npoint) int32, non-differentiable."""
 
@@ -36,7 +35,7 @@ class GatherOperation(Function):
     @staticmethod
     def backward(ctx, grad_out):
         (idx,) = ctx.saved_tensors
-        return ops.gather_bwd(grad_out.contiguous(), idx, ctx.N), None
+        return ops.gather_bwd(grad_out.contiguous(), idx, ctx.N, deterministic=DETERMINISTIC), None
 
 
 class _FpsGather(Function):
@@ -56,7 +55,7 @@ class _FpsGather(Function):
         if grad_centers is None:
             return None, None
         (idx,) = ctx.saved_tensors
-        return ops.fps_gather_bwd(grad_centers.contiguous(), idx, ctx.N), None        # (one launch: zero-fill + int32 indices + scatter)
+        return ops.fps_gather_bwd(grad_centers.contiguous(), idx, ctx.N, deterministic=DETERMINISTIC), None        # (one launch: zero-fill + int32 indices + scatter)
 
 
 class _KnnGroup(Function):
@@ -79,7 +78,7 @@ class _KnnGroup(Function):
             return None, None, None
         (idx,) = ctx.saved_tensors
         gx, gc = ops.group_bwd(grad_neigh.contiguous(), idx, ctx.N,
-                               need_xyz=ctx.needs_input_grad[0], need_center=ctx.needs_input_grad[1])
+                               need_xyz=ctx.needs_input_grad[0], need_center=ctx.needs_input_grad[1], deterministic=DETERMINISTIC)
         return gx, gc, None
 
 
@@ -96,7 +95,7 @@ class _GroupPoints(Function):
     def backward(ctx, grad_out):
         (idx,) = ctx.saved_tensors
         gx, gc = ops.group_bwd(grad_out.contiguous(), idx, ctx.N,
-                               need_xyz=ctx.needs_input_grad[0], need_center=ctx.needs_input_grad[1])
+                               need_xyz=ctx.needs_input_grad[0], need_center=ctx.needs_input_grad[1], deterministic=DETERMINISTIC)
         return gx, gc, None
 
 
@@ -112,7 +111,7 @@ class ChamferFunction(Function):
     @staticmethod
     def backward(ctx, grad_dist1, grad_dist2):
         xyz1, xyz2, idx1, idx2 = ctx.saved_tensors
-        return ops.chamfer_bwd(xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2)
+        return ops.chamfer_bwd(xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2, deterministic=DETERMINISTIC)
 
 
 class _ChamferLoss(Function):
@@ -129,7 +128,7 @@ class _ChamferLoss(Function):
     @staticmethod
     def backward(ctx, g):
         xyz1, xyz2, idx1, idx2, fac1, fac2 = ctx.saved_tensors
-        g1, g2 = ops.chamfer_bwd(xyz1, xyz2, idx1, idx2, fac1 * g, fac2 * g)
+        g1, g2 = ops.chamfer_bwd(xyz1, xyz2, idx1, idx2, fac1 * g, fac2 * g, deterministic=DETERMINISTIC)
         return g1, g2, None
 
 
@@ -147,7 +146,7 @@ class EarthMoverDistanceFunction(Function):
         xyz2 = xyz2.contiguous()
         assert xyz1.is_cuda and xyz2.is_cuda, "Only support cuda currently."
         match = ops.emd_approxmatch(xyz1, xyz2)
-        cost = ops.emd_matchcost(xyz1, xyz2, match)
+        cost = ops.emd_matchcost(xyz1, xyz2, match, deterministic=DETERMINISTIC)
         ctx.save_for_backward(xyz1, xyz2, match)
         return cost
 
@@ -1667,6 +1666,31 @@ class _Adapter(Function):
 
 FUSE_TAIL_BACKWARD = True     # _LnAdapter.backward: one launch (upp_ln_adapter_bwd_fused) instead of adapter backward + row backward
 ADAPTER_FACTORS = True        # ... which inside a deferred scope writes per-row factors; the weight gradients of all blocks in one launch at its exit
+
+# Reproducible training (README "Reproducible training"): with DETERMINISTIC on, the autograd nodes whose backward (or forward: the EMD
+# cost) sums with f32 atomics -- GatherOperation, _FpsGather, _KnnGroup, _GroupPoints, ChamferFunction, _ChamferLoss,
+# EarthMoverDistanceFunction -- call the library's `_det` siblings (a defined summation order: include/upp_hip.h "deterministic
+# scatter-adds").  Read at CALL time, also by the backward thread; a captured step keeps the choice it was captured under, whatever the
+# attribute says at replay.  UPP_DETERMINISTIC=1 sets it once, at import.
+DETERMINISTIC = os.environ.get("UPP_DETERMINISTIC", "").strip() not in ("", "0")
+
+
+class deterministic:
+    """with functional.deterministic(): ... -- DETERMINISTIC set to `on` inside the block and restored after it (also on an exception)."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        global DETERMINISTIC
+        self.prev = DETERMINISTIC
+        DETERMINISTIC = self.on
+        return self
+
+    def __exit__(self, *exc):
+        global DETERMINISTIC
+        DETERMINISTIC = self.prev
+        return False
 
 
 class _LnAdapter(Function):

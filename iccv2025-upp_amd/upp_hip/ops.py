@@ -212,10 +212,16 @@ def gather_fwd(features, idx):
     return out
 
 
-def gather_bwd(grad_out, idx, N):
+def gather_bwd(grad_out, idx, N, deterministic=False):
+    """deterministic: the sums in ascending source index (upp_gather_bwd_det, include/upp_hip.h) instead of f32 atomics."""
     _need(grad_out, "grad_out", torch.float32, 3)
     _need(idx, "idx", torch.int32, 2)
     B, C, M = grad_out.shape
+    if deterministic:
+        grad = torch.empty((B, C, N), dtype=torch.float32, device=grad_out.device)       # (overwritten in full)
+        if B and C:
+            _call(grad_out.device, "upp_gather_bwd_det", _abi.ptr(grad_out), _abi.ptr(idx), _abi.ptr(grad), B, C, N, M)
+        return grad
     grad = torch.zeros((B, C, N), dtype=torch.float32, device=grad_out.device)
     _call(grad_out.device, "upp_gather_bwd", _abi.ptr(grad_out), _abi.ptr(idx), _abi.ptr(grad), B, C, N, M)
     return grad
@@ -255,18 +261,26 @@ def group_fwd(xyz, center, idx):
     return out
 
 
-def group_bwd(grad_out, idx, N, need_xyz=True, need_center=True):
+def group_bwd(grad_out, idx, N, need_xyz=True, need_center=True, deterministic=False):
+    """deterministic: grad_xyz summed in ascending g * K + k (upp_group_bwd_det, include/upp_hip.h) instead of f32 atomics."""
     _need(grad_out, "grad_out", torch.float32, 4, 3)
     _need(idx, "idx", torch.int64, 3)
     B, G, K = idx.shape
+    if deterministic:
+        gx = torch.empty((B, N, 3), dtype=torch.float32, device=grad_out.device) if need_xyz else None      # (overwritten in full)
+        gc = torch.empty((B, G, 3), dtype=torch.float32, device=grad_out.device) if need_center else None
+        if B:
+            _call(grad_out.device, "upp_group_bwd_det", _abi.ptr(grad_out), _abi.ptr(idx), _abi.ptr(gx), _abi.ptr(gc), B, N, G, K)
+        return gx, gc
     gx = torch.zeros((B, N, 3), dtype=torch.float32, device=grad_out.device) if need_xyz else None
     gc = torch.empty((B, G, 3), dtype=torch.float32, device=grad_out.device) if need_center else None
     _call(grad_out.device, "upp_group_bwd", _abi.ptr(grad_out), _abi.ptr(idx), _abi.ptr(gx), _abi.ptr(gc), B, N, G, K)
     return gx, gc
 
 
-def fps_gather_bwd(grad_centers, idx, N):
-    """Gradient of the FPS centre gather: grad_centers (B,M,3), idx (B,M) int32 -> (B,N,3) (upp_fps_gather_bwd: one launch)."""
+def fps_gather_bwd(grad_centers, idx, N, deterministic=False):
+    """Gradient of the FPS centre gather: grad_centers (B,M,3), idx (B,M) int32 -> (B,N,3) (upp_fps_gather_bwd: one launch).
+    deterministic: repeated indices summed in ascending j (upp_fps_gather_bwd_det)."""
     _need(grad_centers, "grad_centers", torch.float32, 3, 3)
     _need(idx, "idx", torch.int32, 2)
     B, M = idx.shape
@@ -274,7 +288,7 @@ def fps_gather_bwd(grad_centers, idx, N):
         raise RuntimeError("fps_gather_bwd: grad_centers must be (B, M, 3) for idx (B, M)")
     gx = torch.empty((B, int(N), 3), dtype=torch.float32, device=grad_centers.device)
     if B:
-        _call(grad_centers.device, "upp_fps_gather_bwd", _abi.ptr(grad_centers), _abi.ptr(idx), _abi.ptr(gx), B, int(N), M)
+        _call(grad_centers.device, "upp_fps_gather_bwd_det" if deterministic else "upp_fps_gather_bwd", _abi.ptr(grad_centers), _abi.ptr(idx), _abi.ptr(gx), B, int(N), M)
     return gx
 
 
@@ -299,7 +313,9 @@ def chamfer_fwd(xyz1, xyz2):
     return dist1, dist2, idx1, idx2
 
 
-def chamfer_bwd(xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2):
+def chamfer_bwd(xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2, deterministic=False):
+    """deterministic: every gradient row = own term, then the other cloud's terms in ascending index (upp_chamfer_bwd_det,
+    include/upp_hip.h) instead of f32 atomics."""
     _need(xyz1, "xyz1", torch.float32, 3, 3)
     _need(xyz2, "xyz2", torch.float32, 3, 3)
     _need(idx1, "idx1", torch.int32, 2)
@@ -314,7 +330,7 @@ def chamfer_bwd(xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2):
     g2 = torch.empty_like(xyz2)
     if B == 0:
         return g1, g2
-    _call(xyz1.device, "upp_chamfer_bwd", _abi.ptr(xyz1), _abi.ptr(xyz2), _abi.ptr(idx1), _abi.ptr(idx2),
+    _call(xyz1.device, "upp_chamfer_bwd_det" if deterministic else "upp_chamfer_bwd", _abi.ptr(xyz1), _abi.ptr(xyz2), _abi.ptr(idx1), _abi.ptr(idx2),
           _abi.ptr(grad_dist1), _abi.ptr(grad_dist2), _abi.ptr(g1), _abi.ptr(g2), B, n, m)
     return g1, g2
 
@@ -351,7 +367,8 @@ def emd_approxmatch(xyz1, xyz2):
     return match
 
 
-def emd_matchcost(xyz1, xyz2, match):
+def emd_matchcost(xyz1, xyz2, match, deterministic=False):
+    """deterministic: the 64-point tiles' partial costs summed in ascending tile order (upp_emd_matchcost_det) instead of atomics."""
     _need(xyz1, "xyz1", torch.float32, 3, 3)
     _need(xyz2, "xyz2", torch.float32, 3, 3)
     _need(match, "match", torch.float32, 3)
@@ -361,6 +378,11 @@ def emd_matchcost(xyz1, xyz2, match):
         raise RuntimeError("match must be (B, n2, n1)")
     cost = torch.empty((B,), dtype=torch.float32, device=xyz1.device)
     if B == 0:
+        return cost
+    if deterministic:
+        nwork = int(_abi.load().upp_emd_matchcost_det_work_bytes(B, n, m))
+        work = torch.empty(((max(nwork, 4) + 3) // 4,), dtype=torch.float32, device=xyz1.device)
+        _call(xyz1.device, "upp_emd_matchcost_det", _abi.ptr(xyz1), _abi.ptr(xyz2), _abi.ptr(match), _abi.ptr(cost), _abi.ptr(work), B, n, m)
         return cost
     _call(xyz1.device, "upp_emd_matchcost", _abi.ptr(xyz1), _abi.ptr(xyz2), _abi.ptr(match), _abi.ptr(cost), B, n, m)
     return cost

@@ -9,6 +9,7 @@ tools/runner_module.py:193-212) built for MI355X:
     graph launch (the eager step is launch-bound: 32 ms wall vs 24 ms of kernels).  The
     all-reduce stays outside the graphs; clip + AdamW are a second graph.
 """
+import contextlib
 import os
 import torch
 import torch.distributed as dist
@@ -225,8 +226,12 @@ class TrainStep:
     driven with step_inputs(*tensors)."""
 
     def __init__(self, model, batch_shape, grad_clip=10.0, use_graph=True, forward_kwargs=None, lr=5e-4, loss_fn=None,
-                 inputs=None):
+                 inputs=None, deterministic=None):
+        """deterministic: True / False = every pass of THIS driver (warm-up, capture, eager steps) runs with functional.DETERMINISTIC set
+        to it and restores the attribute afterwards; None = whatever the attribute says when the pass runs.  A captured step keeps the
+        choice it was captured under (README "Reproducible training")."""
         self.model = model
+        self.deterministic = None if deterministic is None else bool(deterministic)
         self.device = next(model.parameters()).device
         self.grad_clip = grad_clip
         self.kw = forward_kwargs or dict(completion_prompt=True, denoise=True, point_num=1024)
@@ -258,7 +263,14 @@ class TrainStep:
     # -- the two halves of a step ------------------------------------------------------------
     _seed = None
 
+    def _mode(self):
+        return contextlib.nullcontext() if self.deterministic is None else HF.deterministic(self.deterministic)
+
     def _forward_backward(self, pts=None, labels=None, kw=None):
+        with self._mode():
+            self._forward_backward_pass(pts, labels, kw)
+
+    def _forward_backward_pass(self, pts=None, labels=None, kw=None):
         pts = self.pts if pts is None else pts
         labels = self.labels if labels is None else labels
         self.flat.zero()
@@ -424,13 +436,14 @@ class PipelinedTrainStep(TrainStep):
     workspaces are not shared between graphs that run concurrently."""
 
     def __init__(self, model, batch_shape, grad_clip=10.0, forward_kwargs=None, lr=5e-4, front_fn=None, back_fn=None, extras=None,
-                 back_end_keys=_BACK_END_KEYS):
+                 back_end_keys=_BACK_END_KEYS, deterministic=None):
         """Other recipes than the classification one: front_fn(model, pts) -> tuple of tensors (the hand-over state; default
         model.prompt_tokens), back_fn(model, state, *extras) -> (loss, metric) (default: cross-entropy of
         model.forward_tokens(*state) against extras[0] = labels), extras = example tensors of the per-batch inputs the
         back-end needs besides the state (labels, targets, ...; one static copy per pipeline slot);
         back_end_keys = substrings every trainable parameter name must contain one of (the front-end must be frozen)."""
-        super().__init__(model, batch_shape, grad_clip=grad_clip, use_graph=True, forward_kwargs=forward_kwargs, lr=lr)
+        super().__init__(model, batch_shape, grad_clip=grad_clip, use_graph=True, forward_kwargs=forward_kwargs, lr=lr,
+                         deterministic=deterministic)
         if self.device.type != 'cuda' or not (hasattr(model, 'prompt_tokens') or front_fn is not None):
             raise RuntimeError("PipelinedTrainStep needs a HIP device and a model with prompt_tokens() / forward_tokens()")
         names = {id(p): n for n, p in model.named_parameters()}
@@ -485,7 +498,7 @@ class PipelinedTrainStep(TrainStep):
     # -- the three parts of a step -----------------------------------------------------------
     def _front(self, p):
         # (the front-end runs beside the back-end: its FPS launches keep to CUs of their own -- ops.fps_form; UPP_PIPE_FPS_FORM=0: the spread form)
-        with torch.no_grad(), self._L.use_rng(self._bank_front), HF.ops.fps_form(*self._fps_form):
+        with torch.no_grad(), self._L.use_rng(self._bank_front), HF.ops.fps_form(*self._fps_form), self._mode():
             if self.front_fn is not None:
                 state = self.front_fn(self.model, self.pts)
             else:

@@ -178,7 +178,8 @@ int upp_fps_gather_bwd(const float *g_centers, const int32_t *idx, float *g_xyz,
  *         other direction.
  * Backward: g1 (B,n,3) and g2 (B,m,3) are OVERWRITTEN (no pre-zeroing: the reference's wrapper allocates zeros and its kernel adds,
  * chamfer.cu:194-199,215-222); sums by f32 atomics in an unspecified order as there -- in the LDS, one workgroup per cloud pair, when
- * both gradient arrays fit (n + m <= 5,461), in global memory otherwise. */
+ * both gradient arrays fit (n + m <= 5,461), in global memory otherwise.  The same sums in a defined order: upp_chamfer_bwd_det
+ * ("deterministic scatter-adds" below). */
 int upp_chamfer_fwd(const float *xyz1, const float *xyz2,
                     float *dist1, float *dist2, int32_t *idx1, int32_t *idx2,
                     int B, int n, int m, void *stream);
@@ -210,6 +211,40 @@ int upp_emd_matchcost(const float *xyz1, const float *xyz2, const float *match, 
                       int B, int n, int m, void *stream);
 int upp_emd_matchcost_bwd(const float *grad_cost, const float *xyz1, const float *xyz2, const float *match,
                           float *grad1, float *grad2, int B, int n, int m, void *stream);
+
+/* ---- deterministic scatter-adds ---------------------------------------------------
+ * Per-call siblings of the five entry points whose f32 sums the hardware orders (atomics): the arguments, shapes, limits and error
+ * codes of the sibling (upp_emd_matchcost_det takes a scratch pointer besides), the same terms, a DEFINED summation order -- each
+ * can be restated on the CPU and compared bit for bit (tests/_det_reference.py), and two runs give the same bits.  Every product
+ * and sum below is one f32 operation rounded to nearest, none contracted into an fma.  Every output is overwritten in full on
+ * every launch (nothing to zero-fill), all work is kernel launches, nothing is allocated or read back.  No process-wide switch:
+ * the choice is the entry point.  Kernels: one lane per TARGET walks its cloud's sources in ascending index (csrc/det_scan.h:
+ * O(targets x sources / 64) wave steps per cloud whatever the index distribution, no size limit, no scratch).
+ *
+ *   upp_chamfer_bwd_det     t1(j)[c] = (grad_dist1[b][j] * 2.0f) * (xyz1[b][j][c] - xyz2[b][idx1[b][j]][c]), t2(i) likewise from cloud 2.
+ *                           g1[b][j][c] = +0.0f + t1(j)[c], then - t2(i)[c] for every i with idx2[b][i] == j, in ascending i;
+ *                           g2 the mirror image.  (+0.0f first, as the sibling's zero-filled accumulators: where a target has at
+ *                           most one foreign term the result has upp_chamfer_bwd's bits.)
+ *   upp_group_bwd_det       grad_xyz[b][r][c] = +0.0f, then + grad_out[b][g][k][c] for every (g,k) with idx[b][g][k] == r, in
+ *                           ascending g * K + k; grad_xyz needs NO zero-fill.  grad_center as upp_group_bwd (k ascending there too).
+ *   upp_gather_bwd_det      grad_feat[b][ch][r] = +0.0f, then + grad_out[b][ch][j] for every j with idx[b][j] == r, ascending j;
+ *                           grad_feat needs NO zero-fill.
+ *   upp_fps_gather_bwd_det  g_xyz[b][r][c] = +0.0f, then + g_centers[b][j][c] for every j with idx[b][j] == r, ascending j; indices
+ *                           outside [0, N) are skipped.
+ *   upp_emd_matchcost_det   p_t = the value upp_emd_matchcost adds for the t-th tile of 64 points of xyz1 (same arithmetic);
+ *                           cost[b] = ((+0.0f + p_0) + p_1) + ... in ascending t.  work: upp_emd_matchcost_det_work_bytes(B,n,m)
+ *                           bytes of scratch (the p_t; a host function, 0 for a negative argument). */
+int upp_chamfer_bwd_det(const float *xyz1, const float *xyz2, const int32_t *idx1, const int32_t *idx2,
+                        const float *grad_dist1, const float *grad_dist2, float *g1, float *g2,
+                        int B, int n, int m, void *stream);
+int upp_group_bwd_det(const float *grad_out, const int64_t *idx, float *grad_xyz, float *grad_center,
+                      int B, int N, int G, int K, void *stream);
+int upp_gather_bwd_det(const float *grad_out, const int32_t *idx, float *grad_feat,
+                       int B, int C, int N, int M, void *stream);
+int upp_fps_gather_bwd_det(const float *g_centers, const int32_t *idx, float *g_xyz, int B, int N, int M, void *stream);
+long long upp_emd_matchcost_det_work_bytes(int B, int n, int m);
+int upp_emd_matchcost_det(const float *xyz1, const float *xyz2, const float *match, float *cost, float *work,
+                          int B, int n, int m, void *stream);
 
 /* ---- patch embedding (mini-PointNet) forward --------------------------------------
  * Replaces Encoder.forward (reference models/Point_MAE_unify.py:191-222): the chain
