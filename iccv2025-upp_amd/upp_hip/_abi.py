@@ -45,6 +45,14 @@ SIGNATURES = {
     "upp_group_bwd_det": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_f]),
     "upp_gather_bwd_det": (_c_i, [_c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_f]),
     "upp_fps_gather_bwd_det": (_c_i, [_c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_f]),
+    "upp_ball_query": (_c_i, [_c_f, _c_f, ctypes.c_float, _c_i, _c_f, _c_i, _c_i, _c_i, _c_f]),
+    "upp_three_nn": (_c_i, [_c_f] * 4 + [_c_i] * 3 + [_c_f]),
+    "upp_three_interpolate_fwd": (_c_i, [_c_f] * 4 + [_c_i] * 4 + [_c_f]),
+    "upp_three_interpolate_bwd": (_c_i, [_c_f] * 4 + [_c_i] * 4 + [_c_f]),
+    "upp_three_interpolate_bwd_det": (_c_i, [_c_f] * 4 + [_c_i] * 4 + [_c_f]),
+    "upp_grouping_fwd": (_c_i, [_c_f] * 3 + [_c_i] * 5 + [_c_f]),
+    "upp_grouping_bwd": (_c_i, [_c_f] * 3 + [_c_i] * 5 + [_c_f]),
+    "upp_grouping_bwd_det": (_c_i, [_c_f] * 3 + [_c_i] * 5 + [_c_f]),
     "upp_emd_matchcost_det_work_bytes": (ctypes.c_longlong, [_c_i, _c_i, _c_i]),
     "upp_emd_matchcost_det": (_c_i, [_c_f] * 5 + [_c_i] * 3 + [_c_f]),
     "upp_patch_embed_work_floats": (ctypes.c_longlong, [_c_i, _c_i]),

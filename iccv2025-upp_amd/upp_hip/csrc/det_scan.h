@@ -1,5 +1,6 @@
 // det_scan.h -- the ordered "pull" behind the deterministic (`_det`) siblings of the scatter-add backward kernels
-// (upp_chamfer_bwd_det, upp_group_bwd_det, upp_gather_bwd_det, upp_fps_gather_bwd_det).
+// (upp_chamfer_bwd_det, upp_group_bwd_det, upp_gather_bwd_det, upp_fps_gather_bwd_det, upp_three_interpolate_bwd_det,
+// upp_grouping_bwd_det).
 //
 // A scatter-add by f32 atomics sums each target's contributions in whatever order the hardware retires them.  Here every TARGET is
 // one lane, and the lane walks the source list of its cloud in ASCENDING source index: a chunk of source keys (and the NV values

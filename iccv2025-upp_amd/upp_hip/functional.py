@@ -156,6 +156,64 @@ class EarthMoverDistanceFunction(Function):
         return ops.emd_matchcost_bwd(grad_cost.contiguous(), xyz1, xyz2, match)
 
 
+class BallQuery(Function):
+    """pointnet2_utils.ball_query: radius, nsample, xyz (B,N,3), new_xyz (B,P,3) -> (B,P,nsample) int32, non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, radius, nsample, xyz, new_xyz):
+        idx = ops.ball_query(radius, nsample, xyz, new_xyz)
+        ctx.mark_non_differentiable(idx)
+        return idx
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return None, None, None, None
+
+
+class ThreeNN(Function):
+    """pointnet2_utils.three_nn: unknown (B,n,3), known (B,m,3) -> (dist (B,n,3) f32 Euclidean, idx (B,n,3) int32), non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, unknown, known):
+        dist, idx = ops.three_nn(unknown, known)
+        ctx.mark_non_differentiable(dist, idx)
+        return dist, idx
+
+    @staticmethod
+    def backward(ctx, grad_dist, grad_idx):
+        return None, None
+
+
+class ThreeInterpolate(Function):
+    """pointnet2_utils.three_interpolate: features (B,C,m), idx (B,n,3) int32, weight (B,n,3) -> (B,C,n); grad w.r.t. features."""
+
+    @staticmethod
+    def forward(ctx, features, idx, weight):
+        ctx.save_for_backward(idx, weight)
+        ctx.m = features.shape[2]
+        return ops.three_interpolate_fwd(features, idx, weight)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        idx, weight = ctx.saved_tensors
+        return ops.three_interpolate_bwd(grad_out.contiguous(), idx, weight, ctx.m, deterministic=DETERMINISTIC), None, None
+
+
+class GroupingOperation(Function):
+    """pointnet2_utils.grouping_operation: features (B,C,N), idx (B,P,S) int32 -> (B,C,P,S); grad w.r.t. features."""
+
+    @staticmethod
+    def forward(ctx, features, idx):
+        ctx.save_for_backward(idx)
+        ctx.N = features.shape[2]
+        return ops.grouping_fwd(features, idx)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (idx,) = ctx.saved_tensors
+        return ops.grouping_bwd(grad_out.contiguous(), idx, ctx.N, deterministic=DETERMINISTIC), None
+
+
 furthest_point_sample = FurthestPointSampling.apply
 gather_operation = GatherOperation.apply
 
@@ -218,6 +276,77 @@ def knn_group(xyz, center, k):
 
 def group_points(xyz, center, idx):
     return _GroupPoints.apply(xyz, center, idx)
+
+
+# ------------------------------------------------------------------ the pointnet2_ops surface (README "The pointnet2_ops surface")
+def ball_query(radius, nsample, xyz, new_xyz):
+    """pointnet2_utils.ball_query -> (B,P,nsample) int32."""
+    if _torch_cpu(xyz, new_xyz):
+        from . import torch_cpu
+        return torch_cpu.ball_query(float(radius), int(nsample), xyz, new_xyz)
+    return BallQuery.apply(float(radius), int(nsample), xyz, new_xyz)
+
+
+def three_nn(unknown, known):
+    """pointnet2_utils.three_nn -> (dist (B,n,3) f32, idx (B,n,3) int32)."""
+    if _torch_cpu(unknown, known):
+        from . import torch_cpu
+        return torch_cpu.three_nn(unknown, known)
+    return ThreeNN.apply(unknown, known)
+
+
+def three_interpolate(features, idx, weight):
+    """pointnet2_utils.three_interpolate: features (B,C,m) -> (B,C,n)."""
+    if _torch_cpu(features, idx, weight):
+        from . import torch_cpu
+        return torch_cpu.three_interpolate(features, idx, weight)
+    return ThreeInterpolate.apply(features, idx, weight)
+
+
+def grouping_operation(features, idx):
+    """pointnet2_utils.grouping_operation: features (B,C,N), idx (B,P,S) int32 -> (B,C,P,S)."""
+    if _torch_cpu(features, idx):
+        from . import torch_cpu
+        return torch_cpu.grouping_operation(features, idx)
+    return GroupingOperation.apply(features, idx)
+
+
+class QueryAndGroup(torch.nn.Module):
+    """pointnet2_utils.QueryAndGroup: ball query around new_xyz, then the grouped coordinates (centre subtracted) and / or features.
+    forward(xyz (B,N,3), new_xyz (B,P,3), features (B,C,N) | None) -> (B, 3+C, P, S) | (B, C, P, S) with use_xyz=False | (B, 3, P, S)
+    without features."""
+
+    def __init__(self, radius, nsample, use_xyz=True):
+        super().__init__()
+        self.radius, self.nsample, self.use_xyz = radius, nsample, use_xyz
+
+    def forward(self, xyz, new_xyz, features=None):
+        idx = ball_query(self.radius, self.nsample, xyz, new_xyz)
+        grouped_xyz = None
+        if self.use_xyz or features is None:
+            grouped_xyz = grouping_operation(xyz.transpose(1, 2).contiguous(), idx) - new_xyz.transpose(1, 2).unsqueeze(-1)
+        if features is None:
+            if not self.use_xyz:
+                raise ValueError("QueryAndGroup: no features and use_xyz=False leave nothing to group")
+            return grouped_xyz
+        grouped = grouping_operation(features, idx)
+        return torch.cat([grouped_xyz, grouped], dim=1) if self.use_xyz else grouped
+
+
+class GroupAll(torch.nn.Module):
+    """pointnet2_utils.GroupAll: the whole cloud as one group.  forward(xyz (B,N,3), new_xyz (ignored), features (B,C,N) | None)
+    -> (B, 3+C, 1, N) | (B, C, 1, N) with use_xyz=False | (B, 3, 1, N) without features."""
+
+    def __init__(self, use_xyz=True):
+        super().__init__()
+        self.use_xyz = use_xyz
+
+    def forward(self, xyz, new_xyz, features=None):
+        grouped_xyz = xyz.transpose(1, 2).unsqueeze(2)
+        if features is None:
+            return grouped_xyz
+        grouped = features.unsqueeze(2)
+        return torch.cat([grouped_xyz, grouped], dim=1) if self.use_xyz else grouped
 
 
 # ------------------------------------------------------------------ Transformer block glue
@@ -1669,7 +1798,7 @@ ADAPTER_FACTORS = True        # ... which inside a deferred scope writes per-row
 
 # Reproducible training (README "Reproducible training"): with DETERMINISTIC on, the autograd nodes whose backward (or forward: the EMD
 # cost) sums with f32 atomics -- GatherOperation, _FpsGather, _KnnGroup, _GroupPoints, ChamferFunction, _ChamferLoss,
-# EarthMoverDistanceFunction -- call the library's `_det` siblings (a defined summation order: include/upp_hip.h "deterministic
+# EarthMoverDistanceFunction, ThreeInterpolate, GroupingOperation -- call the library's `_det` siblings (a defined summation order: include/upp_hip.h "deterministic
 # scatter-adds").  Read at CALL time, also by the backward thread; a captured step keeps the choice it was captured under, whatever the
 # attribute says at replay.  UPP_DETERMINISTIC=1 sets it once, at import.
 DETERMINISTIC = os.environ.get("UPP_DETERMINISTIC", "").strip() not in ("", "0")

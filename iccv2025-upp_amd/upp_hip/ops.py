@@ -292,6 +292,116 @@ def fps_gather_bwd(grad_centers, idx, N, deterministic=False):
     return gx
 
 
+# ------------------------------------------------------------------ the pointnet2_ops surface (include/upp_hip.h)
+def ball_query(radius, nsample, xyz, new_xyz):
+    """xyz (B,N,3), new_xyz (B,P,3) -> idx (B,P,nsample) int32: the first nsample points (ascending index) strictly inside `radius` of each
+    query, the first hit filling every slot first, zeros for a query without a hit (upp_ball_query).  Every element is written by the kernel."""
+    _need(xyz, "xyz", torch.float32, 3, 3)
+    _need(new_xyz, "new_xyz", torch.float32, 3, 3)
+    _same_device(xyz, new_xyz)
+    B, N, _ = xyz.shape
+    P = new_xyz.shape[1]
+    if new_xyz.shape[0] != B:
+        raise RuntimeError("xyz and new_xyz batch sizes differ")
+    radius, nsample = float(radius), int(nsample)
+    if not (radius > 0.0 and radius != float("inf")) or nsample < 1:
+        raise ValueError("ball_query: radius must be finite and positive, nsample positive")
+    idx = torch.empty((B, P, nsample), dtype=torch.int32, device=xyz.device)
+    if B:
+        _call(xyz.device, "upp_ball_query", _abi.ptr(xyz), _abi.ptr(new_xyz), radius, nsample, _abi.ptr(idx), B, N, P)
+    return idx
+
+
+def three_nn(unknown, known):
+    """unknown (B,n,3), known (B,m,3) -> dist (B,n,3) f32 Euclidean distances ascending, idx (B,n,3) int32 (ties: lower index first; with
+    m < 3 the unfilled slots are index 0 / +inf): upp_three_nn."""
+    _need(unknown, "unknown", torch.float32, 3, 3)
+    _need(known, "known", torch.float32, 3, 3)
+    _same_device(unknown, known)
+    B, n, _ = unknown.shape
+    m = known.shape[1]
+    if known.shape[0] != B:
+        raise RuntimeError("unknown and known batch sizes differ")
+    dist = torch.empty((B, n, 3), dtype=torch.float32, device=unknown.device)
+    idx = torch.empty((B, n, 3), dtype=torch.int32, device=unknown.device)
+    if B:
+        _call(unknown.device, "upp_three_nn", _abi.ptr(unknown), _abi.ptr(known), _abi.ptr(dist), _abi.ptr(idx), B, n, m)
+    return dist, idx
+
+
+def _interp_args(dense, idx, weight):
+    _need(dense, "features", torch.float32, 3)
+    _need(idx, "idx", torch.int32, 3, 3)
+    _need(weight, "weight", torch.float32, 3, 3)
+    _same_device(dense, idx, weight)
+    if idx.shape != weight.shape or idx.shape[0] != dense.shape[0]:
+        raise RuntimeError("three_interpolate: idx and weight must both be (B, n, 3) for features (B, C, m)")
+
+
+def three_interpolate_fwd(features, idx, weight):
+    """features (B,C,m), idx (B,n,3) int32, weight (B,n,3) -> (B,C,n) = (w0 f[i0] + w1 f[i1]) + w2 f[i2], every operation rounded once."""
+    _interp_args(features, idx, weight)
+    B, C, m = features.shape
+    n = idx.shape[1]
+    out = torch.empty((B, C, n), dtype=torch.float32, device=features.device)
+    if B:
+        _call(features.device, "upp_three_interpolate_fwd", _abi.ptr(features), _abi.ptr(idx), _abi.ptr(weight), _abi.ptr(out), B, C, m, n)
+    return out
+
+
+def three_interpolate_bwd(grad_out, idx, weight, m, deterministic=False):
+    """grad_out (B,C,n) -> grad_features (B,C,m).  deterministic: the sums in ascending i * 3 + j (upp_three_interpolate_bwd_det,
+    include/upp_hip.h) instead of f32 atomics."""
+    _interp_args(grad_out, idx, weight)
+    B, C, n = grad_out.shape
+    if idx.shape[1] != n:
+        raise RuntimeError("three_interpolate_bwd: grad_out must be (B, C, n) for idx (B, n, 3)")
+    m = int(m)
+    if deterministic:
+        grad = torch.empty((B, C, m), dtype=torch.float32, device=grad_out.device)       # (overwritten in full)
+    else:
+        grad = torch.zeros((B, C, m), dtype=torch.float32, device=grad_out.device)
+    if B:
+        _call(grad_out.device, "upp_three_interpolate_bwd_det" if deterministic else "upp_three_interpolate_bwd",
+              _abi.ptr(grad_out), _abi.ptr(idx), _abi.ptr(weight), _abi.ptr(grad), B, C, m, n)
+    return grad
+
+
+def grouping_fwd(features, idx):
+    """features (B,C,N), idx (B,P,S) int32 -> (B,C,P,S) = features[b, c, idx[b, p, s]] (upp_grouping_fwd)."""
+    _need(features, "features", torch.float32, 3)
+    _need(idx, "idx", torch.int32, 3)
+    _same_device(features, idx)
+    B, C, N = features.shape
+    _, P, S = idx.shape
+    if idx.shape[0] != B:
+        raise RuntimeError("features and idx batch sizes differ")
+    out = torch.empty((B, C, P, S), dtype=torch.float32, device=features.device)
+    if B:
+        _call(features.device, "upp_grouping_fwd", _abi.ptr(features), _abi.ptr(idx), _abi.ptr(out), B, C, N, P, S)
+    return out
+
+
+def grouping_bwd(grad_out, idx, N, deterministic=False):
+    """grad_out (B,C,P,S) -> grad_features (B,C,N).  deterministic: the sums in ascending p * S + s (upp_grouping_bwd_det,
+    include/upp_hip.h) instead of f32 atomics."""
+    _need(grad_out, "grad_out", torch.float32, 4)
+    _need(idx, "idx", torch.int32, 3)
+    _same_device(grad_out, idx)
+    B, C, P, S = grad_out.shape
+    if tuple(idx.shape) != (B, P, S):
+        raise RuntimeError("grouping_bwd: grad_out must be (B, C, P, S) for idx (B, P, S)")
+    N = int(N)
+    if deterministic:
+        grad = torch.empty((B, C, N), dtype=torch.float32, device=grad_out.device)       # (overwritten in full)
+    else:
+        grad = torch.zeros((B, C, N), dtype=torch.float32, device=grad_out.device)
+    if B:
+        _call(grad_out.device, "upp_grouping_bwd_det" if deterministic else "upp_grouping_bwd",
+              _abi.ptr(grad_out), _abi.ptr(idx), _abi.ptr(grad), B, C, N, P, S)
+    return grad
+
+
 # ------------------------------------------------------------------ Chamfer
 def chamfer_fwd(xyz1, xyz2):
     _need(xyz1, "xyz1", torch.float32, 3, 3)

@@ -2,9 +2,9 @@
 torch-CPU: utils.misc.fps + torch.cdist kNN fallback -- plumbing, no GPU").  OFF by default: the product's operators have no CPU
 path (`upp_hip.ops` raises on CPU tensors) and a HIP tensor never comes here.  `enable()` -- or UPP_TORCH_CPU=1 in the environment --
 lets the grouping entry points of upp_hip.functional (fps_gather, knn_query, knn_group, ChamferFunction, and the packed-batch pair
-fps_gather_ragged / cloud_norm_ragged) serve CPU tensors with the
-torch formulations below, so that a reference user can run the model's forward on a GPU-less host to check plumbing (state-dict
-loading, shapes, config wiring).  Nothing here touches oracle/ (test infrastructure) and nothing here is timed by bench.py.
+fps_gather_ragged / cloud_norm_ragged, and the four pointnet2_ops operators ball_query, three_nn, three_interpolate,
+grouping_operation) serve CPU tensors with the torch formulations below, so that a reference user can run the model's forward on a
+GPU-less host to check plumbing (state-dict loading, shapes, config wiring).  Nothing here touches oracle/ (test infrastructure) and nothing here is timed by bench.py.
 
 Semantics follow the reference's own CPU-side formulations: FPS as datasets/ModelNetDataset.py:29-49 (start at index 0, arg-max of the
 running minimum distance) with pointnet2_ops' rule that points with |p|^2 <= 1e-3 are never candidates; kNN as models/modules.py
@@ -86,6 +86,52 @@ def knn_group(xyz, center, k):
     B, G, _ = idx.shape
     nb = torch.gather(xyz.unsqueeze(1).expand(-1, G, -1, -1), 2, idx.unsqueeze(-1).expand(-1, -1, -1, 3))
     return nb - center.unsqueeze(2), idx
+
+
+def ball_query(radius, nsample, xyz, new_xyz):
+    """pointnet2_utils.ball_query: xyz (B,N,3), new_xyz (B,P,3) -> (B,P,nsample) int32: the first nsample points (ascending index) with
+    squared distance < radius * radius (an f32 product, strict), the first hit in every unfilled slot, zeros without a hit."""
+    x, q = xyz.detach(), new_xyz.detach()
+    N = x.shape[1]
+    r = torch.tensor(radius, dtype=x.dtype)
+    d2 = ((q.unsqueeze(2) - x.unsqueeze(1)) ** 2).sum(-1)
+    key = torch.where(d2 < r * r, torch.arange(N), torch.tensor(N))                 # hits keep their index, misses sort last
+    if nsample > N:
+        key = torch.cat([key, key.new_full(key.shape[:2] + (nsample - N,), N)], -1)
+    key = key.sort(-1)[0][:, :, :nsample]
+    first = key[:, :, :1]
+    key = torch.where(key == N, first, key)
+    return torch.where(key == N, torch.zeros_like(key), key).to(torch.int32)
+
+
+def three_nn(unknown, known):
+    """pointnet2_utils.three_nn: unknown (B,n,3), known (B,m,3) -> (dist (B,n,3) Euclidean ascending, idx (B,n,3) int32; ties: lower index
+    first; with m < 3 the missing neighbours are index 0 at distance +inf)."""
+    u, k = unknown.detach(), known.detach()
+    m = k.shape[1]
+    d2 = ((u.unsqueeze(2) - k.unsqueeze(1)) ** 2).sum(-1)
+    if m < 3:
+        d2 = torch.cat([d2, d2.new_full(d2.shape[:2] + (3 - m,), float("inf"))], -1)
+    order = torch.argsort(d2, dim=-1, stable=True)[:, :, :3]
+    dist = torch.gather(d2, -1, order).sqrt()
+    return dist, torch.where(order < m, order, torch.zeros_like(order)).to(torch.int32)
+
+
+def three_interpolate(features, idx, weight):
+    """pointnet2_utils.three_interpolate: features (B,C,m), idx (B,n,3), weight (B,n,3) -> (B,C,n) = (w0 f[i0] + w1 f[i1]) + w2 f[i2];
+    differentiable w.r.t. features."""
+    B, C, _ = features.shape
+    n = idx.shape[1]
+    f = torch.gather(features, 2, idx.long().reshape(B, 1, n * 3).expand(-1, C, -1)).reshape(B, C, n, 3)
+    t = f * weight.detach().unsqueeze(1)
+    return (t[..., 0] + t[..., 1]) + t[..., 2]
+
+
+def grouping_operation(features, idx):
+    """pointnet2_utils.grouping_operation: features (B,C,N), idx (B,P,S) -> (B,C,P,S); differentiable w.r.t. features."""
+    B, C, _ = features.shape
+    _, P, S = idx.shape
+    return torch.gather(features, 2, idx.long().reshape(B, 1, P * S).expand(-1, C, -1)).reshape(B, C, P, S)
 
 
 def chamfer(xyz1, xyz2):

@@ -168,6 +168,48 @@ int upp_group_bwd(const float *grad_out, const int64_t *idx, float *grad_xyz, fl
  * conversion and scatter in ONE launch, one workgroup per cloud. */
 int upp_fps_gather_bwd(const float *g_centers, const int32_t *idx, float *g_xyz, int B, int N, int M, void *stream);
 
+/* ---- the pointnet2_ops surface: ball_query, three_nn, three_interpolate, grouping_operation -------------
+ * The rest of pointnet2_ops.pointnet2_utils (pointnet2_ops 3.0.0 ball_query_gpu.cu, interpolate_gpu.cu, group_points_gpu.cu; the
+ * reference calls three_nn / three_interpolate from models/Transformer_utils.py:225-230).  The upstream CUDA sources were not at hand
+ * when this was written: the rules below are RESTATED from them, as was done for FPS and kNN, and stay unpinned until they can be
+ * compared with the CUDA kernels' output (tests/_pointnet2_reference.py is the same restatement in numpy).  Shapes, dtypes and tie
+ * rules are upstream's; indices are int32.  Squared distances are the library's convention: with the f32 differences (x, y, z),
+ * d2 = fma(z, z, fma(x, x, y * y)) (csrc/common.h sumsq3 = oracle/upp_oracle.c sumsq3).
+ *
+ * upp_ball_query: xyz (B,N,3), new_xyz (B,P,3) -> idx (B,P,nsample) int32.  For query j walk k = 0 ... N-1 in ascending order; k
+ *   qualifies when d2 < radius * radius (the product formed in f32, the compare strict).  The FIRST qualifying k is written into all
+ *   nsample slots; every qualifying k (the first included) goes into slot cnt++; the walk stops at cnt == nsample.  A query with no
+ *   qualifying point yields zeros.  Every element of idx is written by the kernel: nothing to zero-fill.
+ *   UPP_E_BADARG also for a radius that is not finite or <= 0 and for nsample < 1.
+ * upp_three_nn: unknown (B,n,3), known (B,m,3) -> dist (B,n,3) f32, idx (B,n,3) int32: the three smallest d2 over ascending k by the
+ *   strict-'<' cascade (d < best1, else d < best2, else d < best3), so equal distances keep the lower index first.  Indices start at
+ *   0 and bests at +inf (f32 compares against +inf select what upstream's double 1e40 selects): with m < 3 the unfilled slots report
+ *   index 0 and distance +inf.  dist is the SQUARE ROOT (one IEEE sqrt) of d2, as the upstream Python wrapper returns it.
+ * upp_three_interpolate_fwd: features (B,C,m), idx (B,n,3) int32, weight (B,n,3) -> out (B,C,n):
+ *   out[b][c][i] = (w0 * f[i0] + w1 * f[i1]) + w2 * f[i2] -- three products and two sums in exactly this order, each one f32 operation
+ *   rounded to nearest, none contracted into an fma.  An index outside [0, m) reads 0.0f (and is skipped by the backward).
+ * upp_three_interpolate_bwd: grad_out (B,C,n) -> grad_features (B,C,m), which must be zero-filled by the caller:
+ *   grad_features[b][c][idx[b][i][j]] += grad_out[b][c][i] * weight[b][i][j] by f32 atomics, order unspecified (as upp_gather_bwd).
+ * upp_grouping_fwd: features (B,C,N), idx (B,P,S) int32 in [0,N) -> out (B,C,P,S) = features[b][c][idx[b][p][s]].
+ * upp_grouping_bwd: grad_out (B,C,P,S) scatter-added into the caller-zeroed grad_features (B,C,N), f32 atomics.
+ *   (grouping_operation is gather_operation on the flattened (P S) index list: the same kernels serve both.)
+ * The same two sums in a defined order: upp_three_interpolate_bwd_det / upp_grouping_bwd_det ("deterministic scatter-adds" below).
+ * Every size must be positive (UPP_E_BADARG); B == 0 is a no-op.  Limits: B <= 65535 for upp_ball_query / upp_three_nn (UPP_E_RANGE
+ * beyond: one grid row per cloud, as kNN / Chamfer / EMD); the other entry points loop their grid and have no batch limit;
+ * P * S < 2^31. */
+int upp_ball_query(const float *xyz, const float *new_xyz, float radius, int nsample, int32_t *idx,
+                   int B, int N, int P, void *stream);
+int upp_three_nn(const float *unknown, const float *known, float *dist, int32_t *idx,
+                 int B, int n, int m, void *stream);
+int upp_three_interpolate_fwd(const float *features, const int32_t *idx, const float *weight, float *out,
+                              int B, int C, int m, int n, void *stream);
+int upp_three_interpolate_bwd(const float *grad_out, const int32_t *idx, const float *weight, float *grad_features,
+                              int B, int C, int m, int n, void *stream);
+int upp_grouping_fwd(const float *features, const int32_t *idx, float *out,
+                     int B, int C, int N, int P, int S, void *stream);
+int upp_grouping_bwd(const float *grad_out, const int32_t *idx, float *grad_features,
+                     int B, int C, int N, int P, int S, void *stream);
+
 /* ---- Chamfer distance ----------------------------------------------------------
  * Replaces chamfer.forward / chamfer.backward (reference
  * extensions/chamfer_dist/chamfer_cuda.cpp:36-39, kernels chamfer.cu:15-145 and
@@ -213,7 +255,7 @@ int upp_emd_matchcost_bwd(const float *grad_cost, const float *xyz1, const float
                           float *grad1, float *grad2, int B, int n, int m, void *stream);
 
 /* ---- deterministic scatter-adds ---------------------------------------------------
- * Per-call siblings of the five entry points whose f32 sums the hardware orders (atomics): the arguments, shapes, limits and error
+ * Per-call siblings of the seven entry points whose f32 sums the hardware orders (atomics): the arguments, shapes, limits and error
  * codes of the sibling (upp_emd_matchcost_det takes a scratch pointer besides), the same terms, a DEFINED summation order -- each
  * can be restated on the CPU and compared bit for bit (tests/_det_reference.py), and two runs give the same bits.  Every product
  * and sum below is one f32 operation rounded to nearest, none contracted into an fma.  Every output is overwritten in full on
@@ -233,7 +275,12 @@ int upp_emd_matchcost_bwd(const float *grad_cost, const float *xyz1, const float
  *                           outside [0, N) are skipped.
  *   upp_emd_matchcost_det   p_t = the value upp_emd_matchcost adds for the t-th tile of 64 points of xyz1 (same arithmetic);
  *                           cost[b] = ((+0.0f + p_0) + p_1) + ... in ascending t.  work: upp_emd_matchcost_det_work_bytes(B,n,m)
- *                           bytes of scratch (the p_t; a host function, 0 for a negative argument). */
+ *                           bytes of scratch (the p_t; a host function, 0 for a negative argument).
+ *   upp_three_interpolate_bwd_det  grad_features[b][ch][r] = +0.0f, then + (grad_out[b][ch][i] * weight[b][i][j]) for every (i, j)
+ *                           with idx[b][i][j] == r, in ascending i * 3 + j (the product rounded first, then the sum); indices outside
+ *                           [0, m) are skipped; grad_features needs NO zero-fill.
+ *   upp_grouping_bwd_det    grad_features[b][ch][r] = +0.0f, then + grad_out[b][ch][p][s] for every (p, s) with idx[b][p][s] == r,
+ *                           in ascending p * S + s; grad_features needs NO zero-fill (upp_gather_bwd_det on the flattened list). */
 int upp_chamfer_bwd_det(const float *xyz1, const float *xyz2, const int32_t *idx1, const int32_t *idx2,
                         const float *grad_dist1, const float *grad_dist2, float *g1, float *g2,
                         int B, int n, int m, void *stream);
@@ -242,6 +289,10 @@ int upp_group_bwd_det(const float *grad_out, const int64_t *idx, float *grad_xyz
 int upp_gather_bwd_det(const float *grad_out, const int32_t *idx, float *grad_feat,
                        int B, int C, int N, int M, void *stream);
 int upp_fps_gather_bwd_det(const float *g_centers, const int32_t *idx, float *g_xyz, int B, int N, int M, void *stream);
+int upp_three_interpolate_bwd_det(const float *grad_out, const int32_t *idx, const float *weight, float *grad_features,
+                                  int B, int C, int m, int n, void *stream);
+int upp_grouping_bwd_det(const float *grad_out, const int32_t *idx, float *grad_features,
+                         int B, int C, int N, int P, int S, void *stream);
 long long upp_emd_matchcost_det_work_bytes(int B, int n, int m);
 int upp_emd_matchcost_det(const float *xyz1, const float *xyz2, const float *match, float *cost, float *work,
                           int B, int n, int m, void *stream);
