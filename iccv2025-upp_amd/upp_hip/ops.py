@@ -1778,7 +1778,11 @@ def copy_batched(dsts, srcs):
     for d, s_ in zip(dsts, srcs):
         if not (d.is_cuda and s_.is_cuda and d.dtype == s_.dtype and d.shape == s_.shape and d.is_contiguous() and s_.is_contiguous()):
             raise RuntimeError("copy_batched: contiguous HIP (cuda) tensors of equal shape and dtype are required")
-    S = (ctypes.c_void_p * k)(*[t.data_ptr() for t in srcs])
+    pairs = [(d, s_) for d, s_ in zip(dsts, srcs) if d.numel() > 0]        # an empty tensor's data_ptr() is NULL, which the library refuses
+    if not pairs:
+        return
+    dsts, srcs, k = [d for d, _ in pairs], [s_ for _, s_ in pairs], len(pairs)
+    S =(ctypes.c_void_p * k)(*[t.data_ptr() for t in srcs])
     D = (ctypes.c_void_p * k)(*[t.data_ptr() for t in dsts])
     n = (ctypes.c_longlong * k)(*[t.numel() * t.element_size() for t in dsts])
     _call(dsts[0].device, "upp_copy_batched", S, D, n, k)
