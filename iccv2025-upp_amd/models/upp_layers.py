@@ -211,6 +211,8 @@ def build_prop_index(c1, c2, i1, i2, gather_idx, B, Lp, off):
         if G2 <= 64 and i1.dtype == torch.int64 and i2.dtype == torch.int64 and POOL_TRACE is None:
             lists = HF.ops.prop_index(c1.contiguous(), c2.contiguous(), i1.contiguous(), i2.contiguous(), gather_idx, Lp, off, 1e-3)
         else:
+            if c1.is_cuda and POOL_TRACE is None:
+                HF.note_declined("prompt propagation index", "more than 64 level-2 centres / indices not int64")
             lists = _prop_lists_torch(c1, c2, i1, i2, gather_idx, B, Lp, off)
         return HF.PropIndex(*lists, rows=B * Lp)
 
@@ -629,8 +631,8 @@ class Attention(nn.Module):
         self.proj_drop = nn.Dropout(proj_drop)
 
     def fusable(self, x):
-        """The gfx950 attention kernel serves head_dim 64, L <= 144 and no attention dropout (all UPP configs)."""
-        return (x.is_cuda and x.dtype == torch.float32 and x.shape[-1] // self.num_heads == 64 and x.shape[1] <= 144
+        """The gfx950 attention kernels serve head_dim 64, L <= HF.ATTN_MAX_L and no attention dropout (all UPP configs)."""
+        return (x.is_cuda and x.dtype == torch.float32 and x.shape[-1] // self.num_heads == 64 and x.shape[1] <= HF.ATTN_MAX_L
                 and not (self.training and self.attn_drop.p > 0))
 
     def forward(self, x):
@@ -781,7 +783,7 @@ class Block(nn.Module):
     def fusable(self, x):
         return (x.is_cuda and x.dtype == torch.float32 and x.shape[-1] <= 512 and self.attn.fusable(x)
                 and isinstance(self.norm1, nn.LayerNorm) and self.mlp.drop.p == 0 and self.attn.proj_drop.p == 0
-                and x.shape[1] + 16 <= 144)
+                and x.shape[1] + 16 <= HF.ATTN_MAX_L)
 
     def forward_fused(self, x, pos, **kw):
         """Same function as forward(x + pos, **kw); the element-wise glue runs in the row kernels of

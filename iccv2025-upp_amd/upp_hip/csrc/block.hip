@@ -385,28 +385,33 @@ extern "C" int upp_ln_param_grad(const float *g_h, const float *xo, const float 
 }
 
 // attention core, head dim 64: qkv (B, L, 3, H, 64); ctx (B, L, H*64); lse (B, H, L).  L <= 96: attn_flash16.hip (operands in registers);
-// L <= 160: attn_long.hip.  (Rounds 1-3 also shipped a VALU pair and the LDS-staged 32x32x2 pair of attn_mfma.hip behind a `variant`
+// L <= 160: attn_long.hip; L <= UPP_ATTN_MAX_L: attn_stream.hip (K / V streamed through the LDS, online softmax).  (Rounds 1-3 also shipped a VALU pair and the LDS-staged 32x32x2 pair of attn_mfma.hip behind a `variant`
 // argument, for measurements: removed from the library in round 4 -- tools/micro/attn_mfma.hip keeps the latter reproducible.)
 int upp_attn_fwd_long(const float *qkv, float *ctx, float *lse, int B, int L, int H, float scale, hipStream_t st);
 int upp_attn_bwd_long(const float *qkv, const float *ctx, const float *d_ctx, const float *lse, float *d_qkv, int B, int L, int H,
                       float scale, hipStream_t st);
+int upp_attn_fwd_stream(const float *qkv, float *ctx, float *lse, int B, int L, int H, float scale, hipStream_t st);
+int upp_attn_bwd_stream(const float *qkv, const float *ctx, const float *d_ctx, const float *lse, float *d_qkv, int B, int L, int H,
+                        float scale, hipStream_t st);
 int upp_attn_fwd_flash16(const float *qkv, float *ctx, float *lse, int B, int L, int H, float scale, hipStream_t st);
 int upp_attn_bwd_flash16(const float *qkv, const float *ctx, const float *d_ctx, const float *lse, float *d_qkv, int B, int L, int H,
                          float scale, hipStream_t st);
 extern "C" int upp_attn_fwd(const float *qkv, float *ctx, float *lse, int B, int L, int H, int head_dim, float scale, void *stream) {
     if (!qkv || !ctx || !lse || B < 0 || L < 1 || H < 1) return UPP_E_BADARG;
-    if (head_dim != 64 || L > 160) return UPP_E_RANGE;
+    if (head_dim != 64 || L > UPP_ATTN_MAX_L) return UPP_E_RANGE;
     if (B == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
+    if (L > 160) return upp_attn_fwd_stream(qkv, ctx, lse, B, L, H, scale, st);
     return L <= 96 ? upp_attn_fwd_flash16(qkv, ctx, lse, B, L, H, scale, st) : upp_attn_fwd_long(qkv, ctx, lse, B, L, H, scale, st);
 }
 
 extern "C" int upp_attn_bwd(const float *qkv, const float *ctx, const float *d_ctx, const float *lse, float *d_qkv, int B, int L,
                             int H, int head_dim, float scale, void *stream) {
     if (!qkv || !ctx || !d_ctx || !lse || !d_qkv || B < 0 || L < 1 || H < 1) return UPP_E_BADARG;
-    if (head_dim != 64 || L > 160) return UPP_E_RANGE;
+    if (head_dim != 64 || L > UPP_ATTN_MAX_L) return UPP_E_RANGE;
     if (B == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
+    if (L > 160) return upp_attn_bwd_stream(qkv, ctx, d_ctx, lse, d_qkv, B, L, H, scale, st);
     return L <= 96 ? upp_attn_bwd_flash16(qkv, ctx, d_ctx, lse, d_qkv, B, L, H, scale, st) : upp_attn_bwd_long(qkv, ctx, d_ctx, lse, d_qkv, B, L, H, scale, st);
 }
 

@@ -464,8 +464,14 @@ class _Attention(Function):
         return ops.attn_bwd(qkv, out, g.contiguous(), lse, B, L, H, scale), None, None
 
 
+ATTN_MAX_L = ops.ATTN_MAX_L
+
+
 def attention(qkv, num_heads, scale):
-    """softmax(q k^T scale) v per head on the FP32-MFMA attention kernels (L <= 96: attn_flash16.hip, L <= 160: attn_long.hip)."""
+    """softmax(q k^T scale) v per head on the FP32-MFMA attention kernels, head_dim 64, three families by sequence length:
+    L <= 96 attn_flash16.hip (operands in registers), L <= 160 attn_long.hip (K and V resident in the LDS), L <= ATTN_MAX_L
+    attn_stream.hip (64-row query blocks, K / V streamed in 64-key blocks, online softmax; the backward runs one kernel per key
+    block for dK / dV and one per query block for dQ).  Deterministic at every L; longer sequences raise."""
     return _Attention.apply(qkv, int(num_heads), float(scale))
 
 

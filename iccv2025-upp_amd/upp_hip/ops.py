@@ -1144,7 +1144,14 @@ def ln_param_grad(g_h, xo, mean, rstd, chunks=32):
     return part          # (2, chunks, D): [0] d_gamma partials, [1] d_beta partials; the caller sums over the chunks
 
 
+# The longest sequence upp_attn_fwd / upp_attn_bwd serve (UPP_ATTN_MAX_L of include/upp_hip.h; tests/test_attention_stream_host.py holds the
+# two together).  The models' `fusable` predicates read it, so a longer sequence takes the torch formulation instead of raising.
+ATTN_MAX_L = 2048
+
+
 def attn_fwd(qkv, B, L, H, scale):
+    """qkv (B, L, 3, H, 64) -> ctx (B, L, H * 64), lse (B, H, L).  L <= 96: attn_flash16.hip, L <= 160: attn_long.hip,
+    L <= ATTN_MAX_L: attn_stream.hip (K / V streamed through the LDS, online softmax); longer sequences raise."""
     _need(qkv, "qkv", torch.float32)
     hd = qkv.numel() // (B * L * 3 * H)
     ctx = torch.empty((B, L, H * hd), dtype=torch.float32, device=qkv.device)
@@ -1154,6 +1161,8 @@ def attn_fwd(qkv, B, L, H, scale):
 
 
 def attn_bwd(qkv, ctx, d_ctx, lse, B, L, H, scale):
+    """d_qkv (B, L, 3, H, 64) from d_ctx and the forward's ctx / lse; the same three kernel families and the same range as attn_fwd.
+    No atomics at any L: two calls on the same inputs give the same bits."""
     hd = qkv.numel() // (B * L * 3 * H)
     d_qkv = torch.empty_like(qkv)
     _call(qkv.device, "upp_attn_bwd", _abi.ptr(qkv), _abi.ptr(ctx), _abi.ptr(d_ctx), _abi.ptr(lse), _abi.ptr(d_qkv), B, L, H, hd, float(scale))

@@ -372,11 +372,14 @@ int upp_ln_param_grad(const float *g_h, const float *xo, const float *mean, cons
  *   ctx (B,L,H*64): softmax(q k^T * scale) v, already in the layout of (:193) `.transpose(1,2).reshape(B,N,C)`
  *   lse (B,H,L): log-sum-exp of the scaled scores (saved for backward)
  *   d_qkv (B,L,3,H,64) from d_ctx (B,L,H*64)
- * Limits: head_dim == 64; L <= 192 forward, L <= 160 backward (FP32 MFMA kernels for L <= 96 and L <= 160). */
+ * Limits: head_dim == 64; 1 <= L <= UPP_ATTN_MAX_L, forward and backward alike; UPP_E_RANGE beyond (checked before the B == 0 return).
+ * No atomics, no workspace, no memset at any L: two calls on the same inputs give the same bits. */
+#define UPP_ATTN_MAX_L 2048   /* the longest sequence the attention entry points serve (the longest one the test suite covers) */
 int upp_attn_fwd(const float *qkv, float *ctx, float *lse, int B, int L, int H, int head_dim, float scale, void *stream);
 int upp_attn_bwd(const float *qkv, const float *ctx, const float *d_ctx, const float *lse, float *d_qkv,
                  int B, int L, int H, int head_dim, float scale, void *stream);
-/* (L <= 96: the register-resident 16x16x4 MFMA kernels of attn_flash16.hip; L <= 160: attn_long.hip; UPP_E_RANGE beyond) */
+/* (L <= 96: the register-resident 16x16x4 MFMA kernels of attn_flash16.hip; L <= 160: attn_long.hip, K and V resident in the LDS;
+ *  L <= UPP_ATTN_MAX_L: attn_stream.hip, 64-row query blocks against K / V streamed in 64-key blocks, online softmax) */
 /* ---- prompt propagation (Block.forward, reference models/Point_MAE_pretask_dev.py:275-303) ----
  * X (rows, D): the block's token matrix viewed as rows = B*L' rows [cls | prompts | T centre tokens] per sample.
  * Index arguments are ABSOLUTE row numbers of X (the host converts the reference's flat / per-sample index
