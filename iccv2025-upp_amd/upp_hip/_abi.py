@@ -53,6 +53,11 @@ SIGNATURES = {
     "upp_grouping_fwd": (_c_i, [_c_f] * 3 + [_c_i] * 5 + [_c_f]),
     "upp_grouping_bwd": (_c_i, [_c_f] * 3 + [_c_i] * 5 + [_c_f]),
     "upp_grouping_bwd_det": (_c_i, [_c_f] * 3 + [_c_i] * 5 + [_c_f]),
+    "upp_knn_points": (_c_i, [_c_f] * 7 + [_c_i] * 6 + [_c_f]),
+    "upp_knn_points_bwd": (_c_i, [_c_f] * 8 + [_c_i] * 6 + [_c_f]),
+    "upp_knn_gather": (_c_i, [_c_f] * 4 + [_c_i] * 5 + [_c_f]),
+    "upp_knn_scatter_add": (_c_i, [_c_f] * 5 + [_c_i] * 6 + [_c_f]),
+    "upp_knn_scatter_add_det": (_c_i, [_c_f] * 5 + [_c_i] * 6 + [_c_f]),
     "upp_emd_matchcost_det_work_bytes": (ctypes.c_longlong, [_c_i, _c_i, _c_i]),
     "upp_emd_matchcost_det": (_c_i, [_c_f] * 5 + [_c_i] * 3 + [_c_f]),
     "upp_patch_embed_work_floats": (ctypes.c_longlong, [_c_i, _c_i]),

@@ -214,6 +214,50 @@ class GroupingOperation(Function):
         return ops.grouping_bwd(grad_out.contiguous(), idx, ctx.N, deterministic=DETERMINISTIC), None
 
 
+class KnnPoints(Function):
+    """pytorch3d.ops.knn_points as one node: p1 (N,P1,D), p2 (N,P2,D), lengths1, lengths2 (device int64 | None), K, norm, return_nn
+    -> dists (N,P1,K), idx (N,P1,K) int64 (non-differentiable), nn (N,P1,K,D) | None.  dists is differentiable w.r.t. p1 and p2, nn
+    (= knn_gather(p2, idx, lengths2) on the real rows) w.r.t. p2; the neighbour selection is not differentiated."""
+
+    @staticmethod
+    def forward(ctx, p1, p2, lengths1, lengths2, K, norm, return_nn):
+        dists, idx, nn = ops.knn_points(p1, p2, lengths1, lengths2, K=K, norm=norm, want_nn=return_nn)
+        ctx.save_for_backward(p1, p2, idx, lengths1, lengths2)
+        ctx.norm = norm
+        ctx.mark_non_differentiable(idx)
+        ctx.set_materialize_grads(False)
+        return dists, idx, nn
+
+    @staticmethod
+    def backward(ctx, grad_dists, _grad_idx, grad_nn):
+        p1, p2, idx, lengths1, lengths2 = ctx.saved_tensors
+        g_p1 = g_p2 = None
+        if grad_dists is not None:
+            g_p1, t = ops.knn_points_bwd(p1, p2, idx, grad_dists.contiguous(), lengths1, lengths2, norm=ctx.norm)
+            if ctx.needs_input_grad[1]:
+                g_p2 = ops.knn_scatter_add(t, idx, p2.shape[1], rows=lengths1, slots=lengths2, negate=True, deterministic=DETERMINISTIC)
+        if grad_nn is not None and ctx.needs_input_grad[1]:
+            g_nn = ops.knn_scatter_add(grad_nn.contiguous(), idx, p2.shape[1], rows=lengths1, slots=lengths2, deterministic=DETERMINISTIC)
+            g_p2 = g_nn if g_p2 is None else g_p2 + g_nn
+        return (g_p1 if ctx.needs_input_grad[0] else None), g_p2, None, None, None, None, None
+
+
+class KnnGather(Function):
+    """pytorch3d.ops.knn_gather: x (N,M,U), idx (N,L,K) int64, lengths (device int64 | None) -> (N,L,K,U), zeros in slots
+    k >= lengths[n]; grad w.r.t. x."""
+
+    @staticmethod
+    def forward(ctx, x, idx, lengths):
+        ctx.save_for_backward(idx, lengths)
+        ctx.M = x.shape[1]
+        return ops.knn_gather(x, idx, lengths)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        idx, lengths = ctx.saved_tensors
+        return ops.knn_scatter_add(grad_out.contiguous(), idx, ctx.M, slots=lengths, deterministic=DETERMINISTIC), None, None
+
+
 furthest_point_sample = FurthestPointSampling.apply
 gather_operation = GatherOperation.apply
 
@@ -309,6 +353,43 @@ def grouping_operation(features, idx):
         from . import torch_cpu
         return torch_cpu.grouping_operation(features, idx)
     return GroupingOperation.apply(features, idx)
+
+
+# ------------------------------------------------------------------ the pytorch3d.ops surface (README "The pytorch3d.ops surface")
+def _device_lengths(lengths, N, like, name):
+    """lengths of a ragged batch: None | a device int64 tensor | a CPU tensor or a list, uploaded once -- never read back."""
+    if lengths is None or not like.is_cuda:
+        return lengths if lengths is None or isinstance(lengths, torch.Tensor) else torch.as_tensor(lengths, dtype=torch.int64)
+    return ops._lengths(lengths, N, like.device, name)
+
+
+def knn_points(p1, p2, lengths1=None, lengths2=None, norm=2, K=1, version=-1, return_nn=False, return_sorted=True):
+    """pytorch3d.ops.knn_points -> (dists (N,P1,K), idx (N,P1,K) int64, knn (N,P1,K,D) | None); include/upp_hip.h upp_knn_points."""
+    if norm not in (1, 2):
+        raise ValueError("Support for 1 or 2 norm.")
+    if p1.dim() != 3 or p2.dim() != 3:
+        raise ValueError("pts1 and pts2 must be (N, P, D) tensors.")
+    if p1.shape[0] != p2.shape[0]:
+        raise ValueError("pts1 and pts2 must have the same batch dimension.")
+    if p1.shape[2] != p2.shape[2]:
+        raise ValueError("pts1 and pts2 must have the same point dimension.")
+    N, K = p1.shape[0], int(K)
+    lengths1, lengths2 = _device_lengths(lengths1, N, p1, "lengths1"), _device_lengths(lengths2, N, p1, "lengths2")
+    if _torch_cpu(p1, p2):
+        from . import torch_cpu
+        return torch_cpu.knn_points(p1, p2, lengths1, lengths2, norm=norm, K=K, return_nn=return_nn)
+    return KnnPoints.apply(p1.contiguous(), p2.contiguous(), lengths1, lengths2, K, int(norm), bool(return_nn))
+
+
+def knn_gather(x, idx, lengths=None):
+    """pytorch3d.ops.knn_gather: x (N,M,U), idx (N,L,K) int64 -> (N,L,K,U), zeros in slots k >= lengths[n]."""
+    if x.dim() != 3 or idx.dim() != 3 or x.shape[0] != idx.shape[0]:
+        raise ValueError("x (N, M, U) and idx (N, L, K) must have the same batch dimension.")
+    lengths = _device_lengths(lengths, x.shape[0], x, "lengths")
+    if _torch_cpu(x, idx):
+        from . import torch_cpu
+        return torch_cpu.knn_gather(x, idx, lengths)
+    return KnnGather.apply(x.contiguous(), idx.contiguous(), lengths)
 
 
 class QueryAndGroup(torch.nn.Module):
@@ -1804,7 +1885,7 @@ ADAPTER_FACTORS = True        # ... which inside a deferred scope writes per-row
 
 # Reproducible training (README "Reproducible training"): with DETERMINISTIC on, the autograd nodes whose backward (or forward: the EMD
 # cost) sums with f32 atomics -- GatherOperation, _FpsGather, _KnnGroup, _GroupPoints, ChamferFunction, _ChamferLoss,
-# EarthMoverDistanceFunction, ThreeInterpolate, GroupingOperation -- call the library's `_det` siblings (a defined summation order: include/upp_hip.h "deterministic
+# EarthMoverDistanceFunction, ThreeInterpolate, GroupingOperation, KnnPoints, KnnGather -- call the library's `_det` siblings (a defined summation order: include/upp_hip.h "deterministic
 # scatter-adds").  Read at CALL time, also by the backward thread; a captured step keeps the choice it was captured under, whatever the
 # attribute says at replay.  UPP_DETERMINISTIC=1 sets it once, at import.
 DETERMINISTIC = os.environ.get("UPP_DETERMINISTIC", "").strip() not in ("", "0")

@@ -402,6 +402,121 @@ def grouping_bwd(grad_out, idx, N, deterministic=False):
     return grad
 
 
+# ------------------------------------------------------------------ the pytorch3d.ops surface (include/upp_hip.h)
+KNN_POINTS_MAX_D, KNN_POINTS_MAX_K = 32, 64
+
+
+def _lengths(lengths, N, dev, name):
+    """None | a device int64 tensor (N,) | a CPU tensor or a sequence (uploaded) -> a device int64 tensor or None.  Its CONTENT is never
+    read here: the kernels clamp it to the array's extent (reading it back would synchronise)."""
+    if lengths is None:
+        return None
+    if not isinstance(lengths, torch.Tensor):
+        lengths = torch.as_tensor(lengths, dtype=torch.int64)
+    if lengths.dim() != 1 or lengths.numel() != N:
+        raise ValueError(f"{name} must hold one length per cloud: ({N},), got {tuple(lengths.shape)}")
+    if lengths.is_cuda:
+        if lengths.device != dev:
+            raise RuntimeError("all tensors must be on the same device")
+        if lengths.dtype != torch.int64:
+            raise RuntimeError(f"{name} must be torch.int64 on the device, got {lengths.dtype}")
+        return lengths.contiguous()
+    return lengths.to(torch.int64).to(dev, non_blocking=True)
+
+
+def _knn_points_args(p1, p2, K, norm):
+    _need(p1, "p1", torch.float32, 3)
+    _need(p2, "p2", torch.float32, 3)
+    _same_device(p1, p2)
+    if norm not in (1, 2):
+        raise ValueError("knn_points: norm must be 1 or 2")
+    if p1.shape[0] != p2.shape[0] or p1.shape[2] != p2.shape[2]:
+        raise ValueError("knn_points: p1 (N,P1,D) and p2 (N,P2,D) must agree in N and D, got %s and %s" % (tuple(p1.shape), tuple(p2.shape)))
+    N, P1, D = p1.shape
+    K = int(K)
+    if not (1 <= D <= KNN_POINTS_MAX_D) or not (1 <= K <= KNN_POINTS_MAX_K):
+        # what the library answers with UPP_E_RANGE, said with the limit's name (there is no slower path to fall back to)
+        raise RuntimeError("knn_points: D = %d, K = %d is outside the served range 1 <= D <= %d, 1 <= K <= %d (UPP_E_RANGE)"
+                           % (D, K, KNN_POINTS_MAX_D, KNN_POINTS_MAX_K))
+    if P1 < 1 or p2.shape[1] < 1:
+        raise ValueError("knn_points: p1 and p2 need at least one point per cloud (ragged batches: lengths1 / lengths2)")
+    return N, P1, p2.shape[1], D, K
+
+
+def knn_points(p1, p2, lengths1=None, lengths2=None, K=1, norm=2, want_nn=False):
+    """p1 (N,P1,D), p2 (N,P2,D) -> dists (N,P1,K) f32 (squared L2 / L1), idx (N,P1,K) int64, nn (N,P1,K,D) | None: the K nearest p2
+    points of every p1 point in ascending (distance, index); zeros in slots k >= min(K, lengths2) and rows i >= lengths1
+    (upp_knn_points: one launch that writes every element, lengths applied on the device)."""
+    N, P1, P2, D, K = _knn_points_args(p1, p2, K, norm)
+    dev = p1.device
+    lengths1, lengths2 = _lengths(lengths1, N, dev, "lengths1"), _lengths(lengths2, N, dev, "lengths2")
+    dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
+    idx = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
+    nn = torch.empty((N, P1, K, D), dtype=torch.float32, device=dev) if want_nn else None
+    if N:
+        _call(dev, "upp_knn_points", _abi.ptr(p1), _abi.ptr(p2), _abi.ptr(lengths1), _abi.ptr(lengths2), _abi.ptr(dists), _abi.ptr(idx),
+              _abi.ptr(nn), N, P1, P2, D, K, int(norm))
+    return dists, idx, nn
+
+
+def knn_points_bwd(p1, p2, idx, grad_dists, lengths1=None, lengths2=None, norm=2):
+    """-> g_p1 (N,P1,D) summed over k ascending, t (N,P1,K,D) the per-slot terms (zero in padded slots); the gradient of p2 is
+    knn_scatter_add(t, idx, P2, ..., negate=True) (upp_knn_points_bwd)."""
+    _need(idx, "idx", torch.int64, 3)
+    _need(grad_dists, "grad_dists", torch.float32, 3)
+    N, P1, P2, D, K = _knn_points_args(p1, p2, idx.shape[2], norm)
+    _same_device(p1, idx, grad_dists)
+    if tuple(idx.shape) != (N, P1, K) or tuple(grad_dists.shape) != (N, P1, K):
+        raise RuntimeError("knn_points_bwd: idx and grad_dists must both be (N, P1, K)")
+    dev = p1.device
+    lengths1, lengths2 = _lengths(lengths1, N, dev, "lengths1"), _lengths(lengths2, N, dev, "lengths2")
+    g_p1 = torch.empty((N, P1, D), dtype=torch.float32, device=dev)
+    t = torch.empty((N, P1, K, D), dtype=torch.float32, device=dev)
+    if N:
+        _call(dev, "upp_knn_points_bwd", _abi.ptr(p1), _abi.ptr(p2), _abi.ptr(idx), _abi.ptr(grad_dists), _abi.ptr(lengths1),
+              _abi.ptr(lengths2), _abi.ptr(g_p1), _abi.ptr(t), N, P1, P2, D, K, int(norm))
+    return g_p1, t
+
+
+def knn_gather(x, idx, lengths=None):
+    """x (N,M,U), idx (N,L,K) int64 -> (N,L,K,U) = x[n, idx[n,l,k]], zeros in slots k >= lengths[n] (upp_knn_gather)."""
+    _need(x, "x", torch.float32, 3)
+    _need(idx, "idx", torch.int64, 3)
+    _same_device(x, idx)
+    N, M, U = x.shape
+    if idx.shape[0] != N:
+        raise ValueError("knn_gather: x and idx batch sizes differ")
+    _, L, K = idx.shape
+    lengths = _lengths(lengths, N, x.device, "lengths")
+    out = torch.empty((N, L, K, U), dtype=torch.float32, device=x.device)
+    if out.numel():
+        if M < 1:
+            raise ValueError("knn_gather: x has no rows to gather")
+        _call(x.device, "upp_knn_gather", _abi.ptr(x), _abi.ptr(idx), _abi.ptr(lengths), _abi.ptr(out), N, M, L, K, U)
+    return out
+
+
+def knn_scatter_add(src, idx, M, rows=None, slots=None, negate=False, deterministic=False):
+    """src (N,L,K,U), idx (N,L,K) int64 -> (N,M,U): src[n,l,k] added to (negate: subtracted from) row idx[n,l,k], over the slots with
+    l < rows[n] and k < slots[n].  f32 atomics into an array the library zeroes with a kernel (upp_knn_scatter_add), or -- deterministic
+    -- every row's sum in ascending l * K + k (upp_knn_scatter_add_det).  The gradient of p2 in knn_points and the backward of knn_gather."""
+    _need(src, "src", torch.float32, 4)
+    _need(idx, "idx", torch.int64, 3)
+    _same_device(src, idx)
+    N, L, K, U = src.shape
+    if tuple(idx.shape) != (N, L, K):
+        raise RuntimeError("knn_scatter_add: src must be (N, L, K, U) for idx (N, L, K)")
+    M = int(M)
+    rows, slots = _lengths(rows, N, src.device, "rows"), _lengths(slots, N, src.device, "slots")
+    out = torch.empty((N, M, U), dtype=torch.float32, device=src.device)                 # (written in full by either entry point)
+    if out.numel():
+        if src.numel() == 0:
+            raise ValueError("knn_scatter_add: an empty source list")
+        _call(src.device, "upp_knn_scatter_add_det" if deterministic else "upp_knn_scatter_add", _abi.ptr(src), _abi.ptr(idx),
+              _abi.ptr(rows), _abi.ptr(slots), _abi.ptr(out), N, M, L, K, U, int(bool(negate)))
+    return out
+
+
 # ------------------------------------------------------------------ Chamfer
 def chamfer_fwd(xyz1, xyz2):
     _need(xyz1, "xyz1", torch.float32, 3, 3)

@@ -2,8 +2,8 @@
 torch-CPU: utils.misc.fps + torch.cdist kNN fallback -- plumbing, no GPU").  OFF by default: the product's operators have no CPU
 path (`upp_hip.ops` raises on CPU tensors) and a HIP tensor never comes here.  `enable()` -- or UPP_TORCH_CPU=1 in the environment --
 lets the grouping entry points of upp_hip.functional (fps_gather, knn_query, knn_group, ChamferFunction, and the packed-batch pair
-fps_gather_ragged / cloud_norm_ragged, and the four pointnet2_ops operators ball_query, three_nn, three_interpolate,
-grouping_operation) serve CPU tensors with the torch formulations below, so that a reference user can run the model's forward on a
+fps_gather_ragged / cloud_norm_ragged, the four pointnet2_ops operators ball_query, three_nn, three_interpolate,
+grouping_operation, and pytorch3d.ops' knn_points / knn_gather) serve CPU tensors with the torch formulations below, so that a reference user can run the model's forward on a
 GPU-less host to check plumbing (state-dict loading, shapes, config wiring).  Nothing here touches oracle/ (test infrastructure) and nothing here is timed by bench.py.
 
 Semantics follow the reference's own CPU-side formulations: FPS as datasets/ModelNetDataset.py:29-49 (start at index 0, arg-max of the
@@ -132,6 +132,48 @@ def grouping_operation(features, idx):
     B, C, _ = features.shape
     _, P, S = idx.shape
     return torch.gather(features, 2, idx.long().reshape(B, 1, P * S).expand(-1, C, -1)).reshape(B, C, P, S)
+
+
+def _clamped(lengths, N, P):
+    """lengths (None | tensor | list) -> (N,) int64 in [0, P]."""
+    if lengths is None:
+        return torch.full((N,), P, dtype=torch.int64)
+    return torch.as_tensor(lengths, dtype=torch.int64).reshape(N).clamp(0, P)
+
+
+def knn_gather(x, idx, lengths=None):
+    """pytorch3d.ops.knn_gather: x (N,M,U), idx (N,L,K) -> (N,L,K,U) = x[n, idx[n,l,k]], zeros in slots k >= lengths[n]; differentiable
+    w.r.t. x."""
+    N, M, U = x.shape
+    _, L, K = idx.shape
+    out = torch.gather(x.unsqueeze(1).expand(-1, L, -1, -1), 2, idx.long().unsqueeze(-1).expand(-1, -1, -1, U))
+    live = torch.arange(K).view(1, 1, K) < _clamped(lengths, N, K).view(N, 1, 1)
+    return torch.where(live.unsqueeze(-1), out, torch.zeros((), dtype=x.dtype))
+
+
+def knn_points(p1, p2, lengths1=None, lengths2=None, norm=2, K=1, return_nn=False):
+    """pytorch3d.ops.knn_points by the rules of include/upp_hip.h "the pytorch3d.ops surface": p1 (N,P1,D), p2 (N,P2,D) -> (dists (N,P1,K)
+    squared L2 / L1, idx (N,P1,K) int64 in ascending (distance, index), nn (N,P1,K,D) | None); zeros in slots k >= min(K, lengths2) and
+    rows i >= lengths1.  dists is differentiable w.r.t. p1 and p2, nn w.r.t. p2.  The distance is a plain f32 sum over the coordinates
+    (exact on lattice inputs, where it has the kernels' bits; elsewhere a last-bit difference can reorder near-ties)."""
+    N, P1, D = p1.shape
+    P2 = p2.shape[1]
+    len1, len2 = _clamped(lengths1, N, P1), _clamped(lengths2, N, P2)
+    diff = p1.unsqueeze(2) - p2.unsqueeze(1)                                               # (N,P1,P2,D)
+    d = torch.zeros(diff.shape[:3], dtype=p1.dtype)
+    for j in range(D):                                                                     # ascending j, one term at a time
+        d = d + (diff[..., j] * diff[..., j] if norm == 2 else diff[..., j].abs())
+    rank = torch.where(torch.arange(P2).view(1, 1, P2) < len2.view(N, 1, 1), d.detach(), torch.full((), float("inf"), dtype=d.dtype))
+    if K > P2:
+        rank = torch.cat([rank, rank.new_full((N, P1, K - P2), float("inf"))], -1)
+    order = torch.argsort(rank, dim=-1, stable=True)[:, :, :K]
+    live = (torch.arange(K).view(1, 1, K) < len2.clamp(max=K).view(N, 1, 1)) & (torch.arange(P1).view(1, P1, 1) < len1.view(N, 1, 1))
+    idx = torch.where(live, order, torch.zeros_like(order))
+    dists = torch.where(live, torch.gather(d, 2, idx), torch.zeros((), dtype=d.dtype))
+    nn = None
+    if return_nn:
+        nn = torch.where(live.unsqueeze(-1), knn_gather(p2, idx), torch.zeros((), dtype=p2.dtype))
+    return dists, idx, nn
 
 
 def chamfer(xyz1, xyz2):

@@ -210,6 +210,50 @@ int upp_grouping_fwd(const float *features, const int32_t *idx, float *out,
 int upp_grouping_bwd(const float *grad_out, const int32_t *idx, float *grad_features,
                      int B, int C, int N, int P, int S, void *stream);
 
+/* ---- the pytorch3d.ops surface: knn_points, knn_gather ---------------------------------------------------
+ * The fourth third-party import of the reference's model files (`import pytorch3d.ops`; called as
+ * pytorch3d.ops.knn_points(noise, partial, K=4, return_nn=True) at models/Point_MAE_pretask_dev.py:680).  The upstream sources
+ * (pytorch3d/csrc/knn/knn.cu) were not at hand: the rules below are RESTATED, as for the pointnet2_ops surface above, and stay unpinned
+ * until they can be compared with the CUDA kernels' output (tests/_knn_points_reference.py is the same restatement in numpy).
+ *
+ * upp_knn_points: p1 (N,P1,D), p2 (N,P2,D), lengths1 / lengths2 (N,) int64 ON THE DEVICE or NULL (= P1 / P2; clamped to [0, P] by the
+ *   kernel, never read back) -> dists (N,P1,K) f32, idx (N,P1,K) int64, nn (N,P1,K,D) f32 or NULL.
+ *   Distance of p1[n][i] and p2[n][r]:  d = 0; for j = 0 ... D-1 ascending: diff = p1[j] - p2[j]; d = fma(diff, diff, d)  (norm 2: the
+ *   SQUARED distance, no root is taken) or d = d + |diff| (norm 1), one rounding per step.  At D = 3 this is ssd3 of csrc/common.h: the
+ *   same query lists the same neighbours as upp_knn, and dists is the value upp_knn takes the square root of.
+ *   Order: ascending (distance, index) over r < len2 = lengths2[n] -- a refinement of upstream, whose order among exactly equal
+ *   distances is not defined.
+ *   Padding: slots k >= min(K, len2) hold dists 0, idx 0, nn 0; rows i >= lengths1[n] are zero in all three outputs.  (Upstream gathers
+ *   its zero index there, which puts p2[n][0] into nn: a deliberate deviation.)  Every element of the three outputs is written by the
+ *   kernel: nothing to zero-fill.  One launch.
+ *   Limits: 1 <= D <= 32, 1 <= K <= 64 (K may exceed P2), N <= 65535 -- UPP_E_RANGE beyond; norm must be 1 or 2 and every size
+ *   positive (UPP_E_BADARG); N == 0 is a no-op.
+ * upp_knn_points_bwd: from grad_dists (N,P1,K) and the forward's idx:  t[n][i][k][d] = (2.0f * g) * diff  (norm 2) or sign(diff) * g
+ *   (norm 1; sign(0) = 0) with g = grad_dists[n][i][k], diff = p1[n][i][d] - p2[n][idx[n][i][k]][d]; 0.0f in padded slots.
+ *   g_p1[n][i][d] = +0.0f, then + t[n][i][k][d] for the filled slots in ascending k (plain f32 adds).  t (N,P1,K,D) is an output: the
+ *   gradient of p2 is the row scatter of -t (below).  One launch.
+ * upp_knn_gather: x (N,M,U), idx (N,L,K) int64, lengths (N,) int64 or NULL -> out (N,L,K,U) = x[n][idx[n][l][k]], 0.0f in slots
+ *   k >= lengths[n] (and for an index outside [0, M)).
+ * upp_knn_scatter_add: src (N,L,K,U), idx (N,L,K) int64 -> out (N,M,U): out[n][idx[n][l][k]][u] += src[n][l][k][u] (-= with negate != 0)
+ *   by f32 atomics in an unspecified order, over the slots with l < rows[n] and k < slots[n] (each list (N,) int64 or NULL = all) whose
+ *   index lies in [0, M).  out is zeroed first BY A KERNEL of the library: the caller zero-fills nothing.  It serves the gradient of p2
+ *   (src = t, negate) and the backward of upp_knn_gather.
+ * upp_knn_scatter_add_det: the same sums in a defined order -- out[n][r][u] = +0.0f, then + src (or - src) of its slots in ascending
+ *   l * K + k, one rounded f32 addition at a time (csrc/det_scan.h; every row is written, nothing is zeroed).
+ * Limits of the last three: every size positive, L * K < 2^31, M * U < 2^31; they loop their grid and have no batch limit. */
+int upp_knn_points(const float *p1, const float *p2, const int64_t *lengths1, const int64_t *lengths2,
+                   float *dists, int64_t *idx, float *nn,
+                   int N, int P1, int P2, int D, int K, int norm, void *stream);
+int upp_knn_points_bwd(const float *p1, const float *p2, const int64_t *idx, const float *grad_dists,
+                       const int64_t *lengths1, const int64_t *lengths2, float *g_p1, float *t,
+                       int N, int P1, int P2, int D, int K, int norm, void *stream);
+int upp_knn_gather(const float *x, const int64_t *idx, const int64_t *lengths, float *out,
+                   int N, int M, int L, int K, int U, void *stream);
+int upp_knn_scatter_add(const float *src, const int64_t *idx, const int64_t *rows, const int64_t *slots, float *out,
+                        int N, int M, int L, int K, int U, int negate, void *stream);
+int upp_knn_scatter_add_det(const float *src, const int64_t *idx, const int64_t *rows, const int64_t *slots, float *out,
+                            int N, int M, int L, int K, int U, int negate, void *stream);
+
 /* ---- Chamfer distance ----------------------------------------------------------
  * Replaces chamfer.forward / chamfer.backward (reference
  * extensions/chamfer_dist/chamfer_cuda.cpp:36-39, kernels chamfer.cu:15-145 and
@@ -280,7 +324,8 @@ int upp_emd_matchcost_bwd(const float *grad_cost, const float *xyz1, const float
  *                           with idx[b][i][j] == r, in ascending i * 3 + j (the product rounded first, then the sum); indices outside
  *                           [0, m) are skipped; grad_features needs NO zero-fill.
  *   upp_grouping_bwd_det    grad_features[b][ch][r] = +0.0f, then + grad_out[b][ch][p][s] for every (p, s) with idx[b][p][s] == r,
- *                           in ascending p * S + s; grad_features needs NO zero-fill (upp_gather_bwd_det on the flattened list). */
+ *                           in ascending p * S + s; grad_features needs NO zero-fill (upp_gather_bwd_det on the flattened list).
+ *   upp_knn_scatter_add_det stated and declared with its sibling under "the pytorch3d.ops surface" above: ascending l * K + k. */
 int upp_chamfer_bwd_det(const float *xyz1, const float *xyz2, const int32_t *idx1, const int32_t *idx2,
                         const float *grad_dist1, const float *grad_dist2, float *g1, float *g2,
                         int B, int n, int m, void *stream);
