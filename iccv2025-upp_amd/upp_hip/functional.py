@@ -392,6 +392,73 @@ def knn_gather(x, idx, lengths=None):
     return KnnGather.apply(x.contiguous(), idx.contiguous(), lengths)
 
 
+# ------------------------------------------------------------------ edge convolution (README "The DGCNN grouper")
+class _EdgeConvMax(Function):
+    """max_k lrelu(GroupNorm(A[idx] + Bq)) as one node (include/upp_hip.h "edge convolution"): saves A, Bq, idx, the arg-extreme bytes and
+    the (B,G) statistics -- never a (B,Nq,K,O) tensor.  The g_A scatter-add follows the deterministic mode: `det` None reads DETERMINISTIC
+    when the backward runs, True / False fixes it for this call."""
+
+    @staticmethod
+    def forward(ctx, A, Bq, idx, gamma, beta, groups, eps, slope, det):
+        out, arg, mean, rstd = ops.edge_conv_fwd(A, Bq, idx, gamma, beta, groups, eps, slope)
+        ctx.save_for_backward(A, Bq, idx, arg, gamma, beta, mean, rstd)
+        ctx.cfg = (groups, slope, det)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        A, Bq, idx, arg, gamma, beta, mean, rstd = ctx.saved_tensors
+        groups, slope, det = ctx.cfg
+        g_A, g_Bq, g_gamma, g_beta = ops.edge_conv_bwd(g_out.contiguous(), A, Bq, idx, arg, gamma, beta, mean, rstd, groups, slope,
+                                                       deterministic=DETERMINISTIC if det is None else det)
+        need = ctx.needs_input_grad
+        return (g_A if need[0] else None, g_Bq if need[1] else None, None, g_gamma if groups and need[3] else None,
+                g_beta if groups and need[4] else None, None, None, None, None)
+
+
+def _edge_norm(norm):
+    """None | torch.nn.GroupNorm | (G, gamma, beta, eps) -> None | (G, gamma, beta, eps)"""
+    if norm is None:
+        return None
+    if isinstance(norm, torch.nn.GroupNorm):
+        if norm.weight is None:
+            raise ValueError("edge_conv_max: the GroupNorm must be affine")
+        return norm.num_groups, norm.weight, norm.bias, norm.eps
+    G, gamma, beta, eps = norm
+    return int(G), gamma, beta, float(eps)
+
+
+def edge_conv_usable(A, Bq, idx, norm=None):
+    """Do the fused kernels serve these operands (HIP f32 / int64 tensors of the served sizes)?"""
+    norm = _edge_norm(norm)
+    if not (A.is_cuda and Bq.is_cuda and idx.is_cuda and A.dtype == torch.float32 and Bq.dtype == torch.float32 and idx.dtype == torch.int64
+            and A.dim() == 3 and Bq.dim() == 3 and idx.dim() == 3):
+        return False
+    if norm is not None and not (norm[1].is_cuda and norm[1].dtype == torch.float32 and norm[2].dtype == torch.float32):
+        return False
+    return ops.edge_conv_usable(A.shape[0], A.shape[1], idx.shape[1], idx.shape[2], A.shape[2], norm[0] if norm is not None else 0)
+
+
+def edge_conv_max(A, Bq, idx, norm=None, slope=0.2, deterministic=None):
+    """A (B,Nk,O) key-side product, Bq (B,Nq,O) query-side product (+ bias), idx (B,Nq,K) int64 -> (B,Nq,O) =
+    max_k leaky_relu(norm(A[b, idx[b,q,k]] + Bq[b,q]), slope).  norm: None, a torch.nn.GroupNorm or (G, gamma, beta, eps).
+    deterministic: None follows functional.DETERMINISTIC (read when the backward node runs), True / False per call.  HIP tensors outside
+    the served range raise (upp_edge_conv_fwd: 1 <= K <= 64, 1 <= O <= 512, G | O); CPU tensors take the torch formulation when
+    upp_hip.torch_cpu is enabled."""
+    if not 0.0 <= float(slope) <= 1.0:
+        raise ValueError("edge_conv_max: slope must be in [0, 1]")
+    norm = _edge_norm(norm)
+    if _torch_cpu(A, Bq, idx):
+        from . import torch_cpu
+        return torch_cpu.edge_conv_max(A, Bq, idx, norm, slope)
+    G, gamma, beta, eps = norm if norm is not None else (0, None, None, 1e-5)
+    if norm is not None and G < 1:
+        raise ValueError("edge_conv_max: a norm needs at least one group")
+    return _EdgeConvMax.apply(A.contiguous(), Bq.contiguous(), idx.contiguous(), None if gamma is None else gamma.contiguous(),
+                              None if beta is None else beta.contiguous(), int(G), float(eps), float(slope),
+                              None if deterministic is None else bool(deterministic))
+
+
 class QueryAndGroup(torch.nn.Module):
     """pointnet2_utils.QueryAndGroup: ball query around new_xyz, then the grouped coordinates (centre subtracted) and / or features.
     forward(xyz (B,N,3), new_xyz (B,P,3), features (B,C,N) | None) -> (B, 3+C, P, S) | (B, C, P, S) with use_xyz=False | (B, 3, P, S)
@@ -1885,7 +1952,7 @@ ADAPTER_FACTORS = True        # ... which inside a deferred scope writes per-row
 
 # Reproducible training (README "Reproducible training"): with DETERMINISTIC on, the autograd nodes whose backward (or forward: the EMD
 # cost) sums with f32 atomics -- GatherOperation, _FpsGather, _KnnGroup, _GroupPoints, ChamferFunction, _ChamferLoss,
-# EarthMoverDistanceFunction, ThreeInterpolate, GroupingOperation, KnnPoints, KnnGather -- call the library's `_det` siblings (a defined summation order: include/upp_hip.h "deterministic
+# EarthMoverDistanceFunction, ThreeInterpolate, GroupingOperation, KnnPoints, KnnGather, _EdgeConvMax -- call the library's `_det` siblings (a defined summation order: include/upp_hip.h "deterministic
 # scatter-adds").  Read at CALL time, also by the backward thread; a captured step keeps the choice it was captured under, whatever the
 # attribute says at replay.  UPP_DETERMINISTIC=1 sets it once, at import.
 DETERMINISTIC = os.environ.get("UPP_DETERMINISTIC", "").strip() not in ("", "0")

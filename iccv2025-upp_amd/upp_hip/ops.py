@@ -517,6 +517,82 @@ def knn_scatter_add(src, idx, M, rows=None, slots=None, negate=False, determinis
     return out
 
 
+# ------------------------------------------------------------------ edge convolution (include/upp_hip.h "edge convolution")
+EDGE_CONV_MAX_K, EDGE_CONV_MAX_O = 64, 512
+
+
+def edge_conv_usable(B, Nk, Nq, K, O, G=0):
+    """The served range of upp_edge_conv_fwd / _bwd (sizes only)."""
+    return (1 <= K <= EDGE_CONV_MAX_K and 1 <= O <= EDGE_CONV_MAX_O and (G == 0 or (G > 0 and O % G == 0)) and 0 <= B <= 65535 and Nk >= 1
+            and 1 <= Nq < 2 ** 30 and Nq * K < 2 ** 31 and Nq * O < 2 ** 31 and Nk * O < 2 ** 31)
+
+
+def _edge_conv_args(A, Bq, idx, gamma, beta, G):
+    _need(A, "A", torch.float32, 3)
+    _need(Bq, "Bq", torch.float32, 3)
+    _need(idx, "idx", torch.int64, 3)
+    _same_device(A, Bq, idx)
+    B, Nk, O = A.shape
+    _, Nq, K = idx.shape
+    if tuple(Bq.shape) != (B, Nq, O) or idx.shape[0] != B:
+        raise RuntimeError("edge_conv: A (B, Nk, O), Bq (B, Nq, O) and idx (B, Nq, K) do not fit together")
+    G = int(G)
+    if G:
+        _need(gamma, "gamma", torch.float32, 1, O)
+        _need(beta, "beta", torch.float32, 1, O)
+        _same_device(A, gamma, beta)
+    return B, Nk, Nq, K, O, G
+
+
+def _edge_conv_work(A, B, Nq, O, G):
+    return torch.empty(int(_abi.load().upp_edge_conv_work_floats(B, Nq, O)), dtype=torch.float32, device=A.device) if G else None
+
+
+def edge_conv_fwd(A, Bq, idx, gamma=None, beta=None, groups=0, eps=1e-5, slope=0.2):
+    """A (B,Nk,O), Bq (B,Nq,O), idx (B,Nq,K) int64 -> out (B,Nq,O) = max_k lrelu(GroupNorm(A[idx] + Bq)), arg (B,Nq,O) uint8,
+    mean / rstd (B,G) | None (groups == 0: no norm).  y = A[idx] + Bq is never stored."""
+    B, Nk, Nq, K, O, G = _edge_conv_args(A, Bq, idx, gamma, beta, groups)
+    out = torch.empty((B, Nq, O), dtype=torch.float32, device=A.device)
+    arg = torch.empty((B, Nq, O), dtype=torch.uint8, device=A.device)
+    mean = torch.empty((B, G), dtype=torch.float32, device=A.device) if G else None
+    rstd = torch.empty((B, G), dtype=torch.float32, device=A.device) if G else None
+    work = _edge_conv_work(A, B, Nq, O, G)
+    if B == 0:
+        return out, arg, mean, rstd
+    _call(A.device, "upp_edge_conv_fwd", _abi.ptr(A), _abi.ptr(Bq), _abi.ptr(idx), _abi.ptr(gamma if G else None),
+          _abi.ptr(beta if G else None), float(eps), float(slope), G, _abi.ptr(out), _abi.ptr(arg), _abi.ptr(mean), _abi.ptr(rstd),
+          _abi.ptr(work), B, Nk, Nq, K, O)
+    return out, arg, mean, rstd
+
+
+def edge_conv_bwd(g_out, A, Bq, idx, arg, gamma=None, beta=None, mean=None, rstd=None, groups=0, slope=0.2, deterministic=False):
+    """-> g_A (B,Nk,O), g_Bq (B,Nq,O), g_gamma (O,) | None, g_beta (O,) | None.  g_A is summed by f32 atomics (into zeros written by a
+    kernel), or -- deterministic -- in ascending q * K + k from a stored g_y (B,Nq,K,O); everything else has a fixed order in both modes."""
+    B, Nk, Nq, K, O, G = _edge_conv_args(A, Bq, idx, gamma, beta, groups)
+    _need(g_out, "g_out", torch.float32, 3)
+    _need(arg, "arg", torch.uint8, 3)
+    if tuple(g_out.shape) != (B, Nq, O) or tuple(arg.shape) != (B, Nq, O):
+        raise RuntimeError("edge_conv_bwd: g_out and arg must be (B, Nq, O)")
+    if G:
+        _need(mean, "mean", torch.float32, 2, G)
+        _need(rstd, "rstd", torch.float32, 2, G)
+    g_A = torch.empty((B, Nk, O), dtype=torch.float32, device=A.device)
+    g_Bq = torch.empty((B, Nq, O), dtype=torch.float32, device=A.device)
+    g_gamma = torch.empty((O,), dtype=torch.float32, device=A.device) if G else None
+    g_beta = torch.empty((O,), dtype=torch.float32, device=A.device) if G else None
+    if B == 0:
+        if G:
+            g_gamma.zero_(); g_beta.zero_()
+        return g_A, g_Bq, g_gamma, g_beta
+    work = _edge_conv_work(A, B, Nq, O, G)
+    g_y = torch.empty((B, Nq, K, O), dtype=torch.float32, device=A.device) if deterministic else None
+    _call(A.device, "upp_edge_conv_bwd", _abi.ptr(g_out), _abi.ptr(A), _abi.ptr(Bq), _abi.ptr(idx), _abi.ptr(arg),
+          _abi.ptr(gamma if G else None), _abi.ptr(beta if G else None), _abi.ptr(mean if G else None), _abi.ptr(rstd if G else None),
+          float(slope), G, _abi.ptr(g_A), _abi.ptr(g_Bq), _abi.ptr(g_gamma), _abi.ptr(g_beta), _abi.ptr(work), _abi.ptr(g_y),
+          B, Nk, Nq, K, O)
+    return g_A, g_Bq, g_gamma, g_beta
+
+
 # ------------------------------------------------------------------ Chamfer
 def chamfer_fwd(xyz1, xyz2):
     _need(xyz1, "xyz1", torch.float32, 3, 3)

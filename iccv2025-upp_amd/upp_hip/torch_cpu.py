@@ -176,6 +176,20 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, norm=2, K=1, return_nn=Fals
     return dists, idx, nn
 
 
+def edge_conv_max(A, Bq, idx, norm=None, slope=0.2):
+    """The edge convolution of include/upp_hip.h "edge convolution" as torch operators (any device; differentiable w.r.t. A, Bq, gamma,
+    beta): A (B,Nk,O), Bq (B,Nq,O), idx (B,Nq,K) int64, norm None | (G, gamma, beta, eps) -> (B,Nq,O) =
+    max_k leaky_relu(group_norm(A[b, idx[b,q,k]] + Bq[b,q])).  It stores the (B,Nq,K,O) tensor the kernels avoid."""
+    import torch.nn.functional as F
+    B, Nq, K = idx.shape
+    O = A.shape[2]
+    y = torch.gather(A, 1, idx.reshape(B, Nq * K, 1).expand(-1, -1, O)).view(B, Nq, K, O) + Bq.unsqueeze(2)
+    if norm is not None:
+        G, gamma, beta, eps = norm
+        y = F.group_norm(y.permute(0, 3, 1, 2), int(G), gamma, beta, float(eps)).permute(0, 2, 3, 1)
+    return F.leaky_relu(y, float(slope)).max(dim=2)[0]
+
+
 def chamfer(xyz1, xyz2):
     """-> (dist1 (B,N), dist2 (B,M)) squared nearest-neighbour distances, differentiable (reference extensions/chamfer_dist)."""
     d = ((xyz1.unsqueeze(2) - xyz2.unsqueeze(1)) ** 2).sum(-1)

@@ -254,6 +254,46 @@ int upp_knn_scatter_add(const float *src, const int64_t *idx, const int64_t *row
 int upp_knn_scatter_add_det(const float *src, const int64_t *idx, const int64_t *rows, const int64_t *slots, float *out,
                             int N, int M, int L, int K, int U, int negate, void *stream);
 
+/* ---- edge convolution: gather, GroupNorm, LeakyReLU, max over the neighbours --------------------------------
+ * One layer of the reference's DGCNN_Grouper (models/dgcnn_group.py:91-144, models/AdaPoinTr.py:559-623) and, without the norm, the local
+ * branch of a PoinTr block (models/Transformer.py:176-213): max over k of act(norm(W [f_j - f_i ; f_i])).  With W = [W1 | W2] the conv is
+ * W1 f_j + (W2 - W1) f_i, two per-point products the CALLER makes with upp_linear_*; these entry points take the products:
+ *   A   (B,Nk,O) f32   key-side product            Bq  (B,Nq,O) f32   query-side product (+ bias)
+ *   idx (B,Nq,K) int64 neighbour rows into Nk, as upp_knn returns them; they must lie in [0, Nk) (the kernels clamp: no fault)
+ *   G > 0: GroupNorm(G, O) with gamma (O,), beta (O,), eps;  G == 0: no norm (gamma, beta, mean, rstd, work may be NULL)
+ *   slope: LeakyReLU, 0 <= slope <= 1
+ * Rules.  y[b,q,k,o] = A[b, idx[b,q,k], o] + Bq[b,q,o], one f32 addition.  Per (b, group) mean and BIASED variance over the group's
+ *   O / G channels x Nq x K values of y, rstd = 1 / sqrt(var + eps), as torch.nn.GroupNorm.  The statistics are summed in a fixed order:
+ *   (sum, M2) partials per slab of 8 query rows and channel (shifted by the slab's first value), combined in f64 as
+ *   upp_bn_rows_fwd's finalize does (mean = sum S_i / N, M2 = sum [M2_i + n_i (S_i / n_i - mean)^2]); no atomics.
+ *   z = ((y - mean) * rstd) * gamma + beta (four f32 operations, none contracted);  out = max_k lrelu(z),  lrelu(z) = z > 0 ? z : z * slope.
+ *   Per channel every one of those steps is monotone in y, so the maximum is attained at the largest y when gamma * rstd > 0 and at the
+ *   smallest when < 0: the kernel finds the extreme y and evaluates z ONCE -- the same bits as evaluating every z.  arg is defined ON y:
+ *   the lowest k of the maximum of y when gamma * rstd > 0 (an f32 product), the lowest k of the minimum when < 0, 0 when it is zero;
+ *   without a norm the lowest k of the maximum (z = y).
+ *   -> out (B,Nq,O) f32, arg (B,Nq,O) uint8, mean / rstd (B,G) f32.  Every element is written by a kernel; 3 launches (1 without a norm).
+ * Backward, from g_out (B,Nq,O):  g_z = g_out * (z > 0 ? 1 : slope) at k == arg, 0 elsewhere;  per group m1 = mean(gamma g_z),
+ *   m2 = mean(gamma g_z xhat);  g_y = rstd * ((gamma g_z - m1) - xhat m2), dense in k (no norm: g_y = g_z);  g_Bq = sum_k g_y in ascending
+ *   k;  g_A[b, idx[b,q,k]] += g_y;  g_gamma = sum g_z xhat, g_beta = sum g_z.  xhat = (y - mean) * rstd is recomputed from A, Bq, idx and
+ *   the saved statistics, never stored.  m1, m2, g_gamma, g_beta are summed from per-slab partials in a fixed order (f64), g_Bq in
+ *   registers: bit-identical from call to call.  g_A alone is a scatter-add:
+ *     g_y == NULL: f32 atomics into g_A, which the library zeroes first WITH A KERNEL -- the order is the hardware's; no tensor of
+ *                  B Nq K O elements exists in this mode.  5 launches + the zero fill (2 without a norm).
+ *     g_y != NULL: (B,Nq,K,O) f32 scratch.  The kernel stores g_y there and g_A = upp_knn_scatter_add_det of it: every row's sum in
+ *                  ascending q * K + k, every row written, nothing zeroed.
+ *   work: upp_edge_conv_work_floats(B, Nq, O) floats (a host function; 0 for a non-positive size), for forward and backward alike.
+ * Limits: 1 <= K <= 64, 1 <= O <= 512, G divides O, B <= 65535, Nq K, Nq O, Nk O < 2^31 and Nq < 2^30 -- UPP_E_RANGE beyond.  A null
+ *   pointer, a non-positive size, G < 0, eps < 0 or a slope outside [0, 1] (NaN included): UPP_E_BADARG.  Both before any launch; B == 0
+ *   is a no-op. */
+long long upp_edge_conv_work_floats(int B, int Nq, int O);
+int upp_edge_conv_fwd(const float *A, const float *Bq, const int64_t *idx, const float *gamma, const float *beta, float eps, float slope,
+                      int G, float *out, uint8_t *arg, float *mean, float *rstd, float *work,
+                      int B, int Nk, int Nq, int K, int O, void *stream);
+int upp_edge_conv_bwd(const float *g_out, const float *A, const float *Bq, const int64_t *idx, const uint8_t *arg,
+                      const float *gamma, const float *beta, const float *mean, const float *rstd, float slope, int G,
+                      float *g_A, float *g_Bq, float *g_gamma, float *g_beta, float *work, float *g_y,
+                      int B, int Nk, int Nq, int K, int O, void *stream);
+
 /* ---- Chamfer distance ----------------------------------------------------------
  * Replaces chamfer.forward / chamfer.backward (reference
  * extensions/chamfer_dist/chamfer_cuda.cpp:36-39, kernels chamfer.cu:15-145 and
