@@ -1340,11 +1340,21 @@ def ln_param_grad(g_h, xo, mean, rstd, chunks=32):
 ATTN_MAX_L = 2048
 
 
+def _attn_operand(t, name, count, aligned=True):
+    """float32, contiguous, `count` elements; 16-byte aligned where the kernels load the operand in 16-byte pieces"""
+    _need(t, name, torch.float32)
+    if t.numel() != count:
+        raise RuntimeError(f"{name} must hold {count} elements, got {tuple(t.shape)}")
+    if aligned and t.data_ptr() % 16:
+        raise RuntimeError(f"{name} must be 16-byte aligned (the attention kernels load 16-byte pieces); got a view at a storage offset")
+
+
 def attn_fwd(qkv, B, L, H, scale):
     """qkv (B, L, 3, H, 64) -> ctx (B, L, H * 64), lse (B, H, L).  L <= 96: attn_flash16.hip, L <= 160: attn_long.hip,
-    L <= ATTN_MAX_L: attn_stream.hip (K / V streamed through the LDS, online softmax); longer sequences raise."""
-    _need(qkv, "qkv", torch.float32)
-    hd = qkv.numel() // (B * L * 3 * H)
+    L <= ATTN_MAX_L: attn_stream.hip (K / V streamed through the LDS, online softmax); longer sequences raise.
+    qkv: float32, contiguous, 16-byte aligned."""
+    hd = 64
+    _attn_operand(qkv, "qkv", B * L * 3 * H * hd)
     ctx = torch.empty((B, L, H * hd), dtype=torch.float32, device=qkv.device)
     lse = torch.empty((B, H, L), dtype=torch.float32, device=qkv.device)
     _call(qkv.device, "upp_attn_fwd", _abi.ptr(qkv), _abi.ptr(ctx), _abi.ptr(lse), B, L, H, hd, float(scale))
@@ -1353,8 +1363,14 @@ def attn_fwd(qkv, B, L, H, scale):
 
 def attn_bwd(qkv, ctx, d_ctx, lse, B, L, H, scale):
     """d_qkv (B, L, 3, H, 64) from d_ctx and the forward's ctx / lse; the same three kernel families and the same range as attn_fwd.
-    No atomics at any L: two calls on the same inputs give the same bits."""
-    hd = qkv.numel() // (B * L * 3 * H)
+    No atomics at any L: two calls on the same inputs give the same bits.
+    All four operands: float32, contiguous, on one device; qkv, ctx and d_ctx 16-byte aligned."""
+    hd = 64
+    _attn_operand(qkv, "qkv", B * L * 3 * H * hd)
+    _attn_operand(ctx, "ctx", B * L * H * hd)
+    _attn_operand(d_ctx, "d_ctx", B * L * H * hd)
+    _attn_operand(lse, "lse", B * H * L, aligned=False)
+    _same_device(qkv, ctx, d_ctx, lse)
     d_qkv = torch.empty_like(qkv)
     _call(qkv.device, "upp_attn_bwd", _abi.ptr(qkv), _abi.ptr(ctx), _abi.ptr(d_ctx), _abi.ptr(lse), _abi.ptr(d_qkv), B, L, H, hd, float(scale))
     return d_qkv

@@ -457,6 +457,9 @@ int upp_ln_param_grad(const float *g_h, const float *xo, const float *mean, cons
  *   ctx (B,L,H*64): softmax(q k^T * scale) v, already in the layout of (:193) `.transpose(1,2).reshape(B,N,C)`
  *   lse (B,H,L): log-sum-exp of the scaled scores (saved for backward)
  *   d_qkv (B,L,3,H,64) from d_ctx (B,L,H*64)
+ * All arrays are dense (no strides) and hold exactly the element counts above.  qkv, ctx and d_ctx must be 16-byte aligned: the kernels
+ * load them in 16-byte pieces (every row is a multiple of 256 bytes, so an aligned base aligns every piece).  The library does not check
+ * the alignment; the torch operators (upp_hip/ops.py attn_fwd / attn_bwd) check it, and the element counts, before they launch.
  * Limits: head_dim == 64; 1 <= L <= UPP_ATTN_MAX_L, forward and backward alike; UPP_E_RANGE beyond (checked before the B == 0 return).
  * No atomics, no workspace, no memset at any L: two calls on the same inputs give the same bits. */
 #define UPP_ATTN_MAX_L 2048   /* the longest sequence the attention entry points serve (the longest one the test suite covers) */
