@@ -647,6 +647,106 @@ class Attention(nn.Module):
         return self.proj_drop(self.proj(x))
 
 
+class CrossAttention(nn.Module):
+    """models/Transformer.py:120-155 (and models/Transformer_utils.py:122): queries from one sequence, keys and values from another.
+    forward(q (B,Nq,dim), v (B,Nk,dim)) -> (B,Nq,out_dim).  State-dict keys: q_map, k_map, v_map, proj."""
+
+    def __init__(self, dim, out_dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_drop=0., proj_drop=0.):
+        super().__init__()
+        self.num_heads = num_heads
+        self.dim = dim
+        self.out_dim = out_dim
+        self.scale = qk_scale or (out_dim // num_heads) ** -0.5
+        self.q_map = nn.Linear(dim, out_dim, bias=qkv_bias)
+        self.k_map = nn.Linear(dim, out_dim, bias=qkv_bias)
+        self.v_map = nn.Linear(dim, out_dim, bias=qkv_bias)
+        self.attn_drop = nn.Dropout(attn_drop)
+        self.proj = nn.Linear(out_dim, out_dim)
+        self.proj_drop = nn.Dropout(proj_drop)
+
+    def fusable(self, q, v):
+        """The cross-attention kernels (csrc/attn_cross.hip) serve head_dim 64, both lengths <= HF.ATTN_MAX_L and no attention dropout."""
+        return (q.is_cuda and v.is_cuda and q.dtype == torch.float32 and v.dtype == torch.float32
+                and self.out_dim == 64 * self.num_heads and 1 <= q.shape[1] <= HF.ATTN_MAX_L and 1 <= v.shape[1] <= HF.ATTN_MAX_L
+                and not (self.training and self.attn_drop.p > 0))
+
+    def forward(self, q, v):
+        B, N, _ = q.shape
+        C, H, NK = self.out_dim, self.num_heads, v.shape[1]
+        if self.fusable(q, v):
+            ctx = HF.cross_attention(HF.linear(q, self.q_map.weight, self.q_map.bias), HF.linear(v, self.k_map.weight, self.k_map.bias),
+                                     HF.linear(v, self.v_map.weight, self.v_map.bias), H, self.scale)
+            return self.proj_drop(HF.linear(ctx, self.proj.weight, self.proj.bias))
+        if q.is_cuda:
+            HF.note_declined("CrossAttention (%d,%d) x (%d,%d), %d heads" % (N, self.dim, NK, self.dim, H),
+                             "head_dim != 64 / a length beyond %d / dtype / attention dropout" % HF.ATTN_MAX_L)
+        qh = self.q_map(q).view(B, N, H, C // H).permute(0, 2, 1, 3)
+        kh = self.k_map(v).view(B, NK, H, C // H).permute(0, 2, 1, 3)
+        vh = self.v_map(v).view(B, NK, H, C // H).permute(0, 2, 1, 3)
+        attn = self.attn_drop(((qh @ kh.transpose(-2, -1)) * self.scale).softmax(dim=-1))
+        x = (attn @ vh).transpose(1, 2).reshape(B, N, C)
+        return self.proj_drop(self.proj(x))
+
+
+class DecoderBlock(nn.Module):
+    """The PoinTr decoder block, models/Transformer.py:158-219: self-attention over the queries, cross-attention of the queries over the
+    proxies `v`, an MLP; each attention optionally merged with a local branch -- a max over 8 neighbours of
+    lrelu(Linear([f_j - f_i ; f_i])), i.e. the DGCNN grouper's edge convolution without a norm.
+    forward(q (B,Nq,dim), v (B,Nk,dim), self_knn_index, cross_knn_index): the indices are per-sample neighbour lists (B,Nq,8) (int32 or
+    int64, rows of q for the self branch, rows of v for the cross branch), not the reference's flat bs*k*np form with batch offsets.
+    State-dict keys: norm1, self_attn, norm_q, norm_v, attn, norm2, mlp, knn_map, merge_map, knn_map_cross, merge_map_cross."""
+
+    def __init__(self, dim, num_heads, dim_q=None, mlp_ratio=4., qkv_bias=False, qk_scale=None, drop=0., attn_drop=0., drop_path=0.,
+                 act_layer=nn.GELU, norm_layer=nn.LayerNorm):
+        super().__init__()
+        self.norm1 = norm_layer(dim)
+        self.self_attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale, attn_drop=attn_drop, proj_drop=drop)
+        dim_q = dim_q or dim
+        self.norm_q = norm_layer(dim_q)
+        self.norm_v = norm_layer(dim)
+        self.attn = CrossAttention(dim, dim, num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale, attn_drop=attn_drop, proj_drop=drop)
+        self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()
+        self.norm2 = norm_layer(dim)
+        self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
+        self.knn_map = nn.Sequential(nn.Linear(dim * 2, dim), nn.LeakyReLU(negative_slope=0.2))
+        self.merge_map = nn.Linear(dim * 2, dim)
+        self.knn_map_cross = nn.Sequential(nn.Linear(dim * 2, dim), nn.LeakyReLU(negative_slope=0.2))
+        self.merge_map_cross = nn.Linear(dim * 2, dim)
+
+    @staticmethod
+    def local_branch(knn_map, keys, queries, idx):
+        """max_k lrelu(W [f_j - f_i ; f_i] + b) over the listed neighbours f_j = keys[b, idx[b,i,k]] of every query f_i, as
+        W1 f_j + ((W2 - W1) f_i + b): two per-point products and HF.edge_conv_max without a norm (no (B,Nq,8,2*dim) tensor)."""
+        from upp_hip import torch_cpu
+        lin, act = knn_map[0], knn_map[1]
+        C = keys.shape[-1]
+        W = lin.weight
+        Wk, Wq = W[:, :C].contiguous(), W[:, C:] - W[:, :C]
+        idx = idx.long()
+        A, Bq = HF.linear(keys, Wk), HF.linear(queries, Wq, lin.bias)
+        if POOL_TRACE is None and HF.edge_conv_usable(A, Bq, idx):
+            return HF.edge_conv_max(A, Bq, idx, None, act.negative_slope)
+        if A.is_cuda and POOL_TRACE is None:
+            HF.note_declined("DecoderBlock edge_conv_max %s, k = %d" % (tuple(A.shape), idx.shape[2]), "outside the served range")
+        return torch_cpu.edge_conv_max(A, Bq, idx, None, act.negative_slope)
+
+    def forward(self, q, v, self_knn_index=None, cross_knn_index=None):
+        norm_q = HF.layer_norm(q, self.norm1)
+        q_1 = self.self_attn(norm_q)
+        if self_knn_index is not None:
+            knn_f = self.local_branch(self.knn_map, norm_q, norm_q, self_knn_index)
+            q_1 = HF.linear(torch.cat([q_1, knn_f], dim=-1), self.merge_map.weight, self.merge_map.bias)
+        q = q + self.drop_path(q_1)
+        norm_q = HF.layer_norm(q, self.norm_q)
+        norm_v = HF.layer_norm(v, self.norm_v)
+        q_2 = self.attn(norm_q, norm_v)
+        if cross_knn_index is not None:
+            knn_f = self.local_branch(self.knn_map_cross, norm_v, norm_q, cross_knn_index)
+            q_2 = HF.linear(torch.cat([q_2, knn_f], dim=-1), self.merge_map_cross.weight, self.merge_map_cross.bias)
+        q = q + self.drop_path(q_2)
+        return q + self.drop_path(self.mlp(HF.layer_norm(q, self.norm2)))
+
+
 class Adapter(nn.Module):
     """0.7 * ln2(drop(GELU(ln1(LayerNorm(x)))))  (models/Point_MAE_pretask_dev.py:54-104; the
     variant without the `scale` Linear is the one Block instantiates)."""

@@ -623,6 +623,48 @@ def attention(qkv, num_heads, scale):
     return _Attention.apply(qkv, int(num_heads), float(scale))
 
 
+class _CrossAttention(Function):
+    """ctx = softmax(q k^T * scale) v with q (B, Lq, H*64) and k, v (B, Lk, H*64) from two sequences; saves q, k, v, ctx and lse -- never
+    a (B, H, Lq, Lk) tensor.  No scatter-add: deterministic in every mode."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, num_heads, scale):
+        B, Lq, _ = q.shape
+        Lk = k.shape[1]
+        out, lse = ops.xattn_fwd(q, k, v, B, Lq, Lk, num_heads, scale)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.meta = (B, Lq, Lk, num_heads, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        q, k, v, out, lse = ctx.saved_tensors
+        B, Lq, Lk, H, scale = ctx.meta
+        d_q, d_k, d_v = ops.xattn_bwd(q, k, v, out, g.contiguous(), lse, B, Lq, Lk, H, scale)
+        return d_q, d_k, d_v, None, None
+
+
+def _xattn_view(t):
+    """t as upp_xattn_* can read it (ops._xattn_operand): kept when it is a 16-byte aligned row-strided view, else a contiguous copy"""
+    if t.dim() != 3:
+        raise ValueError("cross_attention: q, k and v must be (B, L, H * 64)")
+    B, L, C = t.shape
+    rs = t.stride(1) if L > 1 else (t.stride(0) if B > 1 else C)
+    ok = t.stride(2) == 1 and rs >= C and rs % 4 == 0 and (B <= 1 or t.stride(0) == L * rs) and t.data_ptr() % 16 == 0
+    return t if ok else t.contiguous()
+
+
+def cross_attention(q, k, v, num_heads, scale):
+    """softmax(q k^T scale) v per head with queries and keys from two sequences (reference models/Transformer.py CrossAttention):
+    q (B, Lq, H*64), k and v (B, Lk, H*64) -> (B, Lq, H*64), on the streaming FP32-MFMA kernels of csrc/attn_cross.hip, head_dim 64,
+    1 <= Lq, Lk <= ATTN_MAX_L (HIP tensors outside that raise).  q, k, v may be row-strided views (slices of a packed product).
+    Deterministic.  CPU tensors take the torch formulation when upp_hip.torch_cpu is enabled."""
+    if _torch_cpu(q, k, v):
+        from . import torch_cpu
+        return torch_cpu.cross_attention(q, k, v, num_heads, scale)
+    return _CrossAttention.apply(_xattn_view(q), _xattn_view(k), _xattn_view(v), int(num_heads), float(scale))
+
+
 # ------------------------------------------------------------------ deferred parameter-gradient sums
 class _DeferredSums:
     """Parameter gradients that are sums of partial results (adapter weights, LayerNorm gamma/beta, prompts) are not read

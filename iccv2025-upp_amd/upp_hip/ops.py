@@ -1376,6 +1376,85 @@ def attn_bwd(qkv, ctx, d_ctx, lse, B, L, H, scale):
     return d_qkv
 
 
+def _xattn_operand(t, name, B, L, H):
+    """One strided operand of upp_xattn_fwd / _bwd: float32 (B, L, H * 64) whose last dimension is contiguous, whose row stride rs is a
+    multiple of 4 and >= H * 64, whose sample stride is L * rs, 16-byte aligned -> rs.  (The device is checked after every operand's layout, by
+    _xattn_device, so that the layout rules can be tested on a host without one.)"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{name} must be torch.float32, got {t.dtype}")
+    if t.dim() != 3 or t.shape[0] != B or t.shape[1] != L:
+        raise RuntimeError(f"{name} must be (B, L, H * 64) = ({B}, {L}, {H * 64}), got {tuple(t.shape)}")
+    if t.shape[2] != H * 64:
+        raise RuntimeError(f"{name}: the cross-attention kernels serve head_dim 64 only (last dimension {H * 64} for {H} heads), got {t.shape[2]}")
+    if t.stride(2) != 1:
+        raise RuntimeError(f"{name}: the last dimension must be contiguous, got strides {tuple(t.stride())}")
+    rs = t.stride(1) if L > 1 else (t.stride(0) if B > 1 else H * 64)
+    if rs < H * 64 or rs % 4:
+        raise RuntimeError(f"{name}: the row stride must be a multiple of 4 floats and at least H * 64 = {H * 64}, got {rs}")
+    if B > 1 and t.stride(0) != L * rs:
+        raise RuntimeError(f"{name}: the sample stride must be L * row stride = {L * rs}, got {t.stride(0)}")
+    if t.data_ptr() % 16:
+        raise RuntimeError(f"{name} must be 16-byte aligned (the attention kernels load 16-byte pieces); got a view at a storage offset")
+    return rs
+
+
+def _xattn_device(**tensors):
+    for name, t in tensors.items():
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must be a HIP (cuda) tensor; upp_hip has no CPU path")
+    _same_device(*tensors.values())
+
+
+def _xattn_lengths(B, Lq, Lk, H):
+    B, Lq, Lk, H = int(B), int(Lq), int(Lk), int(H)
+    if B < 0 or H < 1 or Lq < 1 or Lk < 1:
+        raise RuntimeError(f"cross-attention needs B >= 0, H >= 1 and lengths >= 1, got B = {B}, H = {H}, Lq = {Lq}, Lk = {Lk}")
+    if Lq > ATTN_MAX_L or Lk > ATTN_MAX_L:
+        raise RuntimeError(f"cross-attention serves lengths up to ATTN_MAX_L = {ATTN_MAX_L}, got Lq = {Lq}, Lk = {Lk}")
+    return B, Lq, Lk, H
+
+
+def xattn_fwd(q, k, v, B, Lq, Lk, H, scale):
+    """softmax(q k^T scale) v with queries and keys from two sequences (csrc/attn_cross.hip): q (B, Lq, H * 64), k and v (B, Lk, H * 64)
+    -> ctx (B, Lq, H * 64), lse (B, H, Lq), both dense.  The operands may be views (a slice of a packed [k|v] or qkv product): see
+    _xattn_operand for the stride rule; the strides are taken from the tensors.  1 <= Lq, Lk <= ATTN_MAX_L; everything else raises
+    before a launch."""
+    B, Lq, Lk, H = _xattn_lengths(B, Lq, Lk, H)
+    q_rs = _xattn_operand(q, "q", B, Lq, H)
+    k_rs = _xattn_operand(k, "k", B, Lk, H)
+    v_rs = _xattn_operand(v, "v", B, Lk, H)
+    _xattn_device(q=q, k=k, v=v)
+    ctx = torch.empty((B, Lq, H * 64), dtype=torch.float32, device=q.device)
+    lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
+    _call(q.device, "upp_xattn_fwd", _abi.ptr(q), _abi.ptr(k), _abi.ptr(v), _abi.ptr(ctx), _abi.ptr(lse), B, Lq, Lk, H, 64, q_rs, k_rs, v_rs,
+          float(scale))
+    return ctx, lse
+
+
+def xattn_bwd(q, k, v, ctx, d_ctx, lse, B, Lq, Lk, H, scale):
+    """-> (d_q (B, Lq, H * 64), d_k, d_v (B, Lk, H * 64)) from d_ctx and the forward's ctx / lse.  q, k, v as in xattn_fwd; ctx, d_ctx and
+    lse dense.  The three gradients are fresh dense tensors (so they overlap nothing), every element written by exactly one workgroup: no
+    atomics, two calls give the same bits."""
+    B, Lq, Lk, H = _xattn_lengths(B, Lq, Lk, H)
+    q_rs = _xattn_operand(q, "q", B, Lq, H)
+    k_rs = _xattn_operand(k, "k", B, Lk, H)
+    v_rs = _xattn_operand(v, "v", B, Lk, H)
+    for t, name, count, aligned in ((ctx, "ctx", B * Lq * H * 64, True), (d_ctx, "d_ctx", B * Lq * H * 64, True), (lse, "lse", B * H * Lq, False)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != count:
+            raise RuntimeError(f"{name} must be a dense float32 tensor of {count} elements")
+        if aligned and t.data_ptr() % 16:
+            raise RuntimeError(f"{name} must be 16-byte aligned (the attention kernels load 16-byte pieces); got a view at a storage offset")
+    _xattn_device(q=q, k=k, v=v, ctx=ctx, d_ctx=d_ctx, lse=lse)
+    d_q = torch.empty((B, Lq, H * 64), dtype=torch.float32, device=q.device)
+    d_k = torch.empty((B, Lk, H * 64), dtype=torch.float32, device=q.device)
+    d_v = torch.empty((B, Lk, H * 64), dtype=torch.float32, device=q.device)
+    _call(q.device, "upp_xattn_bwd", _abi.ptr(q), _abi.ptr(k), _abi.ptr(v), _abi.ptr(ctx), _abi.ptr(d_ctx), _abi.ptr(lse), _abi.ptr(d_q),
+          _abi.ptr(d_k), _abi.ptr(d_v), B, Lq, Lk, H, 64, q_rs, k_rs, v_rs, H * 64, H * 64, H * 64, float(scale))
+    return d_q, d_k, d_v
+
+
 # ------------------------------------------------------------------ prompt propagation
 def prop_pool_fwd(X, i1, u, keep, groups):
     D = X.shape[-1]

@@ -190,6 +190,20 @@ def edge_conv_max(A, Bq, idx, norm=None, slope=0.2):
     return F.leaky_relu(y, float(slope)).max(dim=2)[0]
 
 
+def cross_attention(q, k, v, num_heads, scale):
+    """The cross-attention core of include/upp_hip.h "cross-attention" as torch operators (any device, any head_dim; differentiable):
+    q (B,Lq,C), k and v (B,Lk,C) -> (B,Lq,C) = softmax(q k^T scale) v per head (reference models/Transformer.py:148-152).  It keeps the
+    (B,H,Lq,Lk) tensor the kernels avoid."""
+    B, Lq, C = q.shape
+    Lk = k.shape[1]
+    H = int(num_heads)
+    qh = q.reshape(B, Lq, H, C // H).permute(0, 2, 1, 3)
+    kh = k.reshape(B, Lk, H, C // H).permute(0, 2, 1, 3)
+    vh = v.reshape(B, Lk, H, C // H).permute(0, 2, 1, 3)
+    attn = ((qh @ kh.transpose(-2, -1)) * scale).softmax(dim=-1)
+    return (attn @ vh).transpose(1, 2).reshape(B, Lq, C)
+
+
 def chamfer(xyz1, xyz2):
     """-> (dist1 (B,N), dist2 (B,M)) squared nearest-neighbour distances, differentiable (reference extensions/chamfer_dist)."""
     d = ((xyz1.unsqueeze(2) - xyz2.unsqueeze(1)) ** 2).sum(-1)

@@ -468,6 +468,30 @@ int upp_attn_bwd(const float *qkv, const float *ctx, const float *d_ctx, const f
                  int B, int L, int H, int head_dim, float scale, void *stream);
 /* (L <= 96: the register-resident 16x16x4 MFMA kernels of attn_flash16.hip; L <= 160: attn_long.hip, K and V resident in the LDS;
  *  L <= UPP_ATTN_MAX_L: attn_stream.hip, 64-row query blocks against K / V streamed in 64-key blocks, online softmax) */
+/* ---- cross-attention: queries and keys from two sequences -----------------------------------
+ * softmax(q k^T * scale) v of CrossAttention.forward (reference models/Transformer.py:148-152) and its autograd; csrc/attn_cross.hip,
+ * one streaming family (the structure and the summation order of attn_stream.hip) for every length in the range.
+ *   q, d_q            (B, Lq, rs) arrays: head h lives in columns [64h, 64h+64) counted from the pointer
+ *   k, v, d_k, d_v    (B, Lk, rs) arrays with the same head layout
+ *   *_rs              the row strides in floats, one per array; the sample stride of an array is L * rs.  This admits three separate
+ *                     Linear outputs (rs = H*64), a packed [k|v] product (rs = 2*H*64, v = k + H*64) and views into a packed qkv
+ *                     (rs = 3*H*64).
+ *   ctx, d_ctx        dense (B, Lq, H*64);  lse dense (B, H, Lq)
+ * Checked before any launch -- UPP_E_BADARG: a null pointer, B < 0, a length < 1, H < 1, a stride < H*64 or not a multiple of 4;
+ * UPP_E_RANGE: head_dim != 64 or a length > UPP_ATTN_MAX_L (before the B == 0 return, as upp_attn_fwd).
+ * The caller's duties: every base 16-byte aligned (the kernels load 16-byte pieces), and d_q, d_k, d_v not overlapping each other or an
+ * input (they may interleave, e.g. as views of one packed buffer).  The torch operators (upp_hip/ops.py xattn_fwd / xattn_bwd) check both.
+ * Every output element is written by exactly one workgroup: no atomics, no workspace, no memset; two calls give the same bits.  Keys
+ * >= Lk contribute exactly 0; rows >= Lq / Lk of an array are never read and never written.  With Lk <= 64 the softmax-backward row
+ * sum is taken over the key block's own P dP (so a single key gives d_q = d_k = 0 exactly), otherwise it is sum_c d_ctx ctx. */
+int upp_xattn_fwd(const float *q, const float *k, const float *v, float *ctx, float *lse,
+                  int B, int Lq, int Lk, int H, int head_dim,
+                  long long q_rs, long long k_rs, long long v_rs, float scale, void *stream);
+int upp_xattn_bwd(const float *q, const float *k, const float *v, const float *ctx, const float *d_ctx, const float *lse,
+                  float *d_q, float *d_k, float *d_v,
+                  int B, int Lq, int Lk, int H, int head_dim,
+                  long long q_rs, long long k_rs, long long v_rs,
+                  long long dq_rs, long long dk_rs, long long dv_rs, float scale, void *stream);
 /* ---- prompt propagation (Block.forward, reference models/Point_MAE_pretask_dev.py:275-303) ----
  * X (rows, D): the block's token matrix viewed as rows = B*L' rows [cls | prompts | T centre tokens] per sample.
  * Index arguments are ABSOLUTE row numbers of X (the host converts the reference's flat / per-sample index
