@@ -4,3 +4,4 @@ from . import Point_MAE_unify  # noqa: F401  (registers Point_MAE_unify)
 from . import Point_MAE_unify_segment  # noqa: F401,E402  (registers Point_MAE_unify_seg)
 from . import Point_MAE  # noqa: F401,E402  (registers Point_MAE)
 from . import Point_MAE_pretask_dev  # noqa: F401,E402  (registers Point_MAE_pretask_dev)
+from . import PoinTr  # noqa: F401,E402  (registers PoinTr)

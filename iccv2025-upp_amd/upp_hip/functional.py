@@ -459,6 +459,94 @@ def edge_conv_max(A, Bq, idx, norm=None, slope=0.2, deterministic=None):
                               None if deterministic is None else bool(deterministic))
 
 
+# ------------------------------------------------------------------ broadcast expand (README "The PoinTr completion model")
+class _ExpandAct(Function):
+    """lrelu(BatchNorm(P[r] + Wu U[., s])) as one node (include/upp_hip.h "broadcast expand"): saves P, U, Wu and the (O,) statistics --
+    never an (R,S,O) tensor besides the output's own gradient.  Returns (h, mean, var); mean and the biased var are the batch statistics
+    in training mode (for the running buffers; not differentiable) and None otherwise."""
+
+    @staticmethod
+    def forward(ctx, P, U, Wu, gamma, beta, mean, rstd, mode, eps, slope):
+        h, mean, var, rstd = ops.expand_fwd(P, U, Wu, gamma, beta, mean, rstd, mode, eps, slope)
+        ctx.save_for_backward(P, U, Wu, gamma, beta, mean, rstd)
+        ctx.cfg = (mode, slope)
+        if mode == ops.EXPAND_TRAIN:
+            ctx.mark_non_differentiable(mean, var)
+            return h, mean, var
+        return h, None, None
+
+    @staticmethod
+    def backward(ctx, g_h, _g_mean, _g_var):
+        P, U, Wu, gamma, beta, mean, rstd = ctx.saved_tensors
+        mode, slope = ctx.cfg
+        need = ctx.needs_input_grad
+        g_P, g_U, g_Wu, g_gamma, g_beta = ops.expand_bwd(g_h.contiguous(), P, U, Wu, gamma, beta, mean, rstd, mode, slope, want_gU=need[1])
+        return (g_P if need[0] else None, g_U, g_Wu if need[2] else None, g_gamma if mode and need[3] else None,
+                g_beta if mode and need[4] else None, None, None, None, None, None)
+
+
+def _expand_norm(norm):
+    if norm is None:
+        return None
+    if not isinstance(norm, torch.nn.BatchNorm1d) or norm.weight is None:
+        raise ValueError("expand_act: norm must be None or an affine torch.nn.BatchNorm1d")
+    return norm
+
+
+def expand_usable(P, U, Wu, norm=None):
+    """Do the fused kernels serve these operands (HIP f32 tensors of the served sizes: 1 <= J <= 4, 1 <= O <= 1024, R S O < 2^31)?"""
+    ts = [P, U, Wu] + ([norm.weight, norm.bias] if norm is not None else [])
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 for t in ts):
+        return False
+    if P.dim() != 2 or Wu.dim() != 2 or U.dim() not in (2, 3) or U.shape[-1] != Wu.shape[1] or Wu.shape[0] != P.shape[1]:
+        return False
+    return ops.expand_usable(P.shape[0], U.shape[-2], P.shape[1], Wu.shape[1])
+
+
+def expand_act(P, U, Wu, norm=None, slope=0.0):
+    """P (R,O) the per-row product (bias included), U (S,J) shared or (R,S,J) per row, Wu (O,J) -> h (R,S,O) =
+    leaky_relu(norm(P[r] + Wu U[., s]), slope): a 1x1 conv over [u ; f repeated along s] with W = [Wu | Wf], P = Wf f + b, without the
+    concatenation or the pre-norm tensor.  norm: None or an affine torch.nn.BatchNorm1d -- batch statistics in training mode (the running
+    buffers are updated as torch does, with element-wise launches only: capturable), the running statistics in eval mode.  A shared U
+    that requires a gradient raises.  HIP tensors outside the served range take the torch formulation (note_declined records it); CPU
+    tensors take it when upp_hip.torch_cpu is enabled."""
+    if not 0.0 <= float(slope) <= 1.0:
+        raise ValueError("expand_act: slope must be in [0, 1]")
+    norm = _expand_norm(norm)
+    if U.dim() == 2 and U.requires_grad and torch.is_grad_enabled():
+        raise ValueError("expand_act: a shared U (S, J) that requires a gradient is not served; pass it per row (R, S, J)")
+    from . import torch_cpu
+    if _torch_cpu(P, U, Wu):
+        return torch_cpu.expand_act(P, U, Wu, norm, slope)
+    if P.is_cuda and not expand_usable(P, U, Wu, norm):
+        note_declined("expand_act P %s, U %s" % (tuple(P.shape), tuple(U.shape)), "outside the served range")
+        return torch_cpu.expand_act(P, U, Wu, norm, slope)
+    P, U, Wu = P.contiguous(), U.contiguous(), Wu.contiguous()
+    if norm is None:
+        return _ExpandAct.apply(P, U, Wu, None, None, None, None, ops.EXPAND_NONE, 1e-5, float(slope))[0]
+    gamma, beta = norm.weight.contiguous(), norm.bias.contiguous()
+    if norm.training or norm.running_mean is None:
+        n = P.shape[0] * U.shape[-2]
+        if n == 1:
+            raise ValueError("Expected more than 1 value per channel when training, got input size %s" % ((P.shape[0], U.shape[-2], P.shape[1]),))
+        h, mean, var = _ExpandAct.apply(P, U, Wu, gamma, beta, None, None, ops.EXPAND_TRAIN, float(norm.eps), float(slope))
+        if norm.training and norm.running_mean is not None:
+            with torch.no_grad():
+                norm.num_batches_tracked.add_(1)
+                if norm.momentum is None:                                 # the cumulative average: 1 / count, formed on the device
+                    f = norm.num_batches_tracked.to(torch.float32).reciprocal()
+                    norm.running_mean.add_((mean - norm.running_mean) * f)
+                    norm.running_var.add_((var * (n / (n - 1.0)) - norm.running_var) * f)
+                else:
+                    m = float(norm.momentum)
+                    norm.running_mean.mul_(1.0 - m).add_(mean, alpha=m)
+                    norm.running_var.mul_(1.0 - m).add_(var, alpha=m * n / (n - 1.0))
+        return h
+    with torch.no_grad():
+        rstd = torch.rsqrt(norm.running_var + norm.eps)
+    return _ExpandAct.apply(P, U, Wu, gamma, beta, norm.running_mean, rstd, ops.EXPAND_EVAL, float(norm.eps), float(slope))[0]
+
+
 class QueryAndGroup(torch.nn.Module):
     """pointnet2_utils.QueryAndGroup: ball query around new_xyz, then the grouped coordinates (centre subtracted) and / or features.
     forward(xyz (B,N,3), new_xyz (B,P,3), features (B,C,N) | None) -> (B, 3+C, P, S) | (B, C, P, S) with use_xyz=False | (B, 3, P, S)

@@ -593,6 +593,91 @@ def edge_conv_bwd(g_out, A, Bq, idx, arg, gamma=None, beta=None, mean=None, rstd
     return g_A, g_Bq, g_gamma, g_beta
 
 
+# ------------------------------------------------------------------ broadcast expand (include/upp_hip.h "broadcast expand")
+EXPAND_MAX_J, EXPAND_MAX_O = 4, 1024
+EXPAND_NONE, EXPAND_TRAIN, EXPAND_EVAL = 0, 1, 2
+
+
+def expand_usable(R, S, O, J):
+    """The served range of upp_expand_fwd / _bwd (sizes only)."""
+    return 1 <= J <= EXPAND_MAX_J and 1 <= O <= EXPAND_MAX_O and S >= 1 and R >= 1 and R * S * O < 2 ** 31
+
+
+def _expand_args(P, U, Wu, gamma, beta, mean, rstd, mode, slope, stats_given):
+    _need(P, "P", torch.float32, 2)
+    _need(Wu, "Wu", torch.float32, 2)
+    _need(U, "U", torch.float32)
+    _same_device(P, U, Wu)
+    R, O = P.shape
+    J = Wu.shape[1]
+    if U.dim() not in (2, 3) or U.shape[-1] != J or Wu.shape[0] != O or (U.dim() == 3 and U.shape[0] != R):
+        raise RuntimeError("expand: P (R, O), U (S, J) or (R, S, J) and Wu (O, J) do not fit together")
+    S = U.shape[-2]
+    mode = int(mode)
+    if mode not in (EXPAND_NONE, EXPAND_TRAIN, EXPAND_EVAL):
+        raise ValueError("expand: mode must be 0 (no norm), 1 (training norm) or 2 (eval norm)")
+    if not 0.0 <= float(slope) <= 1.0:
+        raise ValueError("expand: slope must be in [0, 1]")
+    if J > EXPAND_MAX_J or J < 1:
+        raise RuntimeError("expand: 1 <= J <= %d is served, got J = %d" % (EXPAND_MAX_J, J))
+    if O > EXPAND_MAX_O or O < 1:
+        raise RuntimeError("expand: 1 <= O <= %d is served, got O = %d" % (EXPAND_MAX_O, O))
+    if R < 1 or S < 1 or R * S * O >= 2 ** 31:
+        raise RuntimeError("expand: R >= 1, S >= 1 and R S O < 2^31 are served, got R = %d, S = %d, O = %d" % (R, S, O))
+    if mode:
+        _need(gamma, "gamma", torch.float32, 1, O)
+        _need(beta, "beta", torch.float32, 1, O)
+        _same_device(P, gamma, beta)
+        if stats_given:
+            _need(mean, "mean", torch.float32, 1, O)
+            _need(rstd, "rstd", torch.float32, 1, O)
+            _same_device(P, mean, rstd)
+    return R, S, O, J, mode, int(U.dim() == 3)
+
+
+def _expand_work(P, R, S, O):
+    return torch.empty(int(_abi.load().upp_expand_work_floats(R, S, O)), dtype=torch.float32, device=P.device)
+
+
+def expand_fwd(P, U, Wu, gamma=None, beta=None, mean=None, rstd=None, mode=0, eps=1e-5, slope=0.0):
+    """P (R,O), U (S,J) | (R,S,J), Wu (O,J) -> h (R,S,O) = lrelu(norm(P[r] + Wu U[.,s])), mean, var, rstd (O,) | None.  mode 0: no norm;
+    1: batch statistics (mean, biased var, rstd are computed and returned); 2: the given mean / rstd.  y is never stored."""
+    R, S, O, J, mode, per_row = _expand_args(P, U, Wu, gamma, beta, mean, rstd, mode, slope, mode == EXPAND_EVAL)
+    if mode == EXPAND_TRAIN and R * S == 1:
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % ((R, S, O),))
+    h = torch.empty((R, S, O), dtype=torch.float32, device=P.device)
+    var = work = None
+    if mode == EXPAND_TRAIN:
+        mean, var, rstd = (torch.empty((O,), dtype=torch.float32, device=P.device) for _ in range(3))
+        work = _expand_work(P, R, S, O)
+    _call(P.device, "upp_expand_fwd", _abi.ptr(P), _abi.ptr(U), per_row, _abi.ptr(Wu), _abi.ptr(gamma if mode else None),
+          _abi.ptr(beta if mode else None), float(eps), float(slope), mode, _abi.ptr(h), _abi.ptr(mean if mode else None), _abi.ptr(var),
+          _abi.ptr(rstd if mode else None), _abi.ptr(work), R, S, O, J)
+    return h, (mean if mode else None), var, (rstd if mode else None)
+
+
+def expand_bwd(g_h, P, U, Wu, gamma=None, beta=None, mean=None, rstd=None, mode=0, slope=0.0, want_gU=True):
+    """-> g_P (R,O), g_U (R,S,J) | None (a shared U, or not wanted), g_Wu (O,J), g_gamma (O,) | None, g_beta (O,) | None: every sum in a
+    fixed order, nothing zeroed, g_y never stored."""
+    R, S, O, J, mode, per_row = _expand_args(P, U, Wu, gamma, beta, mean, rstd, mode, slope, True)
+    _need(g_h, "g_h", torch.float32, 3)
+    _same_device(P, g_h)
+    if tuple(g_h.shape) != (R, S, O):
+        raise RuntimeError("expand_bwd: g_h must be (R, S, O)")
+    if want_gU and not per_row:
+        raise RuntimeError("expand_bwd: a shared U (S, J) has no gradient here")
+    g_P = torch.empty((R, O), dtype=torch.float32, device=P.device)
+    g_U = torch.empty((R, S, J), dtype=torch.float32, device=P.device) if want_gU else None
+    g_Wu = torch.empty((O, J), dtype=torch.float32, device=P.device)
+    g_gamma = torch.empty((O,), dtype=torch.float32, device=P.device) if mode else None
+    g_beta = torch.empty((O,), dtype=torch.float32, device=P.device) if mode else None
+    work = _expand_work(P, R, S, O)
+    _call(P.device, "upp_expand_bwd", _abi.ptr(g_h), _abi.ptr(P), _abi.ptr(U), per_row, _abi.ptr(Wu), _abi.ptr(gamma if mode else None),
+          _abi.ptr(beta if mode else None), _abi.ptr(mean if mode else None), _abi.ptr(rstd if mode else None), float(slope), mode,
+          _abi.ptr(g_P), _abi.ptr(g_U), _abi.ptr(g_Wu), _abi.ptr(g_gamma), _abi.ptr(g_beta), _abi.ptr(work), R, S, O, J)
+    return g_P, g_U, g_Wu, g_gamma, g_beta
+
+
 # ------------------------------------------------------------------ Chamfer
 def chamfer_fwd(xyz1, xyz2):
     _need(xyz1, "xyz1", torch.float32, 3, 3)

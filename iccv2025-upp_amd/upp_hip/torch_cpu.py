@@ -190,6 +190,19 @@ def edge_conv_max(A, Bq, idx, norm=None, slope=0.2):
     return F.leaky_relu(y, float(slope)).max(dim=2)[0]
 
 
+def expand_act(P, U, Wu, norm=None, slope=0.0):
+    """The operator of include/upp_hip.h "broadcast expand" as torch operators (any device and dtype; differentiable): P (R,O), U (S,J)
+    shared or (R,S,J) per row, Wu (O,J), norm None | an affine torch.nn.BatchNorm1d (its own training flag and running buffers, updated as
+    torch does) -> (R,S,O) = leaky_relu(norm(P[r] + Wu U[., s]), slope).  It stores the y (R,S,O) the kernels avoid."""
+    import torch.nn.functional as F
+    R, O = P.shape
+    S = U.shape[-2]
+    y = P.unsqueeze(1) + torch.matmul(U, Wu.t())                   # (R,1,O) + (S,O) | (R,S,O)
+    if norm is not None:
+        y = norm(y.reshape(R * S, O)).view(R, S, O)
+    return F.leaky_relu(y, float(slope))
+
+
 def cross_attention(q, k, v, num_heads, scale):
     """The cross-attention core of include/upp_hip.h "cross-attention" as torch operators (any device, any head_dim; differentiable):
     q (B,Lq,C), k and v (B,Lk,C) -> (B,Lq,C) = softmax(q k^T scale) v per head (reference models/Transformer.py:148-152).  It keeps the

@@ -294,6 +294,48 @@ int upp_edge_conv_bwd(const float *g_out, const float *A, const float *Bq, const
                       float *g_A, float *g_Bq, float *g_gamma, float *g_beta, float *work, float *g_y,
                       int B, int Nk, int Nq, int K, int O, void *stream);
 
+/* ---- broadcast expand: a 1x1 conv over [u ; f repeated], BatchNorm, LeakyReLU ---------------------------------
+ * Three layers of the reference's PoinTr multiply a concatenation in which one part is constant along an axis: Fold.folding1[0] and
+ * folding2[0] (models/PoinTr.py:27-58, conv over [seed | fd1 ; feature repeated S times]) and PCTransformer.mlp_query[0]
+ * (models/Transformer.py:324-332,413-416, conv over [global feature repeated M times ; coarse point]).  With W = [Wu | Wf] the conv is
+ * (Wf f_r + b) + Wu u[r,s]: one per-ROW product the CALLER makes with upp_linear_*; these entry points take the product:
+ *   P   (R,O) f32   the per-row product, bias included
+ *   U   per_row != 0: (R,S,J) f32, one per row;   per_row == 0: (S,J) f32, shared by all rows
+ *   Wu  (O,J) f32,  1 <= J <= 4
+ *   mode 0: no norm (gamma, beta, mean, rstd, var, work may be NULL in the forward);
+ *        1: an affine BatchNorm1d in training mode -- mean, var (biased), rstd (O,) are OUTPUTS of the forward;
+ *        2: the same norm in eval mode -- mean and rstd (O,) are INPUTS (the caller's running mean and 1 / sqrt(running var + eps))
+ *   slope: LeakyReLU, 0 <= slope <= 1 (0: ReLU)
+ * Rules.  t = U[.,s,0] * Wu[o,0], then t = fma(U[.,s,j], Wu[o,j], t) for ascending j;  y[r,s,o] = P[r,o] + t, one f32 addition.  y is
+ *   never stored.  Mode 1: per channel the mean and BIASED variance of y over all R S values, rstd = 1 / sqrt(var + eps), in a fixed
+ *   order: (mean, M2) partials per block of rows and channel -- a block is max(1, 256 / S) whole rows; the partial is the block's sum
+ *   over its count, kept as a mean so that a constant channel's mean is that constant exactly and its variance 0 -- from sums shifted by
+ *   the block's first value, combined in f64 (Chan: mean = sum n_i m_i / N, M2 = sum [M2_i + n_i (m_i - mean)^2]); no atomics.
+ *   z = ((y - mean) * rstd) * gamma + beta (four f32 operations, none contracted; mode 0: z = y);  h = z > 0 ? z : z * slope.
+ *   -> h (R,S,O) f32.  Every element is written by a kernel; 3 launches in mode 1, 1 otherwise.
+ * Backward, from g_h (R,S,O), with y and xhat = (y - mean) * rstd recomputed from P, U, Wu and the (O,) statistics:
+ *   g_z = g_h * (z > 0 ? 1 : slope);   mode 1: m1 = mean(g_z), m2 = mean(g_z xhat), g_y = (rstd * gamma) * ((g_z - m1) - xhat * m2);
+ *   mode 2: g_y = (rstd * gamma) * g_z;   mode 0: g_y = g_z.  g_y is never stored.
+ *   g_P[r,o] = sum_s g_y;   g_U[r,s,j] = sum_o g_y Wu[o,j] (per-row U only; g_U may be NULL: not computed);
+ *   g_Wu[o,j] = sum_{r,s} g_y U[.,s,j];   g_gamma[o] = sum g_z xhat,  g_beta[o] = sum g_z  (modes 1 and 2).
+ *   Every sum has a fixed order and every output element is written by exactly one workgroup: sums over s in registers and across the
+ *   workgroup's four wavefronts in wavefront order, sums over o by a fixed lane tree, sums over rows from per-block partials in `work`,
+ *   added in f64 by a fixed tree.  No atomics, nothing is zeroed: bit-identical from call to call, in either library mode.
+ *   4 launches in modes 1 and 2, 2 in mode 0.
+ *   work: upp_expand_work_floats(R, S, O) floats (a host function; 0 for a non-positive size): the forward needs it in mode 1, the
+ *   backward always.
+ * Limits: 1 <= J <= 4, 1 <= O <= 1024, S >= 1, R >= 1, R S O < 2^31 -- UPP_E_RANGE beyond.  A null pointer, a non-positive size, an
+ *   unknown mode, eps < 0, a slope outside [0, 1] (NaN included), g_U with a shared U: UPP_E_BADARG.  Both before any launch.  16-byte
+ *   loads and stores are used when O is a multiple of 4 and the f32 arrays of O-sized rows are 16-byte aligned; the results do not
+ *   depend on it. */
+long long upp_expand_work_floats(int R, int S, int O);
+int upp_expand_fwd(const float *P, const float *U, int per_row, const float *Wu, const float *gamma, const float *beta, float eps,
+                   float slope, int mode, float *h, float *mean, float *var, float *rstd, float *work,
+                   int R, int S, int O, int J, void *stream);
+int upp_expand_bwd(const float *g_h, const float *P, const float *U, int per_row, const float *Wu, const float *gamma, const float *beta,
+                   const float *mean, const float *rstd, float slope, int mode, float *g_P, float *g_U, float *g_Wu, float *g_gamma,
+                   float *g_beta, float *work, int R, int S, int O, int J, void *stream);
+
 /* ---- Chamfer distance ----------------------------------------------------------
  * Replaces chamfer.forward / chamfer.backward (reference
  * extensions/chamfer_dist/chamfer_cuda.cpp:36-39, kernels chamfer.cu:15-145 and
