@@ -81,6 +81,8 @@ SIGNATURES = {
     "upp_attn_bwd": (_c_i, [_c_f] * 5 + [_c_i] * 4 + [ctypes.c_float, _c_f]),
     "upp_xattn_fwd": (_c_i, [_c_f] * 5 + [_c_i] * 5 + [ctypes.c_longlong] * 3 + [ctypes.c_float, _c_f]),
     "upp_xattn_bwd": (_c_i, [_c_f] * 9 + [_c_i] * 5 + [ctypes.c_longlong] * 6 + [ctypes.c_float, _c_f]),
+    "upp_xattn_prefix_fwd": (_c_i, [_c_f] * 5 + [_c_i] * 5 + [ctypes.c_longlong] * 3 + [ctypes.c_float, _c_i, _c_i, _c_f]),
+    "upp_xattn_prefix_bwd": (_c_i, [_c_f] * 9 + [_c_i] * 5 + [ctypes.c_longlong] * 6 + [ctypes.c_float, _c_i, _c_i, _c_f]),
     "upp_prop_pool_fwd": (_c_i, [_c_f] * 3 + [ctypes.c_float] + [_c_f] * 2 + [_c_i] * 2 + [_c_f]),
     "upp_prop_pool_bwd": (_c_i, [_c_f] * 4 + [ctypes.c_float] + [_c_f] + [_c_i] * 3 + [_c_f]),
     "upp_prop_interp_fwd": (_c_i, [_c_f] * 6 + [_c_i] * 5 + [_c_f]),

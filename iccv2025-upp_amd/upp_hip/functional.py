@@ -753,6 +753,39 @@ def cross_attention(q, k, v, num_heads, scale):
     return _CrossAttention.apply(_xattn_view(q), _xattn_view(k), _xattn_view(v), int(num_heads), float(scale))
 
 
+class _PrefixAttention(Function):
+    """_CrossAttention under the prefix-visibility mask (csrc/attn_prefix.hip); saves q, k, v, ctx and lse -- never an (L, L) tensor, mask
+    included.  No scatter-add: deterministic in every mode."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, num_heads, scale, split_q, split_k):
+        B, Lq, _ = q.shape
+        Lk = k.shape[1]
+        out, lse = ops.xattn_prefix_fwd(q, k, v, B, Lq, Lk, num_heads, scale, split_q, split_k)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.meta = (B, Lq, Lk, num_heads, scale, split_q, split_k)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        q, k, v, out, lse = ctx.saved_tensors
+        B, Lq, Lk, H, scale, split_q, split_k = ctx.meta
+        d_q, d_k, d_v = ops.xattn_prefix_bwd(q, k, v, out, g.contiguous(), lse, B, Lq, Lk, H, scale, split_q, split_k)
+        return d_q, d_k, d_v, None, None, None, None
+
+
+def prefix_attention(q, k, v, num_heads, scale, split_q, split_k):
+    """cross_attention in which query rows < split_q see only the keys < split_k and the other rows see every key: the masked
+    self-attention of AdaPoinTr's decoder over [real queries ; D denoising queries] (reference models/AdaPoinTr.py:217-229) with q, k, v
+    the three views of one packed qkv and both splits L - D.  A hidden key's probability is exactly 0.  Shapes, views, range and
+    determinism as cross_attention; 0 <= split_q <= Lq, 1 <= split_k <= Lk.  CPU tensors take the torch formulation when upp_hip.torch_cpu
+    is enabled."""
+    if _torch_cpu(q, k, v):
+        from . import torch_cpu
+        return torch_cpu.prefix_attention(q, k, v, num_heads, scale, split_q, split_k)
+    return _PrefixAttention.apply(_xattn_view(q), _xattn_view(k), _xattn_view(v), int(num_heads), float(scale), int(split_q), int(split_k))
+
+
 # ------------------------------------------------------------------ deferred parameter-gradient sums
 class _DeferredSums:
     """Parameter gradients that are sums of partial results (adapter weights, LayerNorm gamma/beta, prompts) are not read

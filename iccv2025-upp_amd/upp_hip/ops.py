@@ -1501,6 +1501,15 @@ def _xattn_lengths(B, Lq, Lk, H):
     return B, Lq, Lk, H
 
 
+def _xattn_dense(ctx, d_ctx, lse, B, Lq, H):
+    """The dense operands of the backward entry points: ctx, d_ctx (B, Lq, H * 64) 16-byte aligned, lse (B, H, Lq)."""
+    for t, name, count, aligned in ((ctx, "ctx", B * Lq * H * 64, True), (d_ctx, "d_ctx", B * Lq * H * 64, True), (lse, "lse", B * H * Lq, False)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != count:
+            raise RuntimeError(f"{name} must be a dense float32 tensor of {count} elements")
+        if aligned and t.data_ptr() % 16:
+            raise RuntimeError(f"{name} must be 16-byte aligned (the attention kernels load 16-byte pieces); got a view at a storage offset")
+
+
 def xattn_fwd(q, k, v, B, Lq, Lk, H, scale):
     """softmax(q k^T scale) v with queries and keys from two sequences (csrc/attn_cross.hip): q (B, Lq, H * 64), k and v (B, Lk, H * 64)
     -> ctx (B, Lq, H * 64), lse (B, H, Lq), both dense.  The operands may be views (a slice of a packed [k|v] or qkv product): see
@@ -1526,17 +1535,57 @@ def xattn_bwd(q, k, v, ctx, d_ctx, lse, B, Lq, Lk, H, scale):
     q_rs = _xattn_operand(q, "q", B, Lq, H)
     k_rs = _xattn_operand(k, "k", B, Lk, H)
     v_rs = _xattn_operand(v, "v", B, Lk, H)
-    for t, name, count, aligned in ((ctx, "ctx", B * Lq * H * 64, True), (d_ctx, "d_ctx", B * Lq * H * 64, True), (lse, "lse", B * H * Lq, False)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != count:
-            raise RuntimeError(f"{name} must be a dense float32 tensor of {count} elements")
-        if aligned and t.data_ptr() % 16:
-            raise RuntimeError(f"{name} must be 16-byte aligned (the attention kernels load 16-byte pieces); got a view at a storage offset")
+    _xattn_dense(ctx, d_ctx, lse, B, Lq, H)
     _xattn_device(q=q, k=k, v=v, ctx=ctx, d_ctx=d_ctx, lse=lse)
     d_q = torch.empty((B, Lq, H * 64), dtype=torch.float32, device=q.device)
     d_k = torch.empty((B, Lk, H * 64), dtype=torch.float32, device=q.device)
     d_v = torch.empty((B, Lk, H * 64), dtype=torch.float32, device=q.device)
     _call(q.device, "upp_xattn_bwd", _abi.ptr(q), _abi.ptr(k), _abi.ptr(v), _abi.ptr(ctx), _abi.ptr(d_ctx), _abi.ptr(lse), _abi.ptr(d_q),
           _abi.ptr(d_k), _abi.ptr(d_v), B, Lq, Lk, H, 64, q_rs, k_rs, v_rs, H * 64, H * 64, H * 64, float(scale))
+    return d_q, d_k, d_v
+
+
+def _xattn_splits(Lq, Lk, split_q, split_k):
+    split_q, split_k = int(split_q), int(split_k)
+    if not 0 <= split_q <= Lq:
+        raise RuntimeError(f"prefix attention needs 0 <= split_q <= Lq = {Lq}, got {split_q}")
+    if not 1 <= split_k <= Lk:
+        raise RuntimeError(f"prefix attention needs 1 <= split_k <= Lk = {Lk} (every query row sees at least one key), got {split_k}")
+    return split_q, split_k
+
+
+def xattn_prefix_fwd(q, k, v, B, Lq, Lk, H, scale, split_q, split_k):
+    """xattn_fwd under the prefix-visibility mask of csrc/attn_prefix.hip: query rows < split_q see the keys < split_k, the other rows see
+    all Lk keys (AdaPoinTr's denoising queries: Lq = Lk = L, both splits L - D) -> ctx (B, Lq, H * 64), lse (B, H, Lq) over the visible keys.
+    Operands and their checks as in xattn_fwd; 0 <= split_q <= Lq and 1 <= split_k <= Lk, everything else raises before a launch."""
+    B, Lq, Lk, H = _xattn_lengths(B, Lq, Lk, H)
+    split_q, split_k = _xattn_splits(Lq, Lk, split_q, split_k)
+    q_rs = _xattn_operand(q, "q", B, Lq, H)
+    k_rs = _xattn_operand(k, "k", B, Lk, H)
+    v_rs = _xattn_operand(v, "v", B, Lk, H)
+    _xattn_device(q=q, k=k, v=v)
+    ctx = torch.empty((B, Lq, H * 64), dtype=torch.float32, device=q.device)
+    lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
+    _call(q.device, "upp_xattn_prefix_fwd", _abi.ptr(q), _abi.ptr(k), _abi.ptr(v), _abi.ptr(ctx), _abi.ptr(lse), B, Lq, Lk, H, 64, q_rs, k_rs,
+          v_rs, float(scale), split_q, split_k)
+    return ctx, lse
+
+
+def xattn_prefix_bwd(q, k, v, ctx, d_ctx, lse, B, Lq, Lk, H, scale, split_q, split_k):
+    """-> (d_q, d_k, d_v) of xattn_prefix_fwd, as xattn_bwd returns them: fresh dense tensors, every element written by exactly one
+    workgroup, two calls give the same bits.  Keys no row sees (split_q == Lq, keys >= split_k) get zero gradients."""
+    B, Lq, Lk, H = _xattn_lengths(B, Lq, Lk, H)
+    split_q, split_k = _xattn_splits(Lq, Lk, split_q, split_k)
+    q_rs = _xattn_operand(q, "q", B, Lq, H)
+    k_rs = _xattn_operand(k, "k", B, Lk, H)
+    v_rs = _xattn_operand(v, "v", B, Lk, H)
+    _xattn_dense(ctx, d_ctx, lse, B, Lq, H)
+    _xattn_device(q=q, k=k, v=v, ctx=ctx, d_ctx=d_ctx, lse=lse)
+    d_q = torch.empty((B, Lq, H * 64), dtype=torch.float32, device=q.device)
+    d_k = torch.empty((B, Lk, H * 64), dtype=torch.float32, device=q.device)
+    d_v = torch.empty((B, Lk, H * 64), dtype=torch.float32, device=q.device)
+    _call(q.device, "upp_xattn_prefix_bwd", _abi.ptr(q), _abi.ptr(k), _abi.ptr(v), _abi.ptr(ctx), _abi.ptr(d_ctx), _abi.ptr(lse),
+          _abi.ptr(d_q), _abi.ptr(d_k), _abi.ptr(d_v), B, Lq, Lk, H, 64, q_rs, k_rs, v_rs, H * 64, H * 64, H * 64, float(scale), split_q, split_k)
     return d_q, d_k, d_v
 
 

@@ -217,6 +217,32 @@ def cross_attention(q, k, v, num_heads, scale):
     return (attn @ vh).transpose(1, 2).reshape(B, Lq, C)
 
 
+def prefix_mask(Lq, Lk, split_q, split_k, device=None):
+    """(Lq, Lk) bool, True = hidden: rows < split_q do not see the keys >= split_k (the reference's mask[:-D, -D:] = 1 for
+    Lq = Lk = L, both splits L - D)."""
+    split_q, split_k = int(split_q), int(split_k)
+    if not 0 <= split_q <= Lq or not 1 <= split_k <= Lk:
+        raise ValueError("prefix attention needs 0 <= split_q <= Lq and 1 <= split_k <= Lk, got %d, %d for (%d, %d)" % (split_q, split_k, Lq, Lk))
+    mask = torch.zeros(Lq, Lk, dtype=torch.bool, device=device)
+    mask[:split_q, split_k:] = True
+    return mask
+
+
+def prefix_attention(q, k, v, num_heads, scale, split_q, split_k):
+    """The denoising-query attention of include/upp_hip.h as torch operators (any device, any head_dim; differentiable): cross_attention
+    with the reference's masked_fill(mask, -finfo.max) before the softmax (models/Transformer_utils.py:107-112).  It keeps the (B,H,Lq,Lk)
+    tensor and the (Lq,Lk) mask the kernels avoid."""
+    B, Lq, C = q.shape
+    Lk = k.shape[1]
+    H = int(num_heads)
+    qh = q.reshape(B, Lq, H, C // H).permute(0, 2, 1, 3)
+    kh = k.reshape(B, Lk, H, C // H).permute(0, 2, 1, 3)
+    vh = v.reshape(B, Lk, H, C // H).permute(0, 2, 1, 3)
+    attn = (qh @ kh.transpose(-2, -1)) * scale
+    attn = attn.masked_fill(prefix_mask(Lq, Lk, split_q, split_k, q.device), -torch.finfo(attn.dtype).max).softmax(dim=-1)
+    return (attn @ vh).transpose(1, 2).reshape(B, Lq, C)
+
+
 def chamfer(xyz1, xyz2):
     """-> (dist1 (B,N), dist2 (B,M)) squared nearest-neighbour distances, differentiable (reference extensions/chamfer_dist)."""
     d = ((xyz1.unsqueeze(2) - xyz2.unsqueeze(1)) ** 2).sum(-1)

@@ -534,6 +534,32 @@ int upp_xattn_bwd(const float *q, const float *k, const float *v, const float *c
                   int B, int Lq, int Lk, int H, int head_dim,
                   long long q_rs, long long k_rs, long long v_rs,
                   long long dq_rs, long long dk_rs, long long dv_rs, float scale, void *stream);
+/* ---- denoising-query attention: cross-attention under a prefix-visibility mask --------------
+ * The masked self-attention of AdaPoinTr's decoder in training (reference models/AdaPoinTr.py:217-229, Attention.forward(x, mask) at
+ * models/Transformer_utils.py:100-120: masked_fill(-finfo.max) before the softmax); csrc/attn_prefix.hip.  Operands, strides, layouts,
+ * refusals and the caller's duties are those of upp_xattn_fwd / upp_xattn_bwd ("Stride rule" above).  Two integers are added:
+ *   query rows i <  split_q see the keys j < split_k;   query rows i >= split_q see all Lk keys.
+ * AdaPoinTr: Lq = Lk = L, split_q = split_k = L - D for D denoising queries, q / k / v views of one packed qkv.
+ * Checked before any launch, after the checks of upp_xattn_*: 0 <= split_q <= Lq and 1 <= split_k <= Lk, else UPP_E_BADARG.
+ * A hidden key takes no part: its probability is the constant 0, set by a select on the indices and not by arithmetic on its score, so a
+ * NaN in a hidden k row leaves ctx and lse of the rows that cannot see it untouched (in f32 the reference's masked_fill gives the same
+ * exact 0, split_k >= 1 leaving every row a visible key).  lse is the log-sum-exp over the visible keys.  Nothing is promised for a
+ * non-finite hidden v row or for the gradients next to one (0 * NaN, as in the reference).
+ * Rows < split_q of ctx / lse carry the bits of upp_xattn_fwd on the first split_k keys, rows >= split_q those of upp_xattn_fwd on all
+ * keys; with split_q == 0 or split_k == Lk forward and backward give the bits of upp_xattn_fwd / upp_xattn_bwd.
+ * The mask shortens the walks: a query block wholly below split_q stops at the key block holding split_k - 1, a key block wholly at or
+ * beyond split_k starts at the query block holding split_q.  The single-key-block backward form (the row sum over the block's own P dP,
+ * visible keys only) is taken for every 64-row query block whose rows see one key block: Lk <= 64, or a block wholly below split_q when
+ * split_k <= 64; there a row that sees one key gives d_q = d_k = 0 exactly.  One workgroup per output element: no atomics, no workspace,
+ * no memset. */
+int upp_xattn_prefix_fwd(const float *q, const float *k, const float *v, float *ctx, float *lse,
+                         int B, int Lq, int Lk, int H, int head_dim,
+                         long long q_rs, long long k_rs, long long v_rs, float scale, int split_q, int split_k, void *stream);
+int upp_xattn_prefix_bwd(const float *q, const float *k, const float *v, const float *ctx, const float *d_ctx, const float *lse,
+                         float *d_q, float *d_k, float *d_v,
+                         int B, int Lq, int Lk, int H, int head_dim,
+                         long long q_rs, long long k_rs, long long v_rs,
+                         long long dq_rs, long long dk_rs, long long dv_rs, float scale, int split_q, int split_k, void *stream);
 /* ---- prompt propagation (Block.forward, reference models/Point_MAE_pretask_dev.py:275-303) ----
  * X (rows, D): the block's token matrix viewed as rows = B*L' rows [cls | prompts | T centre tokens] per sample.
  * Index arguments are ABSOLUTE row numbers of X (the host converts the reference's flat / per-sample index
