@@ -615,30 +615,54 @@ __global__ __launch_bounds__(256) void prop_x_csr_kernel(const float *__restrict
 #pragma unroll
         for (int e = 0; e < kMaxE; ++e) { acc[e] += 0.3f * a0[e]; acc[e] += f1 * a1[e]; }
     }
-    for (int h0 = s1; h0 < e1; h0 += 4) {                     // groups that list this row as a neighbour
-        int g[4], k[4];
-        float f[4];
+    // the groups that list this row as a neighbour, entries [b0, b1) of its CSR row, four at a time
+    auto add_entries = [&](int b0, int b1) {
+        for (int h0 = b0; h0 < b1; h0 += 4) {
+            int g[4], k[4];
+            float f[4];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) { const int q = perm1[min(h0 + t, e1 - 1)]; g[t] = q / kNb; k[t] = q - g[t] * kNb; }
+            for (int t = 0; t < 4; ++t) { const int q = perm1[min(h0 + t, b1 - 1)]; g[t] = q / kNb; k[t] = q - g[t] * kNb; }
 #pragma unroll
-        for (int t = 0; t < 4; ++t) f[t] = h0 + t < e1 ? 1.0f + (u ? floorf(keep + u[g[t]]) / keep : 1.0f) : 0.0f;
-        float gl[kMaxE][4], pv[kMaxE][4];
-        int am[kMaxE][4];
+            for (int t = 0; t < 4; ++t) f[t] = h0 + t < b1 ? 1.0f + (u ? floorf(keep + u[g[t]]) / keep : 1.0f) : 0.0f;
+            float gl[kMaxE][4], pv[kMaxE][4];
+            int am[kMaxE][4];
 #pragma unroll
-        for (int e = 0; e < kMaxE; ++e)
+            for (int e = 0; e < kMaxE; ++e)
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const size_t o = (size_t)g[t] * D + cc[e];
-                gl[e][t] = g_c2[o]; pv[e][t] = pooled[o]; am[e][t] = amax[o];
+                for (int t = 0; t < 4; ++t) {
+                    const size_t o = (size_t)g[t] * D + cc[e];
+                    gl[e][t] = g_c2[o]; pv[e][t] = pooled[o]; am[e][t] = amax[o];
+                }
+#pragma unroll
+            for (int e = 0; e < kMaxE; ++e)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const float xh = (pv[e][t] - mu[e]) * rs[e];
+                    // eval: g_pooled = gamma * rstd * g_c2 and nothing else -- a non-finite xhat (a NaN token) must not reach g_X through 0 * xhat
+                    const float gp = (ga[e] * rs[e]) * (training ? gl[e][t] - c1[e] - xh * c2[e] : gl[e][t]);
+                    acc[e] += gp * f[t] * (0.125f + (am[e][t] == k[t] ? 1.0f : 0.0f));
+                }
+        }
+    };
+    constexpr int kRowChunk = 64;
+    if (e1 - s1 <= kRowChunk) {                               // every row of the models: a few dozen entries at most
+        add_entries(s1, e1);
+    } else {
+        // A row listed by hundreds of groups is summed in chunks of kRowChunk entries: every chunk after the first starts a fresh partial
+        // sum, so its terms meet a small accumulator and only one addition per chunk meets the large one -- the rounding of those
+        // additions is what a long row's error consists of.
+        float head[kMaxE];
+#pragma unroll
+        for (int e = 0; e < kMaxE; ++e) head[e] = 0.0f;
+        for (int c0 = s1; c0 < e1; c0 += kRowChunk) {
+            if (c0 > s1) {
+#pragma unroll
+                for (int e = 0; e < kMaxE; ++e) { head[e] += acc[e]; acc[e] = 0.0f; }
             }
+            add_entries(c0, min(e1, c0 + kRowChunk));
+        }
 #pragma unroll
-        for (int e = 0; e < kMaxE; ++e)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const float xh = (pv[e][t] - mu[e]) * rs[e];
-                const float gp = (ga[e] * rs[e]) * (gl[e][t] - c1[e] - xh * c2[e]);
-                acc[e] += gp * f[t] * (0.125f + (am[e][t] == k[t] ? 1.0f : 0.0f));
-            }
+        for (int e = 0; e < kMaxE; ++e) acc[e] += head[e];
     }
 #pragma unroll
     for (int e = 0; e < kMaxE; ++e) { const int c = lane + 64 * e; if (c < D) g_X[(size_t)r * D + c] = acc[e]; }
@@ -791,11 +815,11 @@ __global__ __launch_bounds__(64) void prop_weights_bwd_kernel(const float *__res
             jj[i * kNb + k] = j;
             const float *q = c2 + ((size_t)b * G2 + j) * 3;
             const float bx = q[0], by = q[1], bz = q[2];
-            float d = -2.0f * __builtin_fmaf(az, bz, __builtin_fmaf(ay, by, ax * bx));     // the forward's operation order (prop_index_kernel)
-            d += (ax * ax + ay * ay) + az * az;
-            d += (bx * bx + by * by) + bz * bz;
-            rc[k] = 1.0f / (d + eps); S += rc[k];
             dx[k] = ax - bx; dy[k] = ay - by; dz[k] = az - bz;
+            // d from the differences, not the forward's three-term form: that form's rounding (~1e-7 for unit-ball centres, and not zero for
+            // a coincident pair because the dot product is fused and the norms are not) is 1e-4 of eps, and the gradient inherits it
+            const float d = (dx[k] * dx[k] + dy[k] * dy[k]) + dz[k] * dz[k];
+            rc[k] = 1.0f / (d + eps); S += rc[k];
             G[k] = g_w8[((size_t)b * T + i) * kNb + k];
         }
         float gw = 0.0f;
