@@ -663,7 +663,10 @@ def layer_norm(x, ln, last=None):
     """ln(x) -- or, with `last`, ln(x[:, -last:]) -- for an nn.LayerNorm over the last dimension of a (B,L,D) / (R,D) f32 HIP tensor on
     the row kernel of csrc/block.hip (upp_rowln_fwd: identity / strip row map, the normalised rows only); the module itself for anything
     else.  The prompting front-end calls it (reference models/Point_MAE_unify.py:588 `self.norm`, models/Point_MAE_pretask_dev.py:381
-    the decoder's norm over the returned tokens): no torch kernel, no copy of the row window."""
+    the decoder's norm over the returned tokens): no torch kernel, no copy of the row window.  `last` needs a (B,L,D) input: on (R,D)
+    it would mean the last ROWS on the kernel and the last COLUMNS on the module, so it raises on both."""
+    if last is not None and x.dim() != 3:
+        raise ValueError("layer_norm: `last` selects token rows of a (B, L, D) input, got %s" % (tuple(x.shape),))
     ok = (isinstance(ln, torch.nn.LayerNorm) and x.is_cuda and x.dtype == torch.float32 and x.dim() in (2, 3) and len(ln.normalized_shape) == 1
           and ln.normalized_shape[0] == x.shape[-1] and x.shape[-1] <= 512 and ln.elementwise_affine and ln.bias is not None and x.numel() > 0)
     if not ok:

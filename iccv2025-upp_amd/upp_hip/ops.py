@@ -28,6 +28,15 @@ def _need(t, name, dtype, ndim=None, last=None):
         raise RuntimeError(f"{name} last dim must be {last}, got {tuple(t.shape)}")
 
 
+def _need_f32(t, name, shape, optional=False):
+    """_need for an f32 operand of exactly `shape`; None passes where the operand is optional.  Metadata only: no synchronisation, no copy."""
+    if t is None and optional:
+        return
+    _need(t, name, torch.float32)
+    if tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
+
+
 def _same_device(*ts):
     d = ts[0].device
     for t in ts[1:]:
@@ -1360,8 +1369,21 @@ def linear_wgrad_grouped(pairs):
 
 
 def rowln_fwd(x, add, prompts, mode, P, y, u, keep, gamma, beta, eps, Lout, want_xo=True, ybias=None):
+    _need(x, "x", torch.float32, ndim=3)
     B, Lin, D = x.shape
     dev = x.device
+    _need_f32(add, "add", (B, Lin, D), optional=True)
+    if prompts is not None:
+        if int(mode) in (1, 2):
+            _need_f32(prompts, "prompts", (int(P), D))
+        else:
+            _need(prompts, "prompts", torch.float32)
+    _need_f32(y, "y", (B, Lin, D), optional=True)
+    _need_f32(ybias, "ybias", (D,), optional=True)
+    _need_f32(u, "u", (B,), optional=True)
+    _need_f32(gamma, "gamma", (D,), optional=True)
+    _need_f32(beta, "beta", (D,), optional=gamma is None)
+    _same_device(*[t for t in (x, add, prompts, y, ybias, u, gamma, beta) if t is not None])
     xo = torch.empty((B, Lout, D), dtype=torch.float32, device=dev) if want_xo else None
     if gamma is not None:
         h = torch.empty((B, Lout, D), dtype=torch.float32, device=dev)
@@ -1376,6 +1398,17 @@ def rowln_fwd(x, add, prompts, mode, P, y, u, keep, gamma, beta, eps, Lout, want
 
 
 def rowln_bwd(g_xo, g_h, xo, mean, rstd, gamma, mode, u, keep, B, Lin, Lout, D, P, need_x, need_prompt, need_y, need_ln_part=False):
+    if g_xo is None and g_h is None:
+        raise RuntimeError("rowln_bwd: one of g_xo, g_h is required")
+    _need_f32(g_xo, "g_xo", (B, Lout, D), optional=True)
+    _need_f32(g_h, "g_h", (B, Lout, D), optional=True)
+    with_ln = g_h is not None                                  # the saved rows and statistics are read only for the LayerNorm's backward
+    _need_f32(xo, "xo", (B, Lout, D), optional=not with_ln)
+    _need_f32(mean, "mean", (B, Lout), optional=not with_ln)
+    _need_f32(rstd, "rstd", (B, Lout), optional=not with_ln)
+    _need_f32(gamma, "gamma", (D,), optional=not with_ln)
+    _need_f32(u, "u", (B,), optional=True)
+    _same_device(*[t for t in (g_xo, g_h, xo, mean, rstd, gamma, u) if t is not None])
     dev = (g_xo if g_xo is not None else g_h).device
     g_x = torch.empty((B, Lin, D), dtype=torch.float32, device=dev) if need_x else None      # the kernel writes every row
     g_p = torch.empty((B, P, D), dtype=torch.float32, device=dev) if (need_prompt and P > 0 and mode in (1, 2)) else None
@@ -2244,10 +2277,30 @@ def adamw_flat(p, g, m, v, n, split, state, scratch, lr, beta1, beta2, eps, weig
 
 
 # ------------------------------------------------------------------ bottleneck adapter
-def adapter_fwd(ha, x, W1, b1, W2, b2, u, p, scale):
-    D = ha.shape[-1]
-    R = ha.numel() // D
+def _adapter_args(who, rows, W1, W2, u, s1=None, **row_tensors):
+    """The operands every adapter entry point shares: row tensors (..., D) of ONE shape, W1 (H, D), W2 (D, H), the optional dropout
+    uniforms (R, H) and the saved s1 (R, H).  -> (R, D, H)"""
+    _need(rows, who + ": rows", torch.float32)
+    if rows.dim() not in (2, 3):
+        raise RuntimeError(f"{who}: row tensors must be (R, D) or (B, L, D), got {tuple(rows.shape)}")
+    D = rows.shape[-1]
+    R = rows.numel() // D
+    _need(W1, "W1", torch.float32, ndim=2, last=D)
     H = W1.shape[0]
+    _need_f32(W2, "W2", (D, H))
+    for name, t in row_tensors.items():
+        _need_f32(t, name, rows.shape)
+    _need_f32(u, "dropout uniforms", (R, H), optional=True)
+    _need_f32(s1, "s1", (R, H), optional=True)
+    _same_device(*[t for t in (rows, W1, W2, u, s1) + tuple(row_tensors.values()) if t is not None])
+    return R, D, H
+
+
+def adapter_fwd(ha, x, W1, b1, W2, b2, u, p, scale):
+    R, D, H = _adapter_args("adapter_fwd", ha, W1, W2, u, ha=ha, x=x)
+    _need_f32(b1, "b1", (H,))
+    _need_f32(b2, "b2", (D,))
+    _same_device(ha, b1, b2)
     out = torch.empty_like(x)
     s1 = torch.empty((R, H), dtype=torch.float32, device=ha.device)
     _call(ha.device, "upp_adapter_fwd", _abi.ptr(ha), _abi.ptr(x), _abi.ptr(W1), _abi.ptr(b1), _abi.ptr(W2), _abi.ptr(b2), _abi.ptr(u),
@@ -2265,6 +2318,11 @@ def ln_adapter_fwd(x, y, ybias, u, keep, mode, P, gamma, beta, eps, W1, b1, W2, 
         _need(t_, n_, torch.float32)
         if tuple(t_.shape) != shp:
             raise RuntimeError(f"ln_adapter_fwd: {n_} must be {shp}, got {tuple(t_.shape)}")
+    _need_f32(y, "y", (B, Lin, D), optional=True)
+    _need_f32(ybias, "ybias", (D,), optional=True)
+    _need_f32(u, "u", (B,), optional=True)
+    _need_f32(ud, "ud", (B * Lout, H), optional=True)
+    _same_device(*[t for t in (x, y, ybias, u, gamma, beta, W1, b1, W2, b2, ud) if t is not None])
     xo = torch.empty((B, Lout, D), dtype=torch.float32, device=dev)
     out = torch.empty((B, Lout, D), dtype=torch.float32, device=dev)
     mean = torch.empty((B, Lout), dtype=torch.float32, device=dev)
@@ -2278,9 +2336,12 @@ def ln_adapter_fwd(x, y, ybias, u, keep, mode, P, gamma, beta, eps, W1, b1, W2, 
 
 def ln_adapter_bwd(g_out, xo, mean, rstd, gamma, beta, s1, W1, W2, u, p, scale):
     """upp_adapter_bwd with the LayerNorm output rebuilt from the saved rows and statistics -> (g_ha, partials)."""
-    D = xo.shape[-1]
-    R = xo.numel() // D
-    H = W1.shape[0]
+    R, D, H = _adapter_args("ln_adapter_bwd", xo, W1, W2, u, s1=s1, xo=xo, g_out=g_out)
+    _need_f32(mean, "mean", xo.shape[:-1])
+    _need_f32(rstd, "rstd", xo.shape[:-1])
+    _need_f32(gamma, "gamma", (D,))
+    _need_f32(beta, "beta", (D,))
+    _same_device(xo, mean, rstd, gamma, beta)
     g_ha = torch.empty_like(xo)
     n = int(_abi.load().upp_adapter_part_floats(R, D))
     nblk = (R + 31) // 32
@@ -2295,10 +2356,16 @@ def ln_adapter_bwd_fused(g_out, xo, mean, rstd, gamma, beta, s1, W1, W2, ud, p, 
     """Backward of ln_adapter_fwd in one launch -> (g_x, g_y, adapter partials, LayerNorm partials); upp_ln_adapter_bwd_fused.
     factors=True: the third result is `fac` (B*Lout, 2 H) = [ga | d] per row instead of the per-workgroup partial matrices
     (upp_ln_adapter_bwd_factors; the weight gradients are then formed by adapter_wgrad_batched)."""
+    _need(xo, "xo", torch.float32, ndim=3)
     B, Lout, D = xo.shape
-    H = W1.shape[0]
+    R, D, H = _adapter_args("ln_adapter_bwd_fused", xo, W1, W2, ud, s1=s1, xo=xo, g_out=g_out)
+    _need_f32(mean, "mean", (B, Lout))
+    _need_f32(rstd, "rstd", (B, Lout))
+    _need_f32(gamma, "gamma", (D,))
+    _need_f32(beta, "beta", (D,))
+    _need_f32(u, "u", (B,), optional=True)
+    _same_device(*[t for t in (xo, mean, rstd, gamma, beta, u) if t is not None])
     dev = xo.device
-    R = B * Lout
     nwg = (R + 15) // 16
     g_x = torch.empty((B, Lin, D), dtype=torch.float32, device=dev) if need_x else None
     g_y = torch.empty((B, Lin, D), dtype=torch.float32, device=dev) if need_y else None
@@ -2341,9 +2408,7 @@ def adapter_wgrad_batched(jobs, H=32):
 
 
 def adapter_bwd(g_out, ha, s1, W1, W2, u, p, scale):
-    D = ha.shape[-1]
-    R = ha.numel() // D
-    H = W1.shape[0]
+    R, D, H = _adapter_args("adapter_bwd", ha, W1, W2, u, s1=s1, ha=ha, g_out=g_out)
     g_ha = torch.empty_like(ha)
     n = int(_abi.load().upp_adapter_part_floats(R, D))
     nblk = (R + 31) // 32
