@@ -458,6 +458,10 @@ def _bn_rows(x, bn, training, relu=False, drop=None):
         # (the caller has bumped num_batches_tracked already -- bump_counter is immediate while this switch is on: momentum=None reads it)
         y = _SyncBNRows.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, bn.num_batches_tracked)
         return F.relu(y) if relu else y
+    if bn.momentum is None and training and bn.running_mean is not None:
+        # (the cumulative average 1 / num_batches_tracked: formed by the synchronised form above only.  Momentum 0 in its place would
+        #  leave the running statistics where they are, silently)
+        raise ValueError("BatchNorm with momentum=None (cumulative moving average) is served under synchronised BatchNorm only")
     if x.is_cuda and x.dtype == torch.float32 and x.dim() == 2:
         if _no_grad_needed(x, bn.weight, bn.bias):
             return HF.bn_rows(x, bn, training, relu)   # 3 launches instead of torch's 5-6 (frozen prompter branches)

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(64 * kPW) void cls_pool_fwd_kernel(const float *__r
             for (int e = 0; e < kMaxE; ++e) {
                 const float h = __builtin_fmaf((v[r][e] - s[r]) * q[r], gv[e], bv[e]);
                 if (t == 0) { if (lane + 64 * e < D) feat[(size_t)b * 2 * D + lane + 64 * e] = h; }
-                else if (h > mx[e]) { mx[e] = h; am[e] = t; }      // rows visited in increasing t: strict '>' keeps the first maximum
+                else if (h > mx[e] || (h != h && mx[e] == mx[e])) { mx[e] = h; am[e] = t; }   // rows visited in increasing t: strict '>' keeps the first maximum; the FIRST NaN wins, as torch.max(dim) (group_max_fwd_kernel)
             }
         }
     }
@@ -79,7 +79,8 @@ __global__ __launch_bounds__(64 * kPW) void cls_pool_fwd_kernel(const float *__r
         for (int w = 1; w < kPW; ++w) {
             const float v = smx[w][c];
             const int i = sam[w][c];
-            if (v > best || (v == best && i < bi)) { best = v; bi = i; }
+            const bool vn = v != v, bn = best != best;             // a NaN beats every number; among NaNs, as among equal maxima, the lowest row
+            if (vn ? (!bn || i < bi) : (!bn && (v > best || (v == best && i < bi)))) { best = v; bi = i; }
         }
         feat[(size_t)b * 2 * D + D + c] = best;
         amax[(size_t)b * D + c] = bi;
@@ -158,24 +159,38 @@ __global__ __launch_bounds__(1024) void ce_acc_kernel(const float *__restrict__ 
             mx = fmaxf(mx, v[e]);
         }
         mx = wave_max_f32(mx);
-        float se = 0.0f;
-#pragma unroll
-        for (int e = 0; e < kMaxE; ++e) se += lane + 64 * e < C ? expf(v[e] - mx) : 0.0f;
-        se = wave_sum_f32(se);
-        const float lse = mx + logf(se);
-        const int y = (int)labels[b];
         // first index holding the maximum (torch.argmax)
         int first = C;
 #pragma unroll
         for (int e = 0; e < kMaxE; ++e) if (lane + 64 * e < C && v[e] == mx) first = min(first, lane + 64 * e);
         first = (int)wave_min_u32((uint32_t)first);
+        // Two forms.  The plain one -- lse = mx + log(sum), softmax = exp(v - lse), term = lse - v_y -- rounds lse to ulp(mx) and cancels
+        // in softmax - 1 at a label with p -> 1; it is kept, bit for bit, where neither matters (|mx| < 16, the other classes hold at
+        // least 1/16 of the first maximum's weight).  Elsewhere: log sum exp(v - mx) = log1p(sum over the OTHER classes) -- the first
+        // maximum's term is an exact 1, and a confident sample's loss is the small sum itself --, log p = (v - mx) - that, term =
+        // (mx - v_y) + that, and softmax - 1 at the label = expm1(log p).
+        float se = 0.0f, se1 = 0.0f;
+#pragma unroll
+        for (int e = 0; e < kMaxE; ++e) {
+            const float t = lane + 64 * e < C ? expf(v[e] - mx) : 0.0f;
+            se += t;
+            se1 += lane + 64 * e != first ? t : 0.0f;
+        }
+        se = wave_sum_f32(se);
+        se1 = wave_sum_f32(se1);
+        const bool plain = fabsf(mx) < 16.0f && se1 >= 0.0625f;
+        const float lgs = log1pf(se1), lse = mx + logf(se);
+        const long long yl = labels[b];
+        const int y = (yl >= 0 && yl < C) ? (int)yl : -1;          // (compared in 64 bits: a label of 2^32 + 3 is no class 3)
 #pragma unroll
         for (int e = 0; e < kMaxE; ++e) {
             const int c = lane + 64 * e;
-            if (c < C) dlogits[(size_t)b * C + c] = (expf(v[e] - lse) - (c == y ? 1.0f : 0.0f)) / (float)B;
+            const float lp = (v[e] - mx) - lgs;
+            const float d = plain ? expf(v[e] - lse) - (c == y ? 1.0f : 0.0f) : (c == y ? expm1f(lp) : expf(lp));
+            if (c < C) dlogits[(size_t)b * C + c] = d / (float)B;
         }
         const float vy = (y >= 0 && y < C) ? logits[(size_t)b * C + y] : 0.0f;
-        lsum += lse - vy;
+        lsum += plain ? lse - vy : (mx - vy) + lgs;
         asum += first == y ? 1.0f : 0.0f;
     }
     sl[threadIdx.x] = lsum; sa[threadIdx.x] = asum;
@@ -186,7 +201,7 @@ __global__ __launch_bounds__(1024) void ce_acc_kernel(const float *__restrict__ 
         float l = 0.0f, a = 0.0f;
         for (int w = 0; w < nw; ++w) { l += sl[w * 64]; a += sa[w * 64]; }
         out[0] = l / (float)B;
-        out[1] = a / (float)B * 100.0f;
+        out[1] = a * 100.0f / (float)B;                            // (a * 100 is an exact integer: ONE rounding, the correctly rounded percentage)
     }
 }
 

@@ -435,7 +435,9 @@ __global__ __launch_bounds__(256) void sqdist_topk_kernel(const float *__restric
         d += aa;
         d += (bx[sl] * bx[sl] + by[sl] * by[sl]) + bz[sl] * bz[sl];
         const uint32_t bits = __float_as_uint(d);
-        img[sl] = lane + 64 * sl < S ? ((bits & 0x80000000u) ? ~bits : (bits | 0x80000000u)) : 0xFFFFFFFFu;
+        // (a NaN distance takes ONE image above +inf and below the padding, whatever its sign bit: last among the real points, as
+        // square_distance(...).sort() and argsort_rows rank it -- the raw image of a NaN with the sign bit set is the SMALLEST)
+        img[sl] = lane + 64 * sl < S ? (d != d ? 0xFFFFFFFEu : (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u)) : 0xFFFFFFFFu;
     }
     float myd = 0.0f;
     int myj = 0;
@@ -1000,12 +1002,21 @@ static int bn_drop_args(float p, const long long *seed, long long seed_add, unsi
     return 0;
 }
 
+// C % 4 == 0 takes 16-byte loads and stores of the matrices (the flat vec4 kernels), the tall path of the column parameters too: a pointer
+// off that alignment is refused before anything is launched.
+static bool bn_off16(const void *a, const void *b = nullptr, const void *c = nullptr, const void *d = nullptr, const void *e = nullptr,
+                     const void *f = nullptr) {
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(d) |
+             reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(f)) & 15) != 0;
+}
+
 static int bn_rows_fwd_impl(const float *x, const float *gamma, const float *beta, float *running_mean, float *running_var,
                             float momentum, float eps, int training, int relu, const BnDrop &dr, float *part, float *mean, float *rstd, float *y,
                             int R, int C, void *stream) {
     if (!x || !mean || !rstd || !y || R < 1 || C < 1) return UPP_E_BADARG;
     if (training && !part) return UPP_E_BADARG;
     if (!training && (!running_mean || !running_var)) return UPP_E_BADARG;
+    if ((C & 3) == 0 && (bn_off16(x, y) || (bn_tall(R, C) && bn_off16(mean, rstd, gamma, beta)))) return UPP_E_RANGE;
     hipStream_t st = (hipStream_t)stream;
     const int per = bn_per(R), slabs = (R + per - 1) / per;
     if (training) {
@@ -1045,6 +1056,7 @@ extern "C" int upp_bn_rows_drop_fwd(const float *x, const float *gamma, const fl
 static int bn_rows_bwd_impl(const float *x, const float *g, const float *mean, const float *rstd, const float *gamma, const float *beta,
                             int relu, const BnDrop &dr, float *part, float *g_gamma, float *g_beta, float *g_x, int R, int C, void *stream) {
     if (!x || !g || !mean || !rstd || !part || !g_gamma || !g_beta || R < 1 || C < 1) return UPP_E_BADARG;
+    if (g_x && (C & 3) == 0 && (bn_off16(x, g, g_x) || (bn_tall(R, C) && bn_off16(mean, rstd, gamma, beta, g_gamma, g_beta)))) return UPP_E_RANGE;
     hipStream_t st = (hipStream_t)stream;
     const int per = bn_per(R), slabs = (R + per - 1) / per, Cp = pow2_at_least(C);
     hipLaunchKernelGGL(bn_rows_bwd_partial_kernel, dim3(slabs, (C + 255) / 256), dim3(256), 0, st, x, g, mean, rstd, gamma, beta, relu, R, C, Cp,

@@ -1602,11 +1602,22 @@ def propagate(X, bn, index, u=None, keep=1.0, training=True, w8=None):
                             index.w8 if w8 is None else w8)
 
 
+def _bn_momentum(bn, use_batch):
+    """The momentum of the running-statistics update as the row kernels take it: a number.  momentum=None asks nn.BatchNorm for the
+    cumulative average 1 / num_batches_tracked, which these kernels do not form: refused where the statistics would be updated (batch
+    statistics with running buffers), irrelevant elsewhere."""
+    if bn.momentum is not None:
+        return float(bn.momentum)
+    if use_batch and bn.running_mean is not None:
+        raise ValueError("BatchNorm with momentum=None (cumulative moving average) is not served by the row kernels")
+    return 0.0
+
+
 # ------------------------------------------------------------------ forward-only row operators (frozen prompter branches)
 def bn_rows(x, bn, training, relu=False):
     """BatchNorm(+ReLU) over the rows of a channels-last (R,C) matrix; no autograd (frozen branches only)."""
     use_batch = training or bn.running_mean is None
-    momentum = 0.0 if bn.momentum is None else bn.momentum
+    momentum = _bn_momentum(bn, use_batch)
     return ops.bn_rows_fwd(x.contiguous(), bn.weight, bn.bias, bn.running_mean, bn.running_var, momentum, bn.eps, use_batch, relu)
 
 
@@ -1644,7 +1655,7 @@ def bn_rows_train(x, bn, relu=False, drop_p=0.0, salt=0, bump_pending=False):
     (upp_layers.bump_counter, as nn.BatchNorm1d does); bump_pending: that bump has been queued for the end of the forward, not applied.
     The forward snapshots the counter value it hashes and the backward uses that snapshot, so any number of forwards, a reset or a
     load_state_dict may run between a forward and its backward."""
-    momentum = 0.0 if bn.momentum is None else bn.momentum
+    momentum = _bn_momentum(bn, True)
     if drop_p > 0.0:
         return _BnRowsTrain.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, momentum, bn.eps, relu, float(drop_p),
                                   bn.num_batches_tracked, int(salt), bool(bump_pending))
@@ -2047,7 +2058,7 @@ class _BnReluDrop(Function):
 def bn_relu_drop(z, bn, u=None, p=0.0, training=True):
     """dropout_p(relu(bn(z))) for a (rows, C) matrix with few rows; u: uniforms (rows, C) when p > 0 in training."""
     use_batch = training or bn.running_mean is None
-    momentum = 0.0 if bn.momentum is None else bn.momentum
+    momentum = _bn_momentum(bn, use_batch)
     return _BnReluDrop.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, momentum, bn.eps, use_batch, u, float(p))
 
 

@@ -1094,7 +1094,11 @@ def nll_mean_fwd(logp, target):
 
 def nll_mean_bwd(g_loss, target, R, C):
     """-> g_logp (R, C) = -g_loss / R at (r, target[r]), 0 elsewhere; g_loss a one-element device tensor; upp_nll_mean_bwd."""
-    _need(g_loss, "g_loss", torch.float32)
+    _need(target, "target", torch.int64)
+    if tuple(target.shape) != (int(R),):
+        raise RuntimeError(f"nll_mean_bwd: target must be ({int(R)},), got {tuple(target.shape)}")
+    _need_f32(g_loss, "g_loss", (1,))
+    _same_device(target, g_loss)
     g_logp = torch.empty((int(R), int(C)), dtype=torch.float32, device=target.device)
     _call(target.device, "upp_nll_mean_bwd", _abi.ptr(g_loss), _abi.ptr(target), int(R), int(C), _abi.ptr(g_logp))
     return g_logp
@@ -1115,8 +1119,11 @@ def noise_loss_fwd(pred, noise_vector, pn, want_score=True):
 
 
 def noise_loss_bwd(g_loss, pred, noise_vector, pn):
-    _need(g_loss, "g_loss", torch.float32)
+    _need(pred, "pred", torch.float32, 3, 3)
     B, P, _ = pred.shape
+    _need_f32(noise_vector, "noise_vector", (B, P - int(pn), 3))
+    _need_f32(g_loss, "g_loss", (1,))
+    _same_device(pred, noise_vector, g_loss)
     g_pred = torch.empty_like(pred)
     _call(pred.device, "upp_noise_loss_bwd", _abi.ptr(g_loss), _abi.ptr(pred), _abi.ptr(noise_vector), B, P, int(pn), _abi.ptr(g_pred))
     return g_pred
@@ -1161,6 +1168,10 @@ def group_max_bwd(g, amax, k):
     """g (R,C), amax (R,C) uint8 -> g_x (R,k,C): g at the arg-max row of every (group, column), zero elsewhere (upp_group_max_bwd)."""
     _need(g, "g", torch.float32, ndim=2)
     R, C = g.shape
+    _need(amax, "amax", torch.uint8)
+    if tuple(amax.shape) != (R, C):
+        raise RuntimeError(f"group_max_bwd: amax must be ({R}, {C}), got {tuple(amax.shape)}")
+    _same_device(g, amax)
     g_x = torch.empty((R, int(k), C), dtype=torch.float32, device=g.device)
     _call(g.device, "upp_group_max_bwd", _abi.ptr(g), _abi.ptr(amax), R, int(k), C, _abi.ptr(g_x))
     return g_x
@@ -1757,11 +1768,28 @@ def _drop_seed(drop):
     return float(p), seed, int(add), int(salt) & 0xFFFFFFFF
 
 
+def _bn_params(x, gamma, beta, running_mean, running_var, training, affine_optional=True):
+    """The per-column operands of a BatchNorm over the rows of x (R, C): each (C,) f32 on x's device, or None where the kernel takes that
+    (identity affine; batch statistics without running buffers).  Training-mode statistics of ONE row are refused, as torch refuses them
+    ("Expected more than 1 value per channel when training"): the variance is 0 and its unbiased form 0 / 0."""
+    R, C = x.shape
+    for t, name, optional in ((gamma, "gamma", affine_optional), (beta, "beta", affine_optional),
+                              (running_mean, "running_mean", bool(training)), (running_var, "running_var", bool(training))):
+        _need_f32(t, name, (C,), optional=optional)
+        if t is not None:
+            _same_device(x, t)
+    if (running_mean is None) != (running_var is None):
+        raise RuntimeError("running_mean and running_var come together or not at all")
+    if training and R < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+
+
 def bn_rows_fwd(x, gamma, beta, running_mean, running_var, momentum, eps, training, relu, want_stats=False, drop=None):
     """drop = (p, seed, seed_add, salt): nn.Dropout(p) on the output in the same pass (training only; upp_bn_rows_drop_fwd)."""
     _need(x, "x", torch.float32, ndim=2)
     R, C = x.shape
     dev = x.device
+    _bn_params(x, gamma, beta, running_mean, running_var, training)
     part = torch.empty(_abi.load().upp_bn_rows_part_floats(R, C), dtype=torch.float32, device=dev) if training else None
     mean = torch.empty(C, dtype=torch.float32, device=dev)
     rstd = torch.empty(C, dtype=torch.float32, device=dev)
@@ -1830,6 +1858,9 @@ def interp_fwd(dist, idx, feat, k, eps, out=None, col0=0):
     if out is None:
         out = torch.empty((B, N, C), dtype=torch.float32, device=feat.device)
     _need(out, "out", torch.float32, ndim=3)
+    if tuple(out.shape[:2]) != (B, N) or int(col0) < 0 or out.shape[2] < int(col0) + C:
+        raise RuntimeError(f"out must be ({B}, {N}, >= col0 + {C}), got {tuple(out.shape)} with col0 = {int(col0)}")
+    _same_device(feat, out, dist, idx)
     _call(feat.device, "upp_interp_fwd", _abi.ptr(dist), _abi.ptr(idx), dist.stride(1), _abi.ptr(feat), _abi.ptr(out), out.shape[-1], int(col0),
           B, N, S, C, int(k), float(eps))
     return out
@@ -1910,6 +1941,9 @@ def cls_pool_fwd(x, gamma, beta, eps):
     _need(x, "x", torch.float32, ndim=3)
     B, L, D = x.shape
     dev = x.device
+    _need_f32(gamma, "gamma", (D,))
+    _need_f32(beta, "beta", (D,))
+    _same_device(x, gamma, beta)
     feat = torch.empty((B, 2 * D), dtype=torch.float32, device=dev)
     amax = torch.empty((B, D), dtype=torch.int32, device=dev)
     mean = torch.empty(B * L, dtype=torch.float32, device=dev)
@@ -1920,8 +1954,16 @@ def cls_pool_fwd(x, gamma, beta, eps):
 
 
 def cls_pool_bwd(g_feat, x, mean, rstd, gamma, amax):
-    _need(g_feat, "g_feat", torch.float32, ndim=2)
+    _need(x, "x", torch.float32, ndim=3)
     B, L, D = x.shape
+    _need_f32(g_feat, "g_feat", (B, 2 * D))
+    _need_f32(mean, "mean", (B * L,))
+    _need_f32(rstd, "rstd", (B * L,))
+    _need_f32(gamma, "gamma", (D,))
+    _need(amax, "amax", torch.int32)
+    if tuple(amax.shape) != (B, D):
+        raise RuntimeError(f"cls_pool_bwd: amax must be ({B}, {D}), got {tuple(amax.shape)}")
+    _same_device(x, g_feat, mean, rstd, gamma, amax)
     g_x = torch.empty_like(x)
     _call(x.device, "upp_cls_pool_bwd", _abi.ptr(g_feat), _abi.ptr(x), _abi.ptr(mean), _abi.ptr(rstd), _abi.ptr(gamma), _abi.ptr(amax),
           _abi.ptr(g_x), B, L, D)
@@ -1932,6 +1974,9 @@ def ce_acc(logits, labels):
     _need(logits, "logits", torch.float32, ndim=2)
     _need(labels, "labels", torch.int64, ndim=1)
     B, C = logits.shape
+    if labels.shape[0] != B:
+        raise RuntimeError(f"ce_acc: labels must be ({B},), got {tuple(labels.shape)}")
+    _same_device(logits, labels)
     out2 = torch.empty(2, dtype=torch.float32, device=logits.device)
     dlogits = torch.empty_like(logits)
     _call(logits.device, "upp_ce_acc", _abi.ptr(logits), _abi.ptr(labels), _abi.ptr(out2), _abi.ptr(dlogits), B, C)
@@ -2177,6 +2222,10 @@ def completion_update(coarse, dense, gt, acc, category=None, n_valid=None, th=0.
 def bn_relu_drop_fwd(z, gamma, beta, running_mean, running_var, momentum, eps, training, u, p):
     _need(z, "z", torch.float32, ndim=2)
     R, C = z.shape
+    _bn_params(z, gamma, beta, running_mean, running_var, training, affine_optional=False)
+    _need_f32(u, "u", (R, C), optional=True)
+    if u is not None:
+        _same_device(z, u)
     a = torch.empty_like(z)
     mean = torch.empty(C, dtype=torch.float32, device=z.device)
     rstd = torch.empty(C, dtype=torch.float32, device=z.device)
@@ -2186,7 +2235,13 @@ def bn_relu_drop_fwd(z, gamma, beta, running_mean, running_var, momentum, eps, t
 
 
 def bn_relu_drop_bwd(g_a, z, gamma, beta, mean, rstd, training, u, p):
+    _need(z, "z", torch.float32, ndim=2)
     R, C = z.shape
+    _need_f32(g_a, "g_a", (R, C))
+    _need_f32(u, "u", (R, C), optional=True)
+    for t, name in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (rstd, "rstd")):
+        _need_f32(t, name, (C,))
+    _same_device(z, g_a, gamma, beta, mean, rstd, *(() if u is None else (u,)))
     g_z = torch.empty_like(z)
     g_gamma = torch.empty(C, dtype=torch.float32, device=z.device)
     g_beta = torch.empty(C, dtype=torch.float32, device=z.device)
