@@ -54,6 +54,7 @@ class UniformBank:
 UNIFORMS = UniformBank()
 FUSE_INTERP_GEO = True     # _inverse_distance_interp: HF.interp_geo when the coordinates carry a gradient (False: the torch formulation; tests A/B it)
 FUSE_LN_ADAPTER = True     # Block.forward_fused: close the block with HF.ln_adapter (one launch) instead of HF.rowln + HF.adapter
+FUSE_PROP_TAIL = True      # ... and a prompted block's MLP residual + prompt propagation + that tail with HF.prop_tail (7 launches, not 10)
 
 
 class use_rng:
@@ -837,11 +838,12 @@ class Block(nn.Module):
         return x + branch if scale is None else torch.addcmul(x, branch, scale)
 
     # -- fused gfx950 path ---------------------------------------------------------------------------
-    def _propagate_fused(self, x, kw):
-        """_propagate_prompts on the row kernels of csrc/prop.hip.  The neighbour weights and the absolute row
-        indices depend only on the centres / the token layout, so they are built once per forward (shared dict
-        `_prop_cache` put into the kwargs by TransformerEncoder) with exactly the reference's torch ops."""
-        B, Lp, D = x.shape
+    def _prop_inputs(self, shape, kw):
+        """What the propagation step of this block reads beside the tokens: (index, w8, u, keep).  The neighbour weights and the
+        absolute row indices depend only on the centres / the token layout, so they are built once per forward (shared dict
+        `_prop_cache` put into the kwargs by TransformerEncoder) with exactly the reference's torch ops; u / keep: the
+        stochastic-depth uniforms of the level-2 groups.  Counts the BatchNorm batch: once per forward."""
+        B, Lp, D = shape
         off = 1 if kw.get('classification') else 0
         c1, c2 = kw['center1'], kw['center2']
         T, G2 = c1.shape[1], c2.shape[1]
@@ -873,11 +875,19 @@ class Block(nn.Module):
             w8 = slot[1].pop() if slot[1] else slot[0]
         u, keep = None, 1.0
         if isinstance(self.drop_path, DropPath) and self.training and self.drop_path.drop_prob > 0:
-            u = UNIFORMS.take((B * G2,), x.device)
+            u = UNIFORMS.take((B * G2,), c1.device)
             keep = 1.0 - self.drop_path.drop_prob
         bn = self.bnorm
         if self.training and bn.track_running_stats:
             bump_counter(bn.num_batches_tracked)
+        return entry, w8, u, keep
+
+    def _propagate_fused(self, x, kw):
+        """_propagate_prompts on the row kernels of csrc/prop.hip."""
+        B, Lp, D = x.shape
+        G2 = kw['center2'].shape[1]
+        entry, w8, u, keep = self._prop_inputs(x.shape, kw)
+        bn = self.bnorm
         if bn.affine and (bn.track_running_stats or self.training) and B * Lp <= 15360 and not sync_bn_active(self.training):
             return HF.propagate(x, bn, entry, u, keep, self.training, w8=w8)
         pooled = HF.prop_pool(x, entry.i1, u, keep)
@@ -936,9 +946,24 @@ class Block(nn.Module):
         if path in _PATHS and kw.get(f'{path}_adapter', False):
             assert adapter is not None, 'No adapter inserted in block!'
         u2 = None if u is None else u[1]
+        tail_fused = (adapter is not None and D == 384 and adapter.ln1.weight.shape[0] == 32 and isinstance(adapter.activate, nn.GELU)
+                      and FUSE_LN_ADAPTER)
         if P and kw.get('prompt_propagation_after'):
+            prop_fused = (kw['center1_idx'].numel() == B * kw['center2'].shape[1] * 8 and kw['center1'].dtype == torch.float32
+                          and POOL_TRACE is None)
+            bn = self.bnorm
+            if (FUSE_PROP_TAIL and tail_fused and prop_fused and _no_grad_needed(kw['center1'], kw['center2'])
+                    and (bn.track_running_stats or self.training) and not sync_bn_active(self.training)
+                    and HF.prop_tail_usable(x2, bn, kw['center1'].shape[1], P, rem)):
+                # residual + propagation + tail as one node: x3 and the interpolated rows are never stored (HF.prop_tail).  Stage 2 (the
+                # interpolation weights carry a gradient, whose kernel reads x3) and everything else take the launches below.
+                entry, _, ug, keepg = self._prop_inputs(x2.shape, kw)
+                pd = adapter.dropout.p if self.training else 0.0
+                ud = UNIFORMS.take((B * (x2.shape[1] - P), 32), x.device) if pd > 0 else None
+                return HF.prop_tail(x2, m, mb, u2, keep, rem, P, bn, entry, ug, keepg, self.training, adapter.layer_norm, adapter.ln1.weight,
+                                    adapter.ln1.bias, adapter.ln2.weight, adapter.ln2.bias, ud, pd, 0.7)
             x3, _ = HF.rowln(x2, y=m, ybias=mb, u=u2, keep=keep)
-            if kw['center1_idx'].numel() == B * kw['center2'].shape[1] * 8 and kw['center1'].dtype == torch.float32 and POOL_TRACE is None:
+            if prop_fused:
                 x3 = self._propagate_fused(x3, kw)
             else:
                 if POOL_TRACE is None:
@@ -949,7 +974,7 @@ class Block(nn.Module):
             x4, _ = HF.rowln(x2, y=m, ybias=mb, u=u2, keep=keep, mode=rem, P=P)
             return x4
         ln = adapter.layer_norm
-        if D == 384 and adapter.ln1.weight.shape[0] == 32 and isinstance(adapter.activate, nn.GELU) and FUSE_LN_ADAPTER:
+        if tail_fused:
             # one launch: residual + strip + the adapter's LayerNorm + the adapter (csrc/adapter.hip ln_adapter_fwd_kernel)
             pd = adapter.dropout.p if self.training else 0.0
             Lo = x2.shape[1] - (P if rem != HF.ROW_IDENTITY else 0)

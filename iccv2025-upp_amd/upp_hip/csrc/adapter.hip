@@ -347,9 +347,18 @@ struct LnAdapterArgs {
     float *xo, *mean, *rstd, *s1, *out;
     int B, Lin, Lout;
     int yparts; long long ystride;      // y = sum of yparts partial matrices ystride floats apart (upp_linear_parts_f32), added in order
+    // PROP instantiation only (upp_ln_adapter_prop_fwd): the prompt-propagation step's interpolation as the row phase
+    const float *pooled, *bn_mean, *bn_rstd, *bn_gamma, *bn_beta, *w8;   // (B G2, D) pre-BatchNorm pooled rows, BatchNorm (D) x 4, weights (B, T, 8)
+    const int32_t *i2, *idx8;           // (B G2) absolute rows of the level-2 centres' own tokens, (B, T, 8) interpolation neighbours
+    int T, G2;
 };
 
-template <int D, int kFW>
+// PROP: the rows the plain kernel reads were written by prop_interp_bn_fwd_kernel (prop.hip) from x3 = x + dp_scale (y + ybias), itself
+// written by rowln_fwd_kernel.  The PROP instantiation forms both in its row phase, with their operations in their order, for the
+// rows it keeps -- the cls row (no interpolation) and the centre rows, never the prompt rows:
+//     v = x3[src] + (centre row i ? 0.3 * sum_k (BN(pooled[j_k]) + 0.3 * x3[i2[j_k]]) * w8[i][k] : 0),   j_k = idx8[i][k]
+// Everything after the row phase is the plain kernel's code.
+template <int D, int kFW, bool PROP = false>
 __global__ __launch_bounds__(64 * kFW) void ln_adapter_fwd_kernel(LnAdapterArgs a) {
     constexpr int LDH = D + 4;          // 388 = 4 (mod 64): 16-byte operand reads of 16 rows cover all banks
     constexpr int LDG = kH + 4;         // 36: same property for the 32-wide G rows
@@ -392,6 +401,8 @@ __global__ __launch_bounds__(64 * kFW) void ln_adapter_fwd_kernel(LnAdapterArgs 
         }
         float xv[RW][E], yv[RW][E];
         int rowi[RW], bi[RW];
+        [[maybe_unused]] int ci[RW];        // PROP: the row's index among its cloud's T centre rows, negative for any other row
+        [[maybe_unused]] float pa[RW][E];   // PROP: the interpolation term of the row
 #pragma unroll
         for (int q = 0; q < RW; ++q) {
             const int row = min(row0 + wave * RW + q, R - 1);
@@ -399,6 +410,7 @@ __global__ __launch_bounds__(64 * kFW) void ln_adapter_fwd_kernel(LnAdapterArgs 
             const int src = a.mode == 3 ? (t == 0 ? 0 : t + a.P) : (a.mode == 4 ? t + a.P : t);
             const size_t off = ((size_t)b * a.Lin + src) * D;
             rowi[q] = row; bi[q] = b;
+            if constexpr (PROP) ci[q] = src - (a.Lin - a.T);
 #pragma unroll
             for (int e = 0; e < E; ++e) {
                 xv[q][e] = a.x[off + lane + 64 * e];
@@ -412,6 +424,56 @@ __global__ __launch_bounds__(64 * kFW) void ln_adapter_fwd_kernel(LnAdapterArgs 
                 for (int e = 0; e < E; ++e) yv[q][e] += yp[e];
             }
         }
+        if constexpr (PROP) {
+            constexpr int kNb = 8, EC = 3;      // 8 neighbours; EC column slots of the 8 x 3 gathered rows in flight at a time
+            static_assert(E % EC == 0, "shape");
+            float mu[E], rs[E], ga[E], be[E];
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                mu[e] = a.bn_mean[lane + 64 * e]; rs[e] = a.bn_rstd[lane + 64 * e];
+                ga[e] = a.bn_gamma[lane + 64 * e]; be[e] = a.bn_beta[lane + 64 * e];
+            }
+#pragma unroll
+            for (int q = 0; q < RW; ++q) {
+                float acc[E];
+#pragma unroll
+                for (int e = 0; e < E; ++e) acc[e] = 0.0f;
+                if (ci[q] >= 0) {               // wave-uniform
+                    int j[kNb], cr[kNb];
+                    float w[kNb], scr[kNb];
+                    const size_t tok = ((size_t)bi[q] * a.T + ci[q]) * kNb;
+#pragma unroll
+                    for (int k = 0; k < kNb; ++k) { j[k] = a.idx8[tok + k]; w[k] = a.w8[tok + k]; }
+#pragma unroll
+                    for (int k = 0; k < kNb; ++k) cr[k] = a.i2[bi[q] * a.G2 + j[k]];
+#pragma unroll
+                    for (int k = 0; k < kNb; ++k) scr[k] = a.u ? floorf(a.keep + a.u[cr[k] / a.Lin]) / a.keep : 1.0f;   // the sample of the gathered row
+#pragma unroll
+                    for (int h = 0; h < E; h += EC) {
+                        float lv[EC][kNb], cx[EC][kNb], cy[EC][kNb];
+#pragma unroll
+                        for (int e = 0; e < EC; ++e)
+#pragma unroll
+                            for (int k = 0; k < kNb; ++k) {
+                                const int c = lane + 64 * (h + e);
+                                lv[e][k] = a.pooled[((size_t)bi[q] * a.G2 + j[k]) * D + c];
+                                cx[e][k] = a.x[(size_t)cr[k] * D + c];
+                                cy[e][k] = a.y[(size_t)cr[k] * D + c];
+                            }
+#pragma unroll
+                        for (int e = 0; e < EC; ++e)
+#pragma unroll
+                            for (int k = 0; k < kNb; ++k) {
+                                const float cv = __builtin_fmaf(cy[e][k] + ybv[h + e], scr[k], cx[e][k]);
+                                const float lcv = ((lv[e][k] - mu[h + e]) * rs[h + e]) * ga[h + e] + be[h + e];
+                                acc[h + e] += (lcv + 0.3f * cv) * w[k];
+                            }
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < E; ++e) pa[q][e] = ci[q] >= 0 ? 0.3f * acc[e] : 0.0f;
+            }
+        }
 #pragma unroll
         for (int q = 0; q < RW; ++q) {
             const int rr = wave * RW + q;
@@ -423,6 +485,7 @@ __global__ __launch_bounds__(64 * kFW) void ln_adapter_fwd_kernel(LnAdapterArgs 
             for (int e = 0; e < E; ++e) {
                 float val = xv[q][e];
                 if (a.y) val = __builtin_fmaf(yv[q][e] + ybv[e], sc, val);
+                if constexpr (PROP) val = val + pa[q][e];
                 v[e] = val;
                 s += val;
             }
@@ -929,6 +992,24 @@ extern "C" int upp_ln_adapter_fwd(const float *x, const float *y, const float *y
                                   float *out, int B, int Lin, int Lout, int D, int H, void *stream) {
     return ln_adapter_fwd_impl(x, y, 1, 0, ybias, u, keep, mode, P, gamma, beta, eps, W1, b1, W2, b2, ud, p, scale, xo, mean, rstd, s1, out, B, Lin,
                                     Lout, D, H, stream);
+}
+
+extern "C" int upp_ln_adapter_prop_fwd(const float *x, const float *y, const float *ybias, const float *u, float keep, int mode, int P,
+                                       const float *pooled, const float *bn_mean, const float *bn_rstd, const float *bn_gamma,
+                                       const float *bn_beta, const int32_t *i2, const int32_t *idx8, const float *w8, int T, int G2,
+                                       const float *gamma, const float *beta, float eps, const float *W1, const float *b1,
+                                       const float *W2, const float *b2, const float *ud, float p, float scale, float *xo, float *mean,
+                                       float *rstd, float *s1, float *out, int B, int Lin, int Lout, int D, int H, void *stream) {
+    if (!x || !y || !pooled || !bn_mean || !bn_rstd || !bn_gamma || !bn_beta || !i2 || !idx8 || !w8 || !gamma || !beta || !W1 || !b1 || !W2 ||
+        !b2 || !xo || !mean || !rstd || !s1 || !out || B < 0 || Lin < 1 || Lout < 1 || T < 1 || T > Lin || G2 < 1 || !(keep > 0.0f))
+        return UPP_E_BADARG;
+    if (D != 384 || H != kH) return UPP_E_RANGE;
+    if (!(mode == 0 || mode == 3 || mode == 4) || P < 0 || (mode == 0 && Lout != Lin) || (mode != 0 && Lout != Lin - P)) return UPP_E_BADARG;
+    if (B == 0) return 0;
+    LnAdapterArgs a{x, y, ybias, u, keep, mode, P, gamma, beta, eps, W1, b1, W2, b2, ud, p, scale, xo, mean, rstd, s1, out, B, Lin, Lout, 1, 0,
+                    pooled, bn_mean, bn_rstd, bn_gamma, bn_beta, w8, i2, idx8, T, G2};
+    hipLaunchKernelGGL((ln_adapter_fwd_kernel<384, 8, true>), dim3((B * Lout + kFR - 1) / kFR), dim3(64 * 8), 0, (hipStream_t)stream, a);
+    return upp_launch_status();
 }
 
 static int adapter_bwd_launch(const float *g_out, const float *ha, const float *mean, const float *rstd, const float *gamma,

@@ -668,6 +668,166 @@ __global__ __launch_bounds__(256) void prop_x_csr_kernel(const float *__restrict
     for (int e = 0; e < kMaxE; ++e) { const int c = lane + 64 * e; if (c < D) g_X[(size_t)r * D + c] = acc[e]; }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The step with the MLP residual of the block folded in (upp_prop_res_pool_fwd / upp_prop_res_bwd).  In a prompted block X is
+//     x3[r] = x2[r] + dp_scale(u_dp, r / Lp) * (m[r] + mbias)          (rowln_fwd_kernel without a LayerNorm, block.hip)
+// and was written by a launch of its own only to be gathered here.  The two kernels below are prop_pool_stats_kernel and
+// prop_x_csr_kernel with that row formed (forward) / its two gradients written (backward) in place: the same operations in the
+// same order, so every output is bit-identical to the composition with the row kernels.  They are kernels of their own so that
+// the plain ones keep their code.
+__device__ __forceinline__ float res_scale(const float *u_dp, float keep_dp, int b) {
+    return u_dp ? floorf(keep_dp + u_dp[b]) / keep_dp : 1.0f;
+}
+
+__global__ __launch_bounds__(256) void prop_pool_res_stats_kernel(const float *__restrict__ x2, const float *__restrict__ m,
+                                                                  const float *__restrict__ mbias, const float *__restrict__ u_dp,
+                                                                  float keep_dp, int Lp, const int32_t *__restrict__ i1,
+                                                                  const float *__restrict__ u, float keep, float *__restrict__ pooled,
+                                                                  uint8_t *__restrict__ amax, float *__restrict__ part, int groups, int D) {
+    const int wgx = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);
+    __shared__ float sh[4][64 * kMaxE];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = wgx * 4 + wave;
+    if (g < groups) {
+        const float f = 1.0f + (u ? floorf(keep + u[g]) / keep : 1.0f);
+        int rows8[kNb];
+        float sc[kNb];
+#pragma unroll
+        for (int k = 0; k < kNb; ++k) rows8[k] = i1[g * kNb + k];
+#pragma unroll
+        for (int k = 0; k < kNb; ++k) sc[k] = res_scale(u_dp, keep_dp, rows8[k] / Lp);   // the sample of the gathered row, not of the group
+        float xv[kNb][kMaxE], mv[kNb][kMaxE], mb[kMaxE];
+#pragma unroll
+        for (int k = 0; k < kNb; ++k)
+#pragma unroll
+            for (int e = 0; e < kMaxE; ++e) {
+                const size_t o = (size_t)rows8[k] * D + min(lane + 64 * e, D - 1);
+                xv[k][e] = x2[o]; mv[k][e] = m[o];
+            }
+#pragma unroll
+        for (int e = 0; e < kMaxE; ++e) mb[e] = mbias ? mbias[min(lane + 64 * e, D - 1)] : 0.0f;
+#pragma unroll
+        for (int e = 0; e < kMaxE; ++e) {
+            float mx = -__builtin_inff(), sm = 0.0f;
+            int am = 0;
+#pragma unroll
+            for (int k = 0; k < kNb; ++k) {
+                const float v = __builtin_fmaf(mv[k][e] + mb[e], sc[k], xv[k][e]) * f;
+                if (v > mx) { mx = v; am = k; }
+                sm += v;
+            }
+            const int c = lane + 64 * e;
+            const float pv = mx + sm * 0.125f;
+            if (c < D) { pooled[(size_t)g * D + c] = pv; amax[(size_t)g * D + c] = (uint8_t)am; sh[wave][c] = pv; }
+        }
+    }
+    __syncthreads();
+    const int nw = min(4, groups - (int)wgx * 4);
+    for (int c = threadIdx.x; c < D; c += 256) {
+        float sum = 0.0f;
+        for (int w = 0; w < nw; ++w) sum += sh[w][c];
+        const float mean = sum / (float)nw;
+        float m2 = 0.0f;
+        for (int w = 0; w < nw; ++w) { const float dv = sh[w][c] - mean; m2 = __builtin_fmaf(dv, dv, m2); }
+        part[((size_t)wgx * 2 + 0) * D + c] = sum;
+        part[((size_t)wgx * 2 + 1) * D + c] = m2;
+    }
+}
+
+// prop_x_csr_kernel writing the gradient of x3 as the two gradients of the residual: g_x2[r] = g_X[r], g_m[r] = g_X[r] * dp_scale
+// (rowln_bwd_kernel without a LayerNorm: a copy and a scale of the row this kernel holds in registers).
+__global__ __launch_bounds__(256) void prop_x_csr_res_kernel(const float *__restrict__ g_out, const float *__restrict__ g_c2,
+                                                             const float *__restrict__ pooled, const uint8_t *__restrict__ amax,
+                                                             const float *__restrict__ mean, const float *__restrict__ rstd,
+                                                             const float *__restrict__ gamma, const float *__restrict__ g_gamma,
+                                                             const float *__restrict__ g_beta, const float *__restrict__ u, float keep,
+                                                             const int32_t *__restrict__ start1, const int32_t *__restrict__ perm1,
+                                                             const int32_t *__restrict__ start2, const int32_t *__restrict__ perm2,
+                                                             const float *__restrict__ u_dp, float keep_dp, int Lp,
+                                                             float *__restrict__ g_x2, float *__restrict__ g_m, int rows, int groups, int D,
+                                                             int training) {
+    const int wgx = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);
+    const int lane = threadIdx.x & 63;
+    const int r = wgx * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (r >= rows) return;
+    const int s1 = start1[r], e1 = start1[r + 1], s2 = start2[r], e2 = start2[r + 1];
+    const float sc = res_scale(u_dp, keep_dp, r / Lp);
+    int cc[kMaxE];
+    float acc[kMaxE], mu[kMaxE], rs[kMaxE], ga[kMaxE], c1[kMaxE], c2[kMaxE];
+    const float inv_n = 1.0f / (float)groups;
+#pragma unroll
+    for (int e = 0; e < kMaxE; ++e) {
+        cc[e] = min(lane + 64 * e, D - 1);
+        acc[e] = g_out[(size_t)r * D + cc[e]];
+        mu[e] = mean[cc[e]]; rs[e] = rstd[cc[e]]; ga[e] = gamma[cc[e]];
+        c1[e] = 0.0f; c2[e] = 0.0f;
+    }
+    if (training) {
+#pragma unroll
+        for (int e = 0; e < kMaxE; ++e) { c1[e] = g_beta[cc[e]]; c2[e] = g_gamma[cc[e]]; }
+    }
+#pragma unroll
+    for (int e = 0; e < kMaxE; ++e) { c1[e] *= inv_n; c2[e] *= inv_n; }
+    for (int h0 = s2; h0 < e2; h0 += 2) {
+        const int m0 = perm2[h0], m1 = perm2[min(h0 + 1, e2 - 1)];
+        float a0[kMaxE], a1[kMaxE];
+#pragma unroll
+        for (int e = 0; e < kMaxE; ++e) { a0[e] = g_c2[(size_t)m0 * D + cc[e]]; a1[e] = g_c2[(size_t)m1 * D + cc[e]]; }
+        const float f1 = h0 + 1 < e2 ? 0.3f : 0.0f;
+#pragma unroll
+        for (int e = 0; e < kMaxE; ++e) { acc[e] += 0.3f * a0[e]; acc[e] += f1 * a1[e]; }
+    }
+    auto add_entries = [&](int b0, int b1) {
+        for (int h0 = b0; h0 < b1; h0 += 4) {
+            int g[4], k[4];
+            float f[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) { const int q = perm1[min(h0 + t, b1 - 1)]; g[t] = q / kNb; k[t] = q - g[t] * kNb; }
+#pragma unroll
+            for (int t = 0; t < 4; ++t) f[t] = h0 + t < b1 ? 1.0f + (u ? floorf(keep + u[g[t]]) / keep : 1.0f) : 0.0f;
+            float gl[kMaxE][4], pv[kMaxE][4];
+            int am[kMaxE][4];
+#pragma unroll
+            for (int e = 0; e < kMaxE; ++e)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const size_t o = (size_t)g[t] * D + cc[e];
+                    gl[e][t] = g_c2[o]; pv[e][t] = pooled[o]; am[e][t] = amax[o];
+                }
+#pragma unroll
+            for (int e = 0; e < kMaxE; ++e)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const float xh = (pv[e][t] - mu[e]) * rs[e];
+                    const float gp = (ga[e] * rs[e]) * (training ? gl[e][t] - c1[e] - xh * c2[e] : gl[e][t]);
+                    acc[e] += gp * f[t] * (0.125f + (am[e][t] == k[t] ? 1.0f : 0.0f));
+                }
+        }
+    };
+    constexpr int kRowChunk = 64;                             // long rows: chunked partial sums, as prop_x_csr_kernel
+    if (e1 - s1 <= kRowChunk) {
+        add_entries(s1, e1);
+    } else {
+        float head[kMaxE];
+#pragma unroll
+        for (int e = 0; e < kMaxE; ++e) head[e] = 0.0f;
+        for (int c0 = s1; c0 < e1; c0 += kRowChunk) {
+            if (c0 > s1) {
+#pragma unroll
+                for (int e = 0; e < kMaxE; ++e) { head[e] += acc[e]; acc[e] = 0.0f; }
+            }
+            add_entries(c0, min(e1, c0 + kRowChunk));
+        }
+#pragma unroll
+        for (int e = 0; e < kMaxE; ++e) acc[e] += head[e];
+    }
+#pragma unroll
+    for (int e = 0; e < kMaxE; ++e) {
+        const int c = lane + 64 * e;
+        if (c < D) { g_x2[(size_t)r * D + c] = acc[e]; g_m[(size_t)r * D + c] = acc[e] * sc; }
+    }
+}
+
 // Index lists of the propagation step for one forward, in ONE launch (the reference spends ~30 small torch kernels on
 // them: index arithmetic, square_distance, a full sort, the weight normalisation):
 //   i1a / i2a : absolute rows of the (B*L') token matrix for the level-1 neighbour lists / level-2 centres, from the
@@ -964,6 +1124,42 @@ extern "C" int upp_prop_bwd(const float *g_out, const float *pooled, const uint8
     hipLaunchKernelGGL(prop_bn_grad_kernel, dim3((D + 63) / 64), dim3(256), 0, st, part, wgs, D, g_gamma, g_beta);
     hipLaunchKernelGGL(prop_x_csr_kernel, rows_grid((long long)B * Lp), dim3(256), 0, st, g_out, g_c2, pooled, amax, mean, rstd, gamma,
                        g_gamma, g_beta, u, keep, start1, perm1, start2, perm2, g_X, B * Lp, groups, D, training);
+    return upp_launch_status();
+}
+
+extern "C" int upp_prop_res_pool_fwd(const float *x2, const float *m, const float *mbias, const float *u_dp, float keep_dp,
+                                     const int32_t *i1, const float *u, float keep, float *running_mean, float *running_var,
+                                     float momentum, float eps, int training, float *pooled, uint8_t *amax, float *part, float *mean,
+                                     float *rstd, int B, int Lp, int G2, int D, void *stream) {
+    if (!x2 || !m || !i1 || !pooled || !amax || !part || !mean || !rstd) return UPP_E_BADARG;
+    if (B < 1 || Lp < 1 || G2 < 1 || D < 1 || !(keep_dp > 0.0f) || !(keep > 0.0f)) return UPP_E_BADARG;
+    if (!training && (!running_mean || !running_var)) return UPP_E_BADARG;
+    if (D > 64 * kMaxE) return UPP_E_RANGE;
+    hipStream_t st = (hipStream_t)stream;
+    const int groups = B * G2, wgs = (groups + 3) / 4;
+    hipLaunchKernelGGL(prop_pool_res_stats_kernel, dim3(wgs), dim3(256), 0, st, x2, m, mbias, u_dp, keep_dp, Lp, i1, u, keep, pooled, amax,
+                       part, groups, D);
+    upp_bn_finalize_launch(part, wgs, 4, groups, D, training, momentum, eps, running_mean, running_var, mean, rstd, st);
+    return upp_launch_status();
+}
+
+extern "C" int upp_prop_res_bwd(const float *g_out, const float *pooled, const uint8_t *amax, const float *mean, const float *rstd,
+                                const float *gamma, const float *u, float keep, const float *w8, const int32_t *start1,
+                                const int32_t *perm1, const int32_t *start2, const int32_t *perm2, const int32_t *start8,
+                                const int32_t *perm8, int training, const float *u_dp, float keep_dp, float *g_c2, float *part,
+                                float *g_gamma, float *g_beta, float *g_x2, float *g_m, int B, int Lp, int T, int G2, int D, void *stream) {
+    if (!g_out || !pooled || !amax || !mean || !rstd || !gamma || !w8 || !start1 || !perm1 || !start2 || !perm2 || !start8 || !perm8 ||
+        !g_c2 || !part || !g_gamma || !g_beta || !g_x2 || !g_m)
+        return UPP_E_BADARG;
+    if (B < 1 || Lp < T || T < 1 || G2 < 1 || D < 1 || !(keep_dp > 0.0f)) return UPP_E_BADARG;
+    if (D > 64 * kMaxE) return UPP_E_RANGE;
+    hipStream_t st = (hipStream_t)stream;
+    const int groups = B * G2, wgs = (groups + 3) / 4;
+    hipLaunchKernelGGL(prop_c2_csr_kernel, dim3(wgs), dim3(256), 0, st, g_out, start8, perm8, w8, pooled, mean, rstd, g_c2, part, B, Lp, T,
+                       G2, D);
+    hipLaunchKernelGGL(prop_bn_grad_kernel, dim3((D + 63) / 64), dim3(256), 0, st, part, wgs, D, g_gamma, g_beta);
+    hipLaunchKernelGGL(prop_x_csr_res_kernel, rows_grid((long long)B * Lp), dim3(256), 0, st, g_out, g_c2, pooled, amax, mean, rstd, gamma,
+                       g_gamma, g_beta, u, keep, start1, perm1, start2, perm2, u_dp, keep_dp, Lp, g_x2, g_m, B * Lp, groups, D, training);
     return upp_launch_status();
 }
 

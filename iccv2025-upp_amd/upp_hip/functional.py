@@ -2153,6 +2153,52 @@ class deterministic:
         return False
 
 
+def _ln_adapter_backward(saved, dims, meta, param_ptrs, g_out, need_x, need_y, need_p):
+    """Backward of the block tail (ln_adapter_fwd and its PROP form write the same saved tensors) -> (g_x, g_y, g_gamma, g_beta, gW1, gb1,
+    gW2, gb2).  need_p: which of (gamma, beta, W1, b1, W2, b2) want a gradient; u / keep / has_y describe the residual in front of the rows."""
+    xo, mean, rstd, gamma, beta, u, s1, W1, W2, ud = saved
+    B, Lin, Lout, D, P, mode = dims
+    keep, pd, scale, has_y = meta
+    g_out = g_out.contiguous()
+    need_ln = need_p[0] or need_p[1]
+    need_ad = need_p[2] or need_p[3] or need_p[4] or need_p[5]
+    p_gamma, p_beta, pW1, pb1, pW2, pb2 = param_ptrs
+    H = W1.shape[0]
+    # inside a deferred scope (TrainStep) with all four adapter buffers registered: per-row factors now, the weight gradients of every
+    # block in one launch at scope exit
+    factors = (FUSE_TAIL_BACKWARD and ADAPTER_FACTORS and need_p[2] and need_p[3] and need_p[4] and need_p[5]
+               and _DEFERRED.targets is not None and all(_DEFERRED.targets.get(p_) is not None for p_ in (pW1, pb1, pW2, pb2)))
+    if factors:
+        g_x, g_y, fac, ln_part = ops.ln_adapter_bwd_fused(g_out, xo, mean, rstd, gamma, beta, s1, W1, W2, ud, pd, scale, u, keep, mode, P, Lin,
+                                                          need_x, has_y and need_y, True, need_ln, factors=True)
+        R = B * Lout
+        factors = _DEFERRED.adapter((pW1, pW2, pb1, pb2), (H * D, H * D, H, D),
+                                    (xo.view(R, D), mean.view(R), rstd.view(R), gamma, beta, g_out.view(R, D), fac, scale))
+        if not factors:
+            raise RuntimeError("ln_adapter backward: the registered adapter gradient buffers do not match the adapter's shapes")
+        part = None
+    elif FUSE_TAIL_BACKWARD:
+        g_x, g_y, part, ln_part = ops.ln_adapter_bwd_fused(g_out, xo, mean, rstd, gamma, beta, s1, W1, W2, ud, pd, scale, u, keep, mode, P, Lin,
+                                                           need_x, has_y and need_y, need_ad, need_ln)
+    else:       # the two kernels of the unfused path (kept: tests compare the fused launch against them)
+        g_ha, part = ops.ln_adapter_bwd(g_out, xo, mean, rstd, gamma, beta, s1, W1, W2, ud, pd, scale)
+        g_x, _, g_y, ln_part = ops.rowln_bwd(g_out, g_ha, xo, mean, rstd, gamma, mode, u, keep, B, Lin, Lout, D, P,
+                                             need_x=need_x, need_prompt=False, need_y=has_y and need_y, need_ln_part=need_ln)
+    g_gamma = g_beta = gW1 = gb1 = gW2 = gb2 = None
+    if need_ln:
+        _, g_gamma = _DEFERRED.reduce(p_gamma, ln_part, 0, D)
+        _, g_beta = _DEFERRED.reduce(p_beta, ln_part, D, D)
+    if need_ad and not factors:
+        _, gW1 = _DEFERRED.reduce(pW1, part, 0, H * D)
+        _, gW2 = _DEFERRED.reduce(pW2, part, H * D, H * D)
+        _, gb1 = _DEFERRED.reduce(pb1, part, 2 * H * D, H)
+        _, gb2 = _DEFERRED.reduce(pb2, part, 2 * H * D + H, D)
+        gW1 = gW1.view(H, D) if gW1 is not None else None
+        gW2 = gW2.view(D, H) if gW2 is not None else None
+    return (g_x, g_y, g_gamma if need_p[0] else None, g_beta if need_p[1] else None, gW1 if need_p[2] else None, gb1 if need_p[3] else None,
+            gW2 if need_p[4] else None, gb2 if need_p[5] else None)
+
+
 class _LnAdapter(Function):
     """The tail of a block in one launch: rows = strip(x + dp_scale(u) (y + ybias)), out = rows + scale * adapter(LayerNorm(rows)).
     Forward: upp_ln_adapter_fwd.  Backward: upp_ln_adapter_bwd (the adapter's, rebuilding the LayerNorm output from the saved
@@ -2173,49 +2219,10 @@ class _LnAdapter(Function):
 
     @staticmethod
     def backward(ctx, g_out):
-        xo, mean, rstd, gamma, beta, u, s1, W1, W2, ud = ctx.saved_tensors
-        B, Lin, Lout, D, P, mode = ctx.dims
-        keep, pd, scale, has_y = ctx.meta
         need = ctx.needs_input_grad
-        g_out = g_out.contiguous()
-        need_ln = need[7] or need[8]
-        need_ad = need[10] or need[11] or need[12] or need[13]
-        p_gamma, p_beta, pW1, pb1, pW2, pb2 = ctx.param_ptrs
-        H = W1.shape[0]
-        # inside a deferred scope (TrainStep) with all four adapter buffers registered: per-row factors now, the weight gradients of every
-        # block in one launch at scope exit
-        factors = (FUSE_TAIL_BACKWARD and ADAPTER_FACTORS and need[10] and need[11] and need[12] and need[13]
-                   and _DEFERRED.targets is not None and all(_DEFERRED.targets.get(p_) is not None for p_ in (pW1, pb1, pW2, pb2)))
-        if factors:
-            g_x, g_y, fac, ln_part = ops.ln_adapter_bwd_fused(g_out, xo, mean, rstd, gamma, beta, s1, W1, W2, ud, pd, scale, u, keep, mode, P, Lin,
-                                                              need[0], has_y and need[1], True, need_ln, factors=True)
-            R = B * Lout
-            factors = _DEFERRED.adapter((pW1, pW2, pb1, pb2), (H * D, H * D, H, D),
-                                        (xo.view(R, D), mean.view(R), rstd.view(R), gamma, beta, g_out.view(R, D), fac, scale))
-            if not factors:
-                raise RuntimeError("ln_adapter backward: the registered adapter gradient buffers do not match the adapter's shapes")
-            part = None
-        elif FUSE_TAIL_BACKWARD:
-            g_x, g_y, part, ln_part = ops.ln_adapter_bwd_fused(g_out, xo, mean, rstd, gamma, beta, s1, W1, W2, ud, pd, scale, u, keep, mode, P, Lin,
-                                                               need[0], has_y and need[1], need_ad, need_ln)
-        else:       # the two kernels of the unfused path (kept: tests compare the fused launch against them)
-            g_ha, part = ops.ln_adapter_bwd(g_out, xo, mean, rstd, gamma, beta, s1, W1, W2, ud, pd, scale)
-            g_x, _, g_y, ln_part = ops.rowln_bwd(g_out, g_ha, xo, mean, rstd, gamma, mode, u, keep, B, Lin, Lout, D, P,
-                                                 need_x=need[0], need_prompt=False, need_y=has_y and need[1], need_ln_part=need_ln)
-        g_gamma = g_beta = gW1 = gb1 = gW2 = gb2 = None
-        if need_ln:
-            _, g_gamma = _DEFERRED.reduce(p_gamma, ln_part, 0, D)
-            _, g_beta = _DEFERRED.reduce(p_beta, ln_part, D, D)
-        if need_ad and not factors:
-            _, gW1 = _DEFERRED.reduce(pW1, part, 0, H * D)
-            _, gW2 = _DEFERRED.reduce(pW2, part, H * D, H * D)
-            _, gb1 = _DEFERRED.reduce(pb1, part, 2 * H * D, H)
-            _, gb2 = _DEFERRED.reduce(pb2, part, 2 * H * D + H, D)
-            gW1 = gW1.view(H, D) if gW1 is not None else None
-            gW2 = gW2.view(D, H) if gW2 is not None else None
-        return (g_x if need[0] else None, g_y, None, None, None, None, None, g_gamma if need[7] else None, g_beta if need[8] else None,
-                None, gW1 if need[10] else None, gb1 if need[11] else None, gW2 if need[12] else None, gb2 if need[13] else None,
-                None, None, None)
+        g_x, g_y, g_gamma, g_beta, gW1, gb1, gW2, gb2 = _ln_adapter_backward(ctx.saved_tensors, ctx.dims, ctx.meta, ctx.param_ptrs, g_out,
+                                                                             need[0], need[1], (need[7], need[8]) + tuple(need[10:14]))
+        return (g_x if need[0] else None, g_y, None, None, None, None, None, g_gamma, g_beta, None, gW1, gb1, gW2, gb2, None, None, None)
 
 
 # (round 5 also let this launch compute the NEXT block's head -- upp_ln_adapter_fwd_next: bit-identical, and slower: the tail grew by what the
@@ -2227,6 +2234,68 @@ def ln_adapter(x, y, ybias, u, keep, mode, P, ln, W1, b1, W2, b2, ud=None, pd=0.
         raise ValueError("ybias is the frozen bias of the Linear that produced y")
     return _LnAdapter.apply(x, y, ybias, u, float(keep), int(mode), int(P), ln.weight, ln.bias, float(ln.eps), W1, b1, W2, b2, ud,
                             float(pd), float(scale))
+
+
+class _PropTail(Function):
+    """A prompted block from the fc2 product to the adapter output in 3 launches forward and 4 backward:
+        x3 = x2 + dp_scale(u_dp) (m + mb);  x3' = propagate(x3);  out = ln_adapter(strip(x3'))
+    Forward: upp_prop_res_pool_fwd (pool + statistics on rows of x3 formed where they are gathered | BatchNorm finalize) and
+    upp_ln_adapter_prop_fwd (the interpolation as the tail's row phase); neither x3 nor x3' is stored.  Backward: upp_ln_adapter_bwd_fused,
+    then upp_prop_res_bwd, whose last launch writes the gradients of x2 and m.  Bit-identical to rowln -> propagate -> ln_adapter."""
+
+    @staticmethod
+    def forward(ctx, x2, m, mb, u_dp, keep_dp, mode, P, index, u_g, keep_g, bn_gamma, bn_beta, running_mean, running_var, momentum, bn_eps,
+                training, ln_gamma, ln_beta, ln_eps, W1, b1, W2, b2, ud, pd, scale):
+        x2, m = x2.contiguous(), m.contiguous()
+        B, Lin, D = x2.shape
+        Lout = Lin - P if mode in (ROW_STRIP_CLS, ROW_STRIP) else Lin
+        w8 = index.w8
+        _, pooled, amax, bn_mean, bn_rstd = ops.prop_fwd(x2, index.i1, u_g, keep_g, index.i2, index.idx8, w8, bn_gamma, bn_beta, running_mean,
+                                                         running_var, momentum, bn_eps, training, B, Lin, index.T, index.G2,
+                                                         residual=(m, mb, u_dp, keep_dp))
+        out, xo, mean, rstd, s1 = ops.ln_adapter_prop_fwd(x2, m, mb, u_dp, keep_dp, mode, P, pooled, bn_mean, bn_rstd, bn_gamma, bn_beta, index.i2,
+                                                          index.idx8, w8, ln_gamma, ln_beta, ln_eps, W1, b1, W2, b2, ud, pd, scale, Lout)
+        ctx.save_for_backward(xo, mean, rstd, ln_gamma, ln_beta, None, s1, W1, W2, ud, pooled, amax, bn_mean, bn_rstd, bn_gamma, u_g, w8, u_dp)
+        ctx.dims = (B, Lin, Lout, D, P, mode)
+        ctx.meta = (index, keep_g, keep_dp, pd, scale, training)
+        ctx.param_ptrs = (ln_gamma.data_ptr(), ln_beta.data_ptr(), W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr())
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        saved = ctx.saved_tensors
+        pooled, amax, bn_mean, bn_rstd, bn_gamma, u_g, w8, u_dp = saved[10:]
+        index, keep_g, keep_dp, pd, scale, training = ctx.meta
+        B, Lin = ctx.dims[0], ctx.dims[1]
+        need = ctx.needs_input_grad
+        # the tail saw x3' as its stream and no residual branch: g (B, Lin, D), zeros in the prompt rows the strip dropped
+        g, _, g_gamma, g_beta, gW1, gb1, gW2, gb2 = _ln_adapter_backward(saved[:10], ctx.dims, (1.0, pd, scale, False), ctx.param_ptrs, g_out,
+                                                                         True, False, (need[17], need[18], need[20], need[21], need[22], need[23]))
+        g_x2, g_m, g_bn_gamma, g_bn_beta = ops.prop_res_bwd(g, pooled, amax, bn_mean, bn_rstd, bn_gamma, u_g, keep_g, w8, index.csr1, index.csr2,
+                                                            index.csr8, training, u_dp, keep_dp, B, Lin, index.T, index.G2)
+        return ((g_x2 if need[0] else None, g_m if need[1] else None) + (None,) * 8 + (g_bn_gamma, g_bn_beta) + (None,) * 5
+                + (g_gamma, g_beta, None, gW1, gb1, gW2, gb2, None, None, None))
+
+
+def prop_tail_usable(x2, bn, T, P, mode):
+    """Can prop_tail serve this block (T centre rows per cloud, P prompts stripped by `mode`)?  f32 rows of D = 384 (the tail kernel), an
+    affine BatchNorm1d, a row count the CSR build takes, a strip map that keeps every centre row."""
+    B, Lin, D = x2.shape
+    return (x2.is_cuda and x2.dtype == torch.float32 and D == 384 and P > 0 and mode in (ROW_STRIP_CLS, ROW_STRIP) and bn.affine
+            and B * Lin <= 15360 and T <= Lin - P)
+
+
+def prop_tail(x2, m, mb, u_dp, keep_dp, mode, P, bn, index, u_g, keep_g, training, ln, W1, b1, W2, b2, ud=None, pd=0.0, scale=0.7):
+    """One autograd node for `rowln(x2, y=m, ybias=mb, u=u_dp, keep=keep_dp)` -> `propagate(., bn, index, u_g, keep_g, training)` ->
+    `ln_adapter(., None, None, None, 1.0, mode, P, ln, W1, b1, W2, b2, ud, pd, scale)`; index.w8 are constants of the forward (no gradient
+    to the centres: that is stage 2 of the recipe, which needs the stored rows).  Limits: prop_tail_usable."""
+    if mb is not None and torch.is_grad_enabled() and mb.requires_grad:
+        raise ValueError("mb is the frozen bias of the Linear that produced m")
+    use_batch = training or bn.running_mean is None
+    momentum = 0.0 if bn.momentum is None else bn.momentum
+    return _PropTail.apply(x2, m, mb, u_dp, float(keep_dp), int(mode), int(P), index, u_g, float(keep_g), bn.weight, bn.bias, bn.running_mean,
+                           bn.running_var, momentum, bn.eps, use_batch, ln.weight, ln.bias, float(ln.eps), W1, b1, W2, b2, ud, float(pd),
+                           float(scale))
 
 
 def adapter(ha, x, W1, b1, W2, b2, u=None, p=0.0, scale=0.7):

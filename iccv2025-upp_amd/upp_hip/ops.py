@@ -1696,7 +1696,15 @@ def prop_index(c1, c2, i1, i2, gather_idx, Lp, off, eps):
     return i1a, i2a, idx8, w8
 
 
-def prop_fwd(X, i1, u, keep, i2, idx8, w8, gamma, beta, running_mean, running_var, momentum, eps, training, B, Lp, T, G2):
+def prop_fwd(X, i1, u, keep, i2, idx8, w8, gamma, beta, running_mean, running_var, momentum, eps, training, B, Lp, T, G2, residual=None):
+    """-> (out, pooled, amax, mean, rstd); upp_prop_fwd.  residual = (m, mbias, u_dp, keep_dp): X is x2 and the step runs on the rows
+    x3 = x2 + dp_scale(u_dp) (m + mbias) without storing them (prop_res_pool_fwd): the first two launches only, out is None -- the
+    interpolation is then the row phase of ln_adapter_prop_fwd."""
+    if residual is not None:
+        m, mbias, u_dp, keep_dp = residual
+        pooled, amax, _, mean, rstd = prop_res_pool_fwd(X, m, mbias, u_dp, keep_dp, i1, u, keep, running_mean, running_var, momentum, eps,
+                                                        training, G2)
+        return None, pooled, amax, mean, rstd
     D = X.shape[-1]
     groups = B * G2
     dev = X.device
@@ -1726,6 +1734,57 @@ def prop_bwd(g_out, pooled, amax, mean, rstd, gamma, u, keep, w8, csr1, csr2, cs
           _abi.ptr(csr8[1]), int(bool(training)), _abi.ptr(g_c2), _abi.ptr(part), _abi.ptr(g_gamma), _abi.ptr(g_beta), _abi.ptr(g_X),
           B, Lp, T, G2, D)
     return g_X, g_gamma, g_beta
+
+
+def _prop_res_args(x2, m, mbias, u_dp, B, Lp, D):
+    _need_f32(x2, "x2", (B, Lp, D))
+    _need_f32(m, "m", (B, Lp, D))
+    _need_f32(mbias, "mbias", (D,), optional=True)
+    _need_f32(u_dp, "u_dp", (B,), optional=True)
+    _same_device(*[t for t in (x2, m, mbias, u_dp) if t is not None])
+
+
+def prop_res_pool_fwd(x2, m, mbias, u_dp, keep_dp, i1, u, keep, running_mean, running_var, momentum, eps, training, G2):
+    """The pool + statistics + finalize launches of prop_fwd on the rows x3 = x2 + dp_scale(u_dp) (m + mbias), formed where they are gathered
+    -> (pooled, amax, part, mean, rstd); upp_prop_res_pool_fwd."""
+    _need(x2, "x2", torch.float32, ndim=3)
+    B, Lp, D = x2.shape
+    _prop_res_args(x2, m, mbias, u_dp, B, Lp, D)
+    groups = B * G2
+    _need(i1, "i1", torch.int32)
+    if i1.numel() != groups * 8:
+        raise RuntimeError("prop_res_pool_fwd: i1 must hold 8 rows for each of the B * G2 groups")
+    _need_f32(u, "u", (groups,), optional=True)
+    dev = x2.device
+    pooled = torch.empty((groups, D), dtype=torch.float32, device=dev)
+    amax = torch.empty((groups, D), dtype=torch.uint8, device=dev)
+    part = torch.empty(_abi.load().upp_prop_part_floats(groups, D), dtype=torch.float32, device=dev)
+    mean = torch.empty(D, dtype=torch.float32, device=dev)
+    rstd = torch.empty(D, dtype=torch.float32, device=dev)
+    _call(dev, "upp_prop_res_pool_fwd", _abi.ptr(x2), _abi.ptr(m), _abi.ptr(mbias), _abi.ptr(u_dp), float(keep_dp), _abi.ptr(i1), _abi.ptr(u),
+          float(keep), _abi.ptr(running_mean), _abi.ptr(running_var), float(momentum), float(eps), int(bool(training)), _abi.ptr(pooled),
+          _abi.ptr(amax), _abi.ptr(part), _abi.ptr(mean), _abi.ptr(rstd), B, Lp, int(G2), D)
+    return pooled, amax, part, mean, rstd
+
+
+def prop_res_bwd(g_out, pooled, amax, mean, rstd, gamma, u, keep, w8, csr1, csr2, csr8, training, u_dp, keep_dp, B, Lp, T, G2):
+    """prop_bwd with the gradient of x3 leaving as the residual's two gradients -> (g_x2, g_m, g_gamma, g_beta); upp_prop_res_bwd."""
+    D = g_out.shape[-1]
+    _need_f32(g_out, "g_out", (B, Lp, D))
+    _need_f32(u_dp, "u_dp", (B,), optional=True)
+    groups = B * G2
+    dev = g_out.device
+    g_c2 = torch.empty((groups, D), dtype=torch.float32, device=dev)
+    part = torch.empty(_abi.load().upp_prop_part_floats(groups, D), dtype=torch.float32, device=dev)
+    g_gamma = torch.empty(D, dtype=torch.float32, device=dev)
+    g_beta = torch.empty(D, dtype=torch.float32, device=dev)
+    g_x2 = torch.empty_like(g_out)
+    g_m = torch.empty_like(g_out)
+    _call(dev, "upp_prop_res_bwd", _abi.ptr(g_out), _abi.ptr(pooled), _abi.ptr(amax), _abi.ptr(mean), _abi.ptr(rstd), _abi.ptr(gamma),
+          _abi.ptr(u), float(keep), _abi.ptr(w8), _abi.ptr(csr1[0]), _abi.ptr(csr1[1]), _abi.ptr(csr2[0]), _abi.ptr(csr2[1]),
+          _abi.ptr(csr8[0]), _abi.ptr(csr8[1]), int(bool(training)), _abi.ptr(u_dp), float(keep_dp), _abi.ptr(g_c2), _abi.ptr(part),
+          _abi.ptr(g_gamma), _abi.ptr(g_beta), _abi.ptr(g_x2), _abi.ptr(g_m), B, Lp, T, G2, D)
+    return g_x2, g_m, g_gamma, g_beta
 
 
 def prop_w8_grad(g_out, X, pooled, bn_stats, i2, idx8, B, Lp, T, G2):
@@ -2386,6 +2445,40 @@ def ln_adapter_fwd(x, y, ybias, u, keep, mode, P, gamma, beta, eps, W1, b1, W2, 
     _call(dev, "upp_ln_adapter_fwd", _abi.ptr(x), _abi.ptr(y), _abi.ptr(ybias), _abi.ptr(u), float(keep), int(mode), int(P), _abi.ptr(gamma),
           _abi.ptr(beta), float(eps), _abi.ptr(W1), _abi.ptr(b1), _abi.ptr(W2), _abi.ptr(b2), _abi.ptr(ud), float(p), float(scale),
           _abi.ptr(xo), _abi.ptr(mean), _abi.ptr(rstd), _abi.ptr(s1), _abi.ptr(out), B, Lin, Lout, D, H)
+    return out, xo, mean, rstd, s1
+
+
+def ln_adapter_prop_fwd(x2, m, mbias, u_dp, keep_dp, mode, P, pooled, bn_mean, bn_rstd, bn_gamma, bn_beta, i2, idx8, w8, gamma, beta, eps,
+                        W1, b1, W2, b2, ud, p, scale, Lout):
+    """ln_adapter_fwd of a prompted block with the propagation step's interpolation (and the MLP residual under it) as its row phase
+    -> (out, xo, mean, rstd, s1); upp_ln_adapter_prop_fwd.  pooled, bn_mean, bn_rstd: what prop_res_pool_fwd wrote."""
+    _need(x2, "x2", torch.float32, ndim=3)
+    B, Lin, D = x2.shape
+    H = W1.shape[0]
+    dev = x2.device
+    _prop_res_args(x2, m, mbias, u_dp, B, Lin, D)
+    for t_, n_, shp in ((gamma, "gamma", (D,)), (beta, "beta", (D,)), (W1, "W1", (H, D)), (b1, "b1", (H,)), (W2, "W2", (D, H)), (b2, "b2", (D,)),
+                        (bn_mean, "bn_mean", (D,)), (bn_rstd, "bn_rstd", (D,)), (bn_gamma, "bn_gamma", (D,)), (bn_beta, "bn_beta", (D,))):
+        _need_f32(t_, n_, shp)
+    _need(idx8, "idx8", torch.int32, ndim=3, last=8)
+    _need(i2, "i2", torch.int32)
+    T = idx8.shape[1]
+    if idx8.shape[0] != B or i2.numel() % B != 0:
+        raise RuntimeError("ln_adapter_prop_fwd: idx8 must be (B, T, 8) and i2 (B * G2)")
+    G2 = i2.numel() // B
+    _need_f32(w8, "w8", (B, T, 8))
+    _need_f32(pooled, "pooled", (B * G2, D))
+    _need_f32(ud, "ud", (B * Lout, H), optional=True)
+    _same_device(*[t for t in (x2, pooled, bn_mean, bn_rstd, bn_gamma, bn_beta, i2, idx8, w8, gamma, beta, W1, b1, W2, b2, ud) if t is not None])
+    xo = torch.empty((B, Lout, D), dtype=torch.float32, device=dev)
+    out = torch.empty((B, Lout, D), dtype=torch.float32, device=dev)
+    mean = torch.empty((B, Lout), dtype=torch.float32, device=dev)
+    rstd = torch.empty((B, Lout), dtype=torch.float32, device=dev)
+    s1 = torch.empty((B * Lout, H), dtype=torch.float32, device=dev)
+    _call(dev, "upp_ln_adapter_prop_fwd", _abi.ptr(x2), _abi.ptr(m), _abi.ptr(mbias), _abi.ptr(u_dp), float(keep_dp), int(mode), int(P),
+          _abi.ptr(pooled), _abi.ptr(bn_mean), _abi.ptr(bn_rstd), _abi.ptr(bn_gamma), _abi.ptr(bn_beta), _abi.ptr(i2), _abi.ptr(idx8), _abi.ptr(w8),
+          T, G2, _abi.ptr(gamma), _abi.ptr(beta), float(eps), _abi.ptr(W1), _abi.ptr(b1), _abi.ptr(W2), _abi.ptr(b2), _abi.ptr(ud), float(p),
+          float(scale), _abi.ptr(xo), _abi.ptr(mean), _abi.ptr(rstd), _abi.ptr(s1), _abi.ptr(out), B, Lin, Lout, D, H)
     return out, xo, mean, rstd, s1
 
 

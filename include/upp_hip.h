@@ -615,6 +615,21 @@ int upp_prop_bwd(const float *g_out, const float *pooled, const uint8_t *amax, c
                  const int32_t *perm1, const int32_t *start2, const int32_t *perm2, const int32_t *start8,
                  const int32_t *perm8, int training, float *g_c2, float *part, float *g_gamma, float *g_beta, float *g_X,
                  int B, int Lp, int T, int G2, int D, void *stream);
+/* The step of a prompted block with the MLP residual folded in: X is never stored, each of its rows is formed where it is read as
+ *   x3[r] = x2[r] + dp_scale(u_dp[r / Lp]) * (m[r] + mbias)        (upp_rowln_fwd without a LayerNorm; mbias, u_dp may be NULL)
+ *   upp_prop_res_pool_fwd : the first two launches of upp_prop_fwd on those rows (pooled, amax, part, mean, rstd as there); the third
+ *                           is upp_ln_adapter_prop_fwd, the block's tail with the interpolation as its row phase.
+ *   upp_prop_res_bwd      : upp_prop_bwd writing g_x2 = g_X and g_m = dp_scale * g_X (upp_rowln_bwd of the residual) instead of g_X.
+ * Every result is bit-identical to the composition with upp_rowln_fwd / upp_rowln_bwd. */
+int upp_prop_res_pool_fwd(const float *x2, const float *m, const float *mbias, const float *u_dp, float keep_dp, const int32_t *i1,
+                          const float *u, float keep, float *running_mean, float *running_var, float momentum, float eps,
+                          int training, float *pooled, uint8_t *amax, float *part, float *mean, float *rstd, int B, int Lp, int G2,
+                          int D, void *stream);
+int upp_prop_res_bwd(const float *g_out, const float *pooled, const uint8_t *amax, const float *mean, const float *rstd,
+                     const float *gamma, const float *u, float keep, const float *w8, const int32_t *start1,
+                     const int32_t *perm1, const int32_t *start2, const int32_t *perm2, const int32_t *start8,
+                     const int32_t *perm8, int training, const float *u_dp, float keep_dp, float *g_c2, float *part,
+                     float *g_gamma, float *g_beta, float *g_x2, float *g_m, int B, int Lp, int T, int G2, int D, void *stream);
 /* Stage 2 of the recipe (run.sh:16, models/Point_MAE_unify.py:22-48 under autograd): the centres carry a gradient, so the
  * interpolation weights w8 do too.
  *   upp_prop_w8_grad    : g_w8 (B,T,8) = 0.3 * <g_out[token], lc[j] + 0.3 * X[i2[j]]>, j = idx8[token,k]; lc = BatchNorm(pooled) when
@@ -815,6 +830,18 @@ int upp_ln_adapter_fwd(const float *x, const float *y, const float *ybias, const
                        const float *gamma, const float *beta, float eps, const float *W1, const float *b1, const float *W2,
                        const float *b2, const float *ud, float p, float scale, float *xo, float *mean, float *rstd, float *s1,
                        float *out, int B, int Lin, int Lout, int D, int H, void *stream);
+/* upp_ln_adapter_prop_fwd: upp_ln_adapter_fwd for a prompted block with prompt propagation, on the inputs of the MLP residual
+ * (x, y, ybias, u as there; y is required) and the tensors upp_prop_res_pool_fwd wrote.  The rows it normalises are
+ *   xo[t] = x3[src(t)] + (src(t) a centre row i = src(t) - (Lin - T) >= 0 ? 0.3 * sum_k w8[i][k] * (BN(pooled[j_k]) + 0.3 * x3[i2[j_k]]) : 0)
+ * with x3 as above, j_k = idx8[i][k], BN = bn_gamma * (. - bn_mean) * bn_rstd + bn_beta: the rows upp_prop_fwd writes, which are
+ * neither stored nor -- the prompt rows -- computed.  Outputs as upp_ln_adapter_fwd, bit-identical to
+ * upp_rowln_fwd -> upp_prop_fwd -> upp_ln_adapter_fwd(y = NULL).  The backward is upp_ln_adapter_bwd_fused -> upp_prop_res_bwd. */
+int upp_ln_adapter_prop_fwd(const float *x, const float *y, const float *ybias, const float *u, float keep, int mode, int P,
+                            const float *pooled, const float *bn_mean, const float *bn_rstd, const float *bn_gamma,
+                            const float *bn_beta, const int32_t *i2, const int32_t *idx8, const float *w8, int T, int G2,
+                            const float *gamma, const float *beta, float eps, const float *W1, const float *b1, const float *W2,
+                            const float *b2, const float *ud, float p, float scale, float *xo, float *mean, float *rstd, float *s1,
+                            float *out, int B, int Lin, int Lout, int D, int H, void *stream);
 /* upp_ln_adapter_bwd_fused: the whole backward of upp_ln_adapter_fwd in one launch on 16-row workgroups -- the adapter's backward
  * (g_ha, per-workgroup partials [dW1 (H,D) | dW2 (D,H) | db1 (H) | db2 (D)] in `part`, upp_ln_adapter_part_floats(R, D) floats, or
  * part = NULL), the LayerNorm backward with the residual (g_x / g_y (B, Lin, D): every row is written, zeros for the prompt rows
