@@ -14,14 +14,41 @@ at construction.
 TransformerEncoder / TransformerDecoder compute every neighbour list once per forward -- the denoise list included, which the reference
 recomputes inside every block; positions do not change between blocks, so the lists are the same -- and only the lists some block uses.
 
-Not ported yet: PCTransformer and AdaPoinTr themselves (query ranking, SimpleRebuildFCLayer, the denoise loss); no model is registered."""
+PCTransformer and AdaPoinTr (reference models/AdaPoinTr.py:737-997) are built from those stacks and
+    grouper           dgcnn_group.DGCNN_Grouper.forward(x, num); encoder_type 'pn' (SimpleEncoder) is not ported and raises ValueError
+    Linear-GELU MLPs  upp_layers.mlp2 (HF.linear / HF.mlp_gelu); the global maxima: upp_layers.max_over; FPS: utils.misc.fps
+    query selection   the ranking MLP under no_grad (its only use is an integer order: its parameters get no gradient), then
+                      HF.query_select: the num_query best of the [predicted ; FPS] candidates and, in training mode, the 64 jittered
+                      denoising points behind them -- one launch each way instead of argsort + expand + gather + cat
+    three Linears over a concatenation whose largest part is constant along the token axis, each split by columns (expand_add below):
+                      PCTransformer.mlp_query[0] over [global ; coarse] (GELU), AdaPoinTr.reduce_map over [global ; q ; coarse] and
+                      SimpleRebuildFCLayer.layer.fc1 over [max token ; token] (GELU).  The per-sample and per-token products run on
+                      HF.linear, so no (B,M,1027+C) or (B,M,2C) tensor is built and the 3-column term needs no padded copy; the
+                      broadcast add, the 3-column term and the GELU are torch element-wise operators -- NOT a fused kernel yet
+                      (README "The AdaPoinTr completion model": what is left out)
+    loss              get_loss: HF.knn_query + HF.gather_rows for the denoise target, ChamferDistanceL1, the 0.5 weight inside
+The selection's fused path is taken for HIP f32 tensors of the served sizes while upp_layers.POOL_TRACE is unset; otherwise the same module
+runs the torch formulation (upp_hip.torch_cpu.query_select), and a HIP tensor that was declined is recorded by HF.note_declined.
+
+The name AdaPoinTr is NOT in the MODELS registry (README "The AdaPoinTr completion model"): build it with from_cfg(cfg), which puts the
+class itself into cfg.NAME -- utils.registry.build_from_cfg accepts a class there.
+
+Deliberate deviations: equal ranking scores are ordered by ascending index (the reference's torch.argsort(descending=True) leaves it
+open); misc.jitter_points, which the reference calls and does not define, is this repository's (utils/misc.py)."""
 from functools import partial
 
 import torch
 import torch.nn as nn
 
+from extensions.chamfer_dist import ChamferDistanceL1
 from upp_hip import functional as HF
+from upp_hip import torch_cpu
+from utils import misc
 from . import upp_layers as L
+from .PoinTr import Fold  # noqa: F401  (the reference's models/AdaPoinTr.py:693-735 is the same class)
+from .Transformer import conv_bn_act_conv
+from .build import build_model_from_cfg
+from .dgcnn_group import DGCNN_Grouper
 from .Transformer_utils import Attention, CrossAttention, DropPath, DynamicGraphAttention, LayerScale, Mlp, denoise_knn, knn_point
 
 SERVED_TOKENS = ('attn', 'graph')
@@ -324,3 +351,226 @@ class PointTransformerEncoderEntry(PointTransformerEncoder):
 class PointTransformerDecoderEntry(PointTransformerDecoder):
     def __init__(self, config, **kwargs):
         super().__init__(**dict(config))
+
+
+# ---------------------------------------------------------------------------------------------- PCTransformer and AdaPoinTr
+DENOISE_PICKS = 64          # reference models/AdaPoinTr.py:863,866: the number of jittered input points appended as denoising queries
+
+
+def expand_add(P, T=None, U=None, Wu=None, act=None):
+    """P (R,O) a per-row product (bias included), T (R,S,O) a dense addend or None, U (R,S,J) with Wu (O,J) or None -> (R,S,O) =
+    act(P[r] + T[r,s] + Wu U[r,s]), act None or 'gelu' (erf form): a Linear over [f repeated along s ; x ; u] with W = [Wf | Wx | Wu],
+    P = Wf f + b, T = Wx x, without the concatenation.  Torch element-wise operators on any device and dtype; the J-column term is J
+    broadcast products, not a matrix product (J = 3 here: no library GEMM of K = 3, no padded copy)."""
+    if T is None and U is None:
+        raise ValueError("expand_add: at least one of T (R, S, O) and U (R, S, J) must be given")
+    if act not in (None, 'gelu'):
+        raise ValueError("expand_add: act must be None or 'gelu'")
+    z = P.unsqueeze(1)
+    if T is not None:
+        z = z + T
+    if U is not None:
+        for j in range(U.shape[-1]):
+            z = z + U[..., j:j + 1] * Wu[:, j]
+    return nn.functional.gelu(z) if act == 'gelu' else z
+
+
+def query_select(score, cand, Q, extra, site):
+    """HF.query_select where the kernel serves the operands, the torch formulation elsewhere -> out (B, Q + D, 3).  With POOL_TRACE set
+    the order is recorded or replayed (upp_layers.trace_idx) like every other discrete choice."""
+    if L.POOL_TRACE is None and HF.query_select_usable(score, cand, Q, extra):
+        return HF.query_select(score, cand, Q, extra)[0]
+    if score.is_cuda and L.POOL_TRACE is None:
+        HF.note_declined("%s query_select score %s, Q = %d" % (site, tuple(score.shape), Q), "outside the served range")
+    if L.POOL_TRACE is None:
+        return torch_cpu.query_select(score, cand, Q, extra)[0]
+    order = L.trace_idx(site + '.order', torch.argsort(score.detach(), dim=1, descending=True, stable=True)[:, :Q])
+    out = torch.gather(cand, 1, order.unsqueeze(-1).expand(-1, -1, 3))
+    return out if extra is None else torch.cat([out, extra], dim=1)
+
+
+class SimpleRebuildFCLayer(nn.Module):
+    """reference models/AdaPoinTr.py:737-758.  forward(rec_feature (B,M,C)) -> (B,M,step,3): the Mlp over [max token ; token], whose
+    fc1 is W1[:, :C] g + b1 per sample, W1[:, C:] tok per token, added and activated by expand_add."""
+
+    def __init__(self, input_dims, step, hidden_dim=512):
+        super().__init__()
+        self.input_dims = input_dims
+        self.step = step
+        self.layer = Mlp(self.input_dims, hidden_dim, step * 3)
+
+    def forward(self, rec_feature):
+        B, M, C = rec_feature.shape
+        if 2 * C != self.input_dims:
+            raise ValueError("SimpleRebuildFCLayer(%d) takes tokens of %d channels, got %d" % (self.input_dims, self.input_dims // 2, C))
+        fc1, fc2 = self.layer.fc1, self.layer.fc2
+        g_feature = L.max_over(rec_feature, 1, 'rebuild_fc.global')                  # (B,C)
+        P = HF.linear(g_feature, fc1.weight[:, :C], fc1.bias)
+        T = HF.linear(rec_feature.reshape(B * M, C), fc1.weight[:, C:]).view(B, M, -1)
+        h = expand_add(P, T, act='gelu')
+        return HF.linear(h.reshape(B * M, -1), fc2.weight, fc2.bias).view(B, M, self.step, 3)
+
+
+class PCTransformer(nn.Module):
+    """reference models/AdaPoinTr.py:761-889.  forward(xyz (B,N,3)) -> (q (B,M,C), coarse (B,M,3), denoise_length): M = num_query in eval
+    mode, num_query + 64 with denoise_length = 64 in training mode (N >= 64)."""
+
+    def __init__(self, config):
+        super().__init__()
+        encoder_config = config.encoder_config
+        decoder_config = config.decoder_config
+        self.center_num = getattr(config, 'center_num', [512, 128])
+        self.encoder_type = config.encoder_type
+        if self.encoder_type == 'pn':
+            raise ValueError("encoder_type 'pn' (SimpleEncoder, the PointNet grouper) is not ported; served: 'graph'")
+        if self.encoder_type != 'graph':
+            raise ValueError("unexpected encoder_type %r" % (self.encoder_type,))
+        in_chans = 3
+        self.num_query = query_num = config.num_query
+        global_feature_dim = config.global_feature_dim
+        self.grouper = DGCNN_Grouper(k=16)
+        self.pos_embed = nn.Sequential(nn.Linear(in_chans, 128), nn.GELU(), nn.Linear(128, encoder_config.embed_dim))
+        self.input_proj = nn.Sequential(nn.Linear(self.grouper.num_features, 512), nn.GELU(), nn.Linear(512, encoder_config.embed_dim))
+        self.encoder = PointTransformerEncoderEntry(encoder_config)
+        self.increase_dim = nn.Sequential(nn.Linear(encoder_config.embed_dim, 1024), nn.GELU(), nn.Linear(1024, global_feature_dim))
+        self.coarse_pred = nn.Sequential(nn.Linear(global_feature_dim, 1024), nn.GELU(), nn.Linear(1024, 3 * query_num))
+        self.mlp_query = nn.Sequential(nn.Linear(global_feature_dim + 3, 1024), nn.GELU(), nn.Linear(1024, 1024), nn.GELU(),
+                                       nn.Linear(1024, decoder_config.embed_dim))
+        if decoder_config.embed_dim == encoder_config.embed_dim:
+            self.mem_link = nn.Identity()
+        else:
+            self.mem_link = nn.Linear(encoder_config.embed_dim, decoder_config.embed_dim)
+        self.decoder = PointTransformerDecoderEntry(decoder_config)
+        self.query_ranking = nn.Sequential(nn.Linear(3, 256), nn.GELU(), nn.Linear(256, 256), nn.GELU(), nn.Linear(256, 1), nn.Sigmoid())
+        self.apply(_init_weights)
+
+    def ranking_scores(self, cand):
+        """cand (B,M,3) -> (B,M): query_ranking's sigmoid scores, under no_grad -- they only order the candidates."""
+        r = self.query_ranking
+        B, M, _ = cand.shape
+        with torch.no_grad():
+            h = HF.linear(cand.detach().reshape(B * M, 3), r[0].weight, r[0].bias, act='gelu')
+            h = HF.linear(h, r[2].weight, r[2].bias, act='gelu')
+            # (one output: three zero rows make the output rows 16 bytes, which upp_linear_f32 serves; no gradient passes here)
+            s = HF.linear(h, nn.functional.pad(r[4].weight, (0, 0, 0, 3)), nn.functional.pad(r[4].bias, (0, 3)))[:, 0]
+            return torch.sigmoid(s).view(B, M)
+
+    def query_features(self, global_feature, coarse):
+        """mlp_query over [global feature repeated M times ; coarse point]: (B,G), (B,M,3) -> (B,M,C)."""
+        l0 = self.mlp_query[0]
+        B, M, _ = coarse.shape
+        G = global_feature.shape[1]
+        P = HF.linear(global_feature, l0.weight[:, :G], l0.bias)
+        h = expand_add(P, None, coarse, l0.weight[:, G:], 'gelu')
+        return L.mlp2(self.mlp_query[2:5], h.reshape(B * M, -1)).view(B, M, -1)
+
+    def forward(self, xyz):
+        B, N, _ = xyz.shape
+        if self.training and N < DENOISE_PICKS:
+            raise ValueError("training mode picks %d denoising points from the input, which has %d" % (DENOISE_PICKS, N))
+        xyz = xyz.contiguous()
+        coor, f = self.grouper(xyz, self.center_num)                                 # (B,n,3), (B,n,128)
+        n = coor.shape[1]
+        pe = L.mlp2(self.pos_embed, coor.reshape(B * n, 3)).view(B, n, -1)
+        x = L.mlp2(self.input_proj, f.reshape(B * n, -1)).view(B, n, -1)
+        x = self.encoder(x + pe, coor)
+        g = L.mlp2(self.increase_dim, x.reshape(B * n, -1)).view(B, n, -1)
+        global_feature = L.max_over(g, 1, 'pctransformer.global')                    # (B,G)
+        coarse = L.mlp2(self.coarse_pred, global_feature).reshape(B, -1, 3)
+        coarse_inp = misc.fps(xyz, self.num_query // 2)[0]
+        cand = torch.cat([coarse, coarse_inp], dim=1)                                # (B, num_query + num_query / 2, 3)
+        mem = x if isinstance(self.mem_link, nn.Identity) else HF.linear(x, self.mem_link.weight, self.mem_link.bias)
+        extra, denoise_length = None, 0
+        if self.training:
+            extra = misc.jitter_points(misc.fps(xyz, DENOISE_PICKS)[0])
+            denoise_length = DENOISE_PICKS
+        coarse = query_select(self.ranking_scores(cand), cand, self.num_query, extra, 'pctransformer.query')
+        q = self.query_features(global_feature, coarse)
+        q = self.decoder(q=q, v=mem, q_pos=coarse, v_pos=coor, denoise_length=denoise_length or None)
+        return q, coarse, denoise_length
+
+
+class AdaPoinTr(nn.Module):
+    """reference models/AdaPoinTr.py:893-997.  forward(xyz (B,N,3)): eval mode -> (coarse (B,M,3), rebuild (B, M factor, 3)); training mode
+    -> (pred_coarse (B,M,3), denoised_coarse (B,64,3), denoised_fine (B, 64 factor, 3), pred_fine (B, M factor, 3)).  get_loss(ret, gt) ->
+    (0.5 x the denoise Chamfer-L1, coarse + fine Chamfer-L1).  Not registered in MODELS: see from_cfg."""
+
+    def __init__(self, config, **kwargs):
+        super().__init__()
+        self.trans_dim = config.decoder_config.embed_dim
+        self.num_query = config.num_query
+        self.num_points = getattr(config, 'num_points', None)
+        self.decoder_type = config.decoder_type
+        if self.decoder_type not in ('fold', 'fc'):
+            raise ValueError("unexpected decoder_type %r" % (self.decoder_type,))
+        self.fold_step = 8
+        self.base_model = PCTransformer(config)
+        if self.decoder_type == 'fold':
+            self.factor = self.fold_step ** 2
+            self.decode_head = Fold(self.trans_dim, step=self.fold_step, hidden_dim=256)
+        elif self.num_points is not None:
+            if self.num_points % self.num_query:
+                raise ValueError("num_points %d is no multiple of num_query %d" % (self.num_points, self.num_query))
+            self.factor = self.num_points // self.num_query
+            self.decode_head = SimpleRebuildFCLayer(self.trans_dim * 2, step=self.factor)
+        else:
+            self.factor = self.fold_step ** 2
+            self.decode_head = SimpleRebuildFCLayer(self.trans_dim * 2, step=self.fold_step ** 2)
+        self.increase_dim = nn.Sequential(nn.Conv1d(self.trans_dim, 1024, 1), nn.BatchNorm1d(1024), nn.LeakyReLU(negative_slope=0.2),
+                                          nn.Conv1d(1024, 1024, 1))
+        self.reduce_map = nn.Linear(self.trans_dim + 1027, self.trans_dim)
+        self.build_loss_func()
+
+    def build_loss_func(self):
+        self.loss_func = ChamferDistanceL1()
+
+    def get_loss(self, ret, gt, epoch=1):
+        pred_coarse, denoised_coarse, denoised_fine, pred_fine = ret
+        if pred_fine.size(1) != gt.size(1):
+            raise ValueError("pred_fine has %d points, the ground truth %d" % (pred_fine.size(1), gt.size(1)))
+        # denoise loss: every denoised coarse point is to rebuild its `factor` nearest ground-truth points
+        B, D, _ = denoised_coarse.shape
+        _, idx = HF.knn_query(gt.contiguous(), denoised_coarse.detach().contiguous(), self.factor)
+        idx = L.trace_idx('adapointr.denoise_target', idx.long())
+        denoised_target = HF.gather_rows(gt.contiguous(), idx.reshape(B, D * self.factor))
+        loss_denoised = self.loss_func(denoised_fine, denoised_target) * 0.5
+        loss_recon = self.loss_func(pred_coarse, gt) + self.loss_func(pred_fine, gt)
+        return loss_denoised, loss_recon
+
+    def rebuild_feature(self, global_feature, q, coarse):
+        """reduce_map over [global feature repeated M times ; q ; coarse]: (B,G), (B,M,C), (B,M,3) -> (B,M,C), never concatenated."""
+        B, M, C = q.shape
+        G = global_feature.shape[1]
+        W = self.reduce_map.weight
+        P = HF.linear(global_feature, W[:, :G], self.reduce_map.bias)
+        T = HF.linear(q.reshape(B * M, C), W[:, G:G + C]).view(B, M, C)
+        return expand_add(P, T, coarse, W[:, G + C:])
+
+    def forward(self, xyz):
+        if L.sync_bn_active(self.training):
+            raise RuntimeError("AdaPoinTr does not support synchronised BatchNorm (upp_layers.enable_sync_bn)")
+        q, coarse, denoise_length = self.base_model(xyz)                             # (B,M,C), (B,M,3)
+        B, M, C = q.shape
+        g = conv_bn_act_conv(self.increase_dim, q.reshape(B * M, C), self.training).view(B, M, -1)
+        global_feature = L.max_over(g, 1, 'adapointr.global')                        # (B,1024)
+        feature = self.rebuild_feature(global_feature, q, coarse)
+        if self.decoder_type == 'fold':
+            relative_xyz = self.decode_head.fold_rows(feature.reshape(B * M, C)).view(B, M, -1, 3)
+        else:
+            relative_xyz = self.decode_head(feature)                                 # (B,M,S,3)
+        rebuild_points = relative_xyz + coarse.unsqueeze(-2)
+        if self.training:
+            R = M - denoise_length
+            pred_fine = rebuild_points[:, :R].reshape(B, -1, 3).contiguous()
+            pred_coarse = coarse[:, :R].contiguous()
+            denoised_fine = rebuild_points[:, R:].reshape(B, -1, 3).contiguous()
+            denoised_coarse = coarse[:, R:].contiguous()
+            return pred_coarse, denoised_coarse, denoised_fine, pred_fine
+        return coarse, rebuild_points.reshape(B, -1, 3).contiguous()
+
+
+def from_cfg(cfg):
+    """cfg: the model section of a config (cfgs/AdaPoinTr.yaml) -> AdaPoinTr(cfg).  The class itself goes into cfg.NAME --
+    utils.registry.build_from_cfg takes a class there -- because the name is deliberately not in the MODELS registry."""
+    cfg['NAME'] = AdaPoinTr
+    return build_model_from_cfg(cfg)

@@ -485,6 +485,59 @@ class _ExpandAct(Function):
                 g_beta if mode and need[4] else None, None, None, None, None, None)
 
 
+# ------------------------------------------------------------------ query selection (README "The AdaPoinTr completion model")
+class _QuerySelect(Function):
+    """The Q best-ranked candidates, then the extra points, as one node (include/upp_hip.h "query selection"); the backward writes
+    every row of g_cand once -- no zero-fill, no scatter.  score gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, score, cand, extra, Q):
+        out, order = ops.query_select_fwd(score, cand, Q, extra)
+        ctx.save_for_backward(order)
+        ctx.M = cand.shape[1]
+        ctx.mark_non_differentiable(order)
+        return out, order
+
+    @staticmethod
+    def backward(ctx, g_out, _g_order):
+        (order,) = ctx.saved_tensors
+        g_cand, g_extra = ops.query_select_bwd(g_out.contiguous(), order, ctx.M)
+        need = ctx.needs_input_grad
+        return None, g_cand if need[1] else None, g_extra if need[2] else None, None
+
+
+def query_select_usable(score, cand, Q, extra=None):
+    ts = [score, cand] + ([extra] if extra is not None else [])
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 for t in ts):
+        return False
+    if score.dim() != 2 or cand.dim() != 3 or tuple(cand.shape) != (score.shape[0], score.shape[1], 3) or score.shape[0] < 1:
+        return False
+    if extra is not None and (extra.dim() != 3 or extra.shape[0] != score.shape[0] or extra.shape[2] != 3):
+        return False
+    return ops.query_select_usable(score.shape[1], int(Q))
+
+
+def query_select(score, cand, Q, extra=None):
+    """score (B,M), cand (B,M,3), extra (B,D,3) or None -> (out (B,Q+D,3), order (B,Q) int32): out[:, :Q] are the Q candidates of
+    greatest score in descending order, equal scores by ascending index and NaN first (the reference's torch.argsort(descending=True)
+    leaves the tie order open), out[:, Q:] the extra points.  cand and extra get gradients, score gets none.  1 <= Q <= M <= 4096 on
+    the kernels; HIP tensors outside that take the torch formulation (note_declined records it); CPU tensors take it when
+    upp_hip.torch_cpu is enabled."""
+    Q = int(Q)
+    if score.dim() != 2 or not 1 <= Q <= score.shape[1]:
+        raise ValueError("query_select: score (B, M) and 1 <= Q <= M, got %s and Q = %d" % (tuple(score.shape), Q))
+    from . import torch_cpu
+    ts = [score, cand] + ([extra] if extra is not None else [])
+    if _torch_cpu(*ts):
+        return torch_cpu.query_select(score, cand, Q, extra)
+    if score.is_cuda and not query_select_usable(score, cand, Q, extra):
+        note_declined("query_select score %s, Q = %d" % (tuple(score.shape), Q), "outside the served range")
+        return torch_cpu.query_select(score, cand, Q, extra)
+    if extra is not None and extra.shape[1] == 0:
+        extra = None
+    return _QuerySelect.apply(score.detach().contiguous(), cand.contiguous(), None if extra is None else extra.contiguous(), Q)
+
+
 def _expand_norm(norm):
     if norm is None:
         return None

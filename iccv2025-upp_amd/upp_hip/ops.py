@@ -687,6 +687,63 @@ def expand_bwd(g_h, P, U, Wu, gamma=None, beta=None, mean=None, rstd=None, mode=
     return g_P, g_U, g_Wu, g_gamma, g_beta
 
 
+# ------------------------------------------------------------------ query selection (include/upp_hip.h)
+QUERY_SELECT_MAX_M = 4096
+
+
+def query_select_usable(M, Q):
+    return 1 <= Q <= M <= QUERY_SELECT_MAX_M
+
+
+def _query_select_sizes(B, M, Q, D):
+    if not 1 <= Q <= M:
+        raise RuntimeError("query_select: 1 <= Q <= M is needed, got Q = %d, M = %d" % (Q, M))
+    if M > QUERY_SELECT_MAX_M:
+        raise RuntimeError("query_select: M <= %d is served, got M = %d" % (QUERY_SELECT_MAX_M, M))
+    if B < 1 or 3 * B * (Q + D) >= 2 ** 31:
+        raise RuntimeError("query_select: B >= 1 and 3 B (Q + D) < 2^31 are served, got B = %d, Q = %d, D = %d" % (B, Q, D))
+
+
+def query_select_fwd(score, cand, Q, extra=None):
+    """score (B,M), cand (B,M,3), extra (B,D,3) | None -> out (B,Q+D,3), order (B,Q) int32: the Q candidates of greatest score in
+    descending order (equal scores by ascending index, NaN first), then the extra points."""
+    _need(score, "score", torch.float32, 2)
+    B, M = score.shape
+    _need_f32(cand, "cand", (B, M, 3))
+    _same_device(score, cand)
+    D = 0
+    if extra is not None:
+        _need(extra, "extra", torch.float32, 3, 3)
+        _same_device(score, extra)
+        if extra.shape[0] != B:
+            raise RuntimeError("query_select: extra must be (B, D, 3)")
+        D = extra.shape[1]
+    Q = int(Q)
+    _query_select_sizes(B, M, Q, D)
+    out = torch.empty((B, Q + D, 3), dtype=torch.float32, device=score.device)
+    order = torch.empty((B, Q), dtype=torch.int32, device=score.device)
+    _call(score.device, "upp_query_select_fwd", _abi.ptr(score), _abi.ptr(cand), _abi.ptr(extra if D else None), _abi.ptr(out),
+          _abi.ptr(order), B, M, Q, D)
+    return out, order
+
+
+def query_select_bwd(g_out, order, M):
+    """g_out (B,Q+D,3), order (B,Q) int32 -> g_cand (B,M,3) (every row written once), g_extra (B,D,3) | None."""
+    _need(order, "order", torch.int32, 2)
+    B, Q = order.shape
+    _need(g_out, "g_out", torch.float32, 3, 3)
+    _same_device(g_out, order)
+    M = int(M)
+    D = g_out.shape[1] - Q
+    if g_out.shape[0] != B or D < 0:
+        raise RuntimeError("query_select_bwd: g_out must be (B, Q + D, 3) for order (B, Q)")
+    _query_select_sizes(B, M, Q, D)
+    g_cand = torch.empty((B, M, 3), dtype=torch.float32, device=g_out.device)
+    g_extra = torch.empty((B, D, 3), dtype=torch.float32, device=g_out.device) if D else None
+    _call(g_out.device, "upp_query_select_bwd", _abi.ptr(g_out), _abi.ptr(order), _abi.ptr(g_cand), _abi.ptr(g_extra), B, M, Q, D)
+    return g_cand, g_extra
+
+
 # ------------------------------------------------------------------ Chamfer
 def chamfer_fwd(xyz1, xyz2):
     _need(xyz1, "xyz1", torch.float32, 3, 3)

@@ -203,6 +203,17 @@ def expand_act(P, U, Wu, norm=None, slope=0.0):
     return F.leaky_relu(y, float(slope))
 
 
+def query_select(score, cand, Q, extra=None):
+    """The selection of include/upp_hip.h "query selection" as torch operators (any device and dtype; differentiable in cand and extra):
+    score (B,M), cand (B,M,3), extra (B,D,3) | None -> (out (B,Q+D,3), order (B,Q) int32): the Q candidates of greatest score in
+    descending order -- equal scores by ascending index (a stable sort), NaN first -- then the extra points."""
+    order = torch.argsort(score.detach(), dim=1, descending=True, stable=True)[:, :int(Q)]
+    out = torch.gather(cand, 1, order.unsqueeze(-1).expand(-1, -1, cand.shape[-1]))
+    if extra is not None and extra.shape[1] > 0:
+        out = torch.cat([out, extra], dim=1)
+    return out, order.to(torch.int32)
+
+
 def cross_attention(q, k, v, num_heads, scale):
     """The cross-attention core of include/upp_hip.h "cross-attention" as torch operators (any device, any head_dim; differentiable):
     q (B,Lq,C), k and v (B,Lk,C) -> (B,Lq,C) = softmax(q k^T scale) v per head (reference models/Transformer.py:148-152).  It keeps the

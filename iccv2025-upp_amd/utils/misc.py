@@ -77,6 +77,16 @@ def gaussian_noise(shape, loc=0., scale=0.2, shell_radius=0.9, device=None, gene
     return g + g / g.norm(p=2, dim=-1, keepdim=True) * shell_radius
 
 
+def jitter_points(pc, std=0.01, clip=0.05, generator=None):
+    """pc (B,N,3) -> pc + clamp(N(0, std), -clip, clip), a new tensor.  The reference's AdaPoinTr calls misc.jitter_points
+    (models/AdaPoinTr.py:864) and its utils/misc.py does not define it; this is an ASSUMPTION: upstream PoinTr's function with its
+    constants (std 0.01, clip 0.05), recalled.  The noise is drawn on pc's device and no host value is taken, so it can be captured."""
+    if std < 0 or clip < 0:
+        raise ValueError("jitter_points: std >= 0 and clip >= 0")
+    noise = torch.empty_like(pc).normal_(0.0, std, generator=generator) if std > 0 else torch.zeros_like(pc)
+    return pc + noise.clamp_(-clip, clip)
+
+
 def seprate_point_cloud(xyz, num_points, crop, fixed_points=None, padding_zeros=False, sample_points=1024,
                         incomplete_shape=True, centers=None, generator=None, keep_crop=True):
     """Online cropping of reference utils/misc.py:205-256, batched on the device.

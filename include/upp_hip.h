@@ -336,6 +336,24 @@ int upp_expand_bwd(const float *g_h, const float *P, const float *U, int per_row
                    const float *mean, const float *rstd, float slope, int mode, float *g_P, float *g_U, float *g_Wu, float *g_gamma,
                    float *g_beta, float *work, int R, int S, int O, int J, void *stream);
 
+/* ---- query selection: the Q best-ranked of M candidate points, then D extra points ----------------------------------------
+ * Replaces the reference's argsort + expand + gather + cat (models/AdaPoinTr.py:855-865) and, in the backward, autograd's zero-fill
+ * and scatter:
+ *   score (B,M) f32, cand (B,M,3) f32, extra (B,D,3) f32 or NULL (D == 0)
+ *   -> order (B,Q) int32: order[b,r] = the candidate of rank r, where the rank of i is the number of j with score_j > score_i, or
+ *      score_j == score_i and j < i (descending, equal scores in ascending index order; NaN ranks as the largest and -0 equals +0: the
+ *      order of upp_argsort_rows.  The reference's torch.argsort(descending=True) leaves the order of equal scores open.)
+ *   -> out (B,Q+D,3) f32: out[b,r] = cand[b, order[b,r]] for r < Q, out[b,Q+d] = extra[b,d].
+ *   One workgroup per cloud, its scores in the LDS; 1 launch.
+ * Backward: g_out (B,Q+D,3), order (B,Q) -> g_cand (B,M,3): a selected row gets its gradient, every other row 0, each row written once
+ *   (the inverse map is built in the LDS; an index outside [0, M) is ignored);  g_extra (B,D,3) = g_out[:, Q:] (NULL for D == 0).
+ *   No atomics, nothing is zeroed beforehand; 1 launch.  score has no gradient.
+ * Limits: 1 <= Q <= M <= 4096, D >= 0, B >= 1, 3 B (Q + D) < 2^31 -- UPP_E_RANGE for M > 4096, Q > M or a larger output; a null pointer or a non-positive B, M or Q, D < 0:
+ *   UPP_E_BADARG.  Both before any launch. */
+int upp_query_select_fwd(const float *score, const float *cand, const float *extra, float *out, int *order, int B, int M, int Q, int D,
+                         void *stream);
+int upp_query_select_bwd(const float *g_out, const int *order, float *g_cand, float *g_extra, int B, int M, int Q, int D, void *stream);
+
 /* ---- Chamfer distance ----------------------------------------------------------
  * Replaces chamfer.forward / chamfer.backward (reference
  * extensions/chamfer_dist/chamfer_cuda.cpp:36-39, kernels chamfer.cu:15-145 and
