@@ -670,7 +670,7 @@ class CrossAttention(nn.Module):
         self.proj_drop = nn.Dropout(proj_drop)
 
     def fusable(self, q, v):
-        """The cross-attention kernels (csrc/attn_cross.hip) serve head_dim 64, both lengths <= HF.ATTN_MAX_L and no attention dropout."""
+        """The cross-attention kernels (csrc/attn_stream.hip) serve head_dim 64, both lengths <= HF.ATTN_MAX_L and no attention dropout."""
         return (q.is_cuda and v.is_cuda and q.dtype == torch.float32 and v.dtype == torch.float32
                 and self.out_dim == 64 * self.num_heads and 1 <= q.shape[1] <= HF.ATTN_MAX_L and 1 <= v.shape[1] <= HF.ATTN_MAX_L
                 and not (self.training and self.attn_drop.p > 0))

@@ -768,24 +768,24 @@ def attention(qkv, num_heads, scale):
 
 
 class _CrossAttention(Function):
-    """ctx = softmax(q k^T * scale) v with q (B, Lq, H*64) and k, v (B, Lk, H*64) from two sequences; saves q, k, v, ctx and lse -- never
-    a (B, H, Lq, Lk) tensor.  No scatter-add: deterministic in every mode."""
+    """ctx = softmax(q k^T * scale) v with q (B, Lq, H*64) and k, v (B, Lk, H*64) from two sequences, under the prefix-visibility mask
+    (csrc/attn_stream.hip) when `splits` is (split_q, split_k) and not None; saves q, k, v, ctx and lse -- never a (B, H, Lq, Lk) or
+    (L, L) tensor, mask included.  No scatter-add: deterministic in every mode."""
 
     @staticmethod
-    def forward(ctx, q, k, v, num_heads, scale):
+    def forward(ctx, q, k, v, num_heads, scale, splits):
         B, Lq, _ = q.shape
         Lk = k.shape[1]
-        out, lse = ops.xattn_fwd(q, k, v, B, Lq, Lk, num_heads, scale)
+        ctx.masked, ctx.meta = splits is not None, (B, Lq, Lk, num_heads, scale) + (splits or ())
+        out, lse = (ops.xattn_prefix_fwd if ctx.masked else ops.xattn_fwd)(q, k, v, *ctx.meta)
         ctx.save_for_backward(q, k, v, out, lse)
-        ctx.meta = (B, Lq, Lk, num_heads, scale)
         return out
 
     @staticmethod
     def backward(ctx, g):
         q, k, v, out, lse = ctx.saved_tensors
-        B, Lq, Lk, H, scale = ctx.meta
-        d_q, d_k, d_v = ops.xattn_bwd(q, k, v, out, g.contiguous(), lse, B, Lq, Lk, H, scale)
-        return d_q, d_k, d_v, None, None
+        bwd = ops.xattn_prefix_bwd if ctx.masked else ops.xattn_bwd
+        return bwd(q, k, v, out, g.contiguous(), lse, *ctx.meta) + (None, None, None)
 
 
 def _xattn_view(t):
@@ -800,34 +800,13 @@ def _xattn_view(t):
 
 def cross_attention(q, k, v, num_heads, scale):
     """softmax(q k^T scale) v per head with queries and keys from two sequences (reference models/Transformer.py CrossAttention):
-    q (B, Lq, H*64), k and v (B, Lk, H*64) -> (B, Lq, H*64), on the streaming FP32-MFMA kernels of csrc/attn_cross.hip, head_dim 64,
+    q (B, Lq, H*64), k and v (B, Lk, H*64) -> (B, Lq, H*64), on the streaming FP32-MFMA kernels of csrc/attn_stream.hip, head_dim 64,
     1 <= Lq, Lk <= ATTN_MAX_L (HIP tensors outside that raise).  q, k, v may be row-strided views (slices of a packed product).
     Deterministic.  CPU tensors take the torch formulation when upp_hip.torch_cpu is enabled."""
     if _torch_cpu(q, k, v):
         from . import torch_cpu
         return torch_cpu.cross_attention(q, k, v, num_heads, scale)
-    return _CrossAttention.apply(_xattn_view(q), _xattn_view(k), _xattn_view(v), int(num_heads), float(scale))
-
-
-class _PrefixAttention(Function):
-    """_CrossAttention under the prefix-visibility mask (csrc/attn_prefix.hip); saves q, k, v, ctx and lse -- never an (L, L) tensor, mask
-    included.  No scatter-add: deterministic in every mode."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, num_heads, scale, split_q, split_k):
-        B, Lq, _ = q.shape
-        Lk = k.shape[1]
-        out, lse = ops.xattn_prefix_fwd(q, k, v, B, Lq, Lk, num_heads, scale, split_q, split_k)
-        ctx.save_for_backward(q, k, v, out, lse)
-        ctx.meta = (B, Lq, Lk, num_heads, scale, split_q, split_k)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        q, k, v, out, lse = ctx.saved_tensors
-        B, Lq, Lk, H, scale, split_q, split_k = ctx.meta
-        d_q, d_k, d_v = ops.xattn_prefix_bwd(q, k, v, out, g.contiguous(), lse, B, Lq, Lk, H, scale, split_q, split_k)
-        return d_q, d_k, d_v, None, None, None, None
+    return _CrossAttention.apply(_xattn_view(q), _xattn_view(k), _xattn_view(v), int(num_heads), float(scale), None)
 
 
 def prefix_attention(q, k, v, num_heads, scale, split_q, split_k):
@@ -839,7 +818,7 @@ def prefix_attention(q, k, v, num_heads, scale, split_q, split_k):
     if _torch_cpu(q, k, v):
         from . import torch_cpu
         return torch_cpu.prefix_attention(q, k, v, num_heads, scale, split_q, split_k)
-    return _PrefixAttention.apply(_xattn_view(q), _xattn_view(k), _xattn_view(v), int(num_heads), float(scale), int(split_q), int(split_k))
+    return _CrossAttention.apply(_xattn_view(q), _xattn_view(k), _xattn_view(v), int(num_heads), float(scale), (int(split_q), int(split_k)))
 
 
 # ------------------------------------------------------------------ deferred parameter-gradient sums

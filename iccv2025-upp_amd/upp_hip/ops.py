@@ -1611,41 +1611,6 @@ def _xattn_dense(ctx, d_ctx, lse, B, Lq, H):
             raise RuntimeError(f"{name} must be 16-byte aligned (the attention kernels load 16-byte pieces); got a view at a storage offset")
 
 
-def xattn_fwd(q, k, v, B, Lq, Lk, H, scale):
-    """softmax(q k^T scale) v with queries and keys from two sequences (csrc/attn_cross.hip): q (B, Lq, H * 64), k and v (B, Lk, H * 64)
-    -> ctx (B, Lq, H * 64), lse (B, H, Lq), both dense.  The operands may be views (a slice of a packed [k|v] or qkv product): see
-    _xattn_operand for the stride rule; the strides are taken from the tensors.  1 <= Lq, Lk <= ATTN_MAX_L; everything else raises
-    before a launch."""
-    B, Lq, Lk, H = _xattn_lengths(B, Lq, Lk, H)
-    q_rs = _xattn_operand(q, "q", B, Lq, H)
-    k_rs = _xattn_operand(k, "k", B, Lk, H)
-    v_rs = _xattn_operand(v, "v", B, Lk, H)
-    _xattn_device(q=q, k=k, v=v)
-    ctx = torch.empty((B, Lq, H * 64), dtype=torch.float32, device=q.device)
-    lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
-    _call(q.device, "upp_xattn_fwd", _abi.ptr(q), _abi.ptr(k), _abi.ptr(v), _abi.ptr(ctx), _abi.ptr(lse), B, Lq, Lk, H, 64, q_rs, k_rs, v_rs,
-          float(scale))
-    return ctx, lse
-
-
-def xattn_bwd(q, k, v, ctx, d_ctx, lse, B, Lq, Lk, H, scale):
-    """-> (d_q (B, Lq, H * 64), d_k, d_v (B, Lk, H * 64)) from d_ctx and the forward's ctx / lse.  q, k, v as in xattn_fwd; ctx, d_ctx and
-    lse dense.  The three gradients are fresh dense tensors (so they overlap nothing), every element written by exactly one workgroup: no
-    atomics, two calls give the same bits."""
-    B, Lq, Lk, H = _xattn_lengths(B, Lq, Lk, H)
-    q_rs = _xattn_operand(q, "q", B, Lq, H)
-    k_rs = _xattn_operand(k, "k", B, Lk, H)
-    v_rs = _xattn_operand(v, "v", B, Lk, H)
-    _xattn_dense(ctx, d_ctx, lse, B, Lq, H)
-    _xattn_device(q=q, k=k, v=v, ctx=ctx, d_ctx=d_ctx, lse=lse)
-    d_q = torch.empty((B, Lq, H * 64), dtype=torch.float32, device=q.device)
-    d_k = torch.empty((B, Lk, H * 64), dtype=torch.float32, device=q.device)
-    d_v = torch.empty((B, Lk, H * 64), dtype=torch.float32, device=q.device)
-    _call(q.device, "upp_xattn_bwd", _abi.ptr(q), _abi.ptr(k), _abi.ptr(v), _abi.ptr(ctx), _abi.ptr(d_ctx), _abi.ptr(lse), _abi.ptr(d_q),
-          _abi.ptr(d_k), _abi.ptr(d_v), B, Lq, Lk, H, 64, q_rs, k_rs, v_rs, H * 64, H * 64, H * 64, float(scale))
-    return d_q, d_k, d_v
-
-
 def _xattn_splits(Lq, Lk, split_q, split_k):
     split_q, split_k = int(split_q), int(split_k)
     if not 0 <= split_q <= Lq:
@@ -1655,28 +1620,25 @@ def _xattn_splits(Lq, Lk, split_q, split_k):
     return split_q, split_k
 
 
-def xattn_prefix_fwd(q, k, v, B, Lq, Lk, H, scale, split_q, split_k):
-    """xattn_fwd under the prefix-visibility mask of csrc/attn_prefix.hip: query rows < split_q see the keys < split_k, the other rows see
-    all Lk keys (AdaPoinTr's denoising queries: Lq = Lk = L, both splits L - D) -> ctx (B, Lq, H * 64), lse (B, H, Lq) over the visible keys.
-    Operands and their checks as in xattn_fwd; 0 <= split_q <= Lq and 1 <= split_k <= Lk, everything else raises before a launch."""
+def _xattn_fwd(q, k, v, B, Lq, Lk, H, scale, splits=None):
+    """xattn_fwd (splits None: upp_xattn_fwd) and xattn_prefix_fwd (splits (split_q, split_k): upp_xattn_prefix_fwd)"""
     B, Lq, Lk, H = _xattn_lengths(B, Lq, Lk, H)
-    split_q, split_k = _xattn_splits(Lq, Lk, split_q, split_k)
+    tail = () if splits is None else _xattn_splits(Lq, Lk, *splits)
     q_rs = _xattn_operand(q, "q", B, Lq, H)
     k_rs = _xattn_operand(k, "k", B, Lk, H)
     v_rs = _xattn_operand(v, "v", B, Lk, H)
     _xattn_device(q=q, k=k, v=v)
     ctx = torch.empty((B, Lq, H * 64), dtype=torch.float32, device=q.device)
     lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
-    _call(q.device, "upp_xattn_prefix_fwd", _abi.ptr(q), _abi.ptr(k), _abi.ptr(v), _abi.ptr(ctx), _abi.ptr(lse), B, Lq, Lk, H, 64, q_rs, k_rs,
-          v_rs, float(scale), split_q, split_k)
+    _call(q.device, "upp_xattn_fwd" if splits is None else "upp_xattn_prefix_fwd", _abi.ptr(q), _abi.ptr(k), _abi.ptr(v), _abi.ptr(ctx),
+          _abi.ptr(lse), B, Lq, Lk, H, 64, q_rs, k_rs, v_rs, float(scale), *tail)
     return ctx, lse
 
 
-def xattn_prefix_bwd(q, k, v, ctx, d_ctx, lse, B, Lq, Lk, H, scale, split_q, split_k):
-    """-> (d_q, d_k, d_v) of xattn_prefix_fwd, as xattn_bwd returns them: fresh dense tensors, every element written by exactly one
-    workgroup, two calls give the same bits.  Keys no row sees (split_q == Lq, keys >= split_k) get zero gradients."""
+def _xattn_bwd(q, k, v, ctx, d_ctx, lse, B, Lq, Lk, H, scale, splits=None):
+    """xattn_bwd (splits None: upp_xattn_bwd) and xattn_prefix_bwd (splits (split_q, split_k): upp_xattn_prefix_bwd)"""
     B, Lq, Lk, H = _xattn_lengths(B, Lq, Lk, H)
-    split_q, split_k = _xattn_splits(Lq, Lk, split_q, split_k)
+    tail = () if splits is None else _xattn_splits(Lq, Lk, *splits)
     q_rs = _xattn_operand(q, "q", B, Lq, H)
     k_rs = _xattn_operand(k, "k", B, Lk, H)
     v_rs = _xattn_operand(v, "v", B, Lk, H)
@@ -1685,9 +1647,38 @@ def xattn_prefix_bwd(q, k, v, ctx, d_ctx, lse, B, Lq, Lk, H, scale, split_q, spl
     d_q = torch.empty((B, Lq, H * 64), dtype=torch.float32, device=q.device)
     d_k = torch.empty((B, Lk, H * 64), dtype=torch.float32, device=q.device)
     d_v = torch.empty((B, Lk, H * 64), dtype=torch.float32, device=q.device)
-    _call(q.device, "upp_xattn_prefix_bwd", _abi.ptr(q), _abi.ptr(k), _abi.ptr(v), _abi.ptr(ctx), _abi.ptr(d_ctx), _abi.ptr(lse),
-          _abi.ptr(d_q), _abi.ptr(d_k), _abi.ptr(d_v), B, Lq, Lk, H, 64, q_rs, k_rs, v_rs, H * 64, H * 64, H * 64, float(scale), split_q, split_k)
+    _call(q.device, "upp_xattn_bwd" if splits is None else "upp_xattn_prefix_bwd", _abi.ptr(q), _abi.ptr(k), _abi.ptr(v), _abi.ptr(ctx),
+          _abi.ptr(d_ctx), _abi.ptr(lse), _abi.ptr(d_q), _abi.ptr(d_k), _abi.ptr(d_v), B, Lq, Lk, H, 64, q_rs, k_rs, v_rs, H * 64, H * 64, H * 64,
+          float(scale), *tail)
     return d_q, d_k, d_v
+
+
+def xattn_fwd(q, k, v, B, Lq, Lk, H, scale):
+    """softmax(q k^T scale) v with queries and keys from two sequences (csrc/attn_stream.hip): q (B, Lq, H * 64), k and v (B, Lk, H * 64)
+    -> ctx (B, Lq, H * 64), lse (B, H, Lq), both dense.  The operands may be views (a slice of a packed [k|v] or qkv product): see
+    _xattn_operand for the stride rule; the strides are taken from the tensors.  1 <= Lq, Lk <= ATTN_MAX_L; everything else raises
+    before a launch."""
+    return _xattn_fwd(q, k, v, B, Lq, Lk, H, scale)
+
+
+def xattn_bwd(q, k, v, ctx, d_ctx, lse, B, Lq, Lk, H, scale):
+    """-> (d_q (B, Lq, H * 64), d_k, d_v (B, Lk, H * 64)) from d_ctx and the forward's ctx / lse.  q, k, v as in xattn_fwd; ctx, d_ctx and
+    lse dense.  The three gradients are fresh dense tensors (so they overlap nothing), every element written by exactly one workgroup: no
+    atomics, two calls give the same bits."""
+    return _xattn_bwd(q, k, v, ctx, d_ctx, lse, B, Lq, Lk, H, scale)
+
+
+def xattn_prefix_fwd(q, k, v, B, Lq, Lk, H, scale, split_q, split_k):
+    """xattn_fwd under the prefix-visibility mask of csrc/attn_stream.hip: query rows < split_q see the keys < split_k, the other rows see
+    all Lk keys (AdaPoinTr's denoising queries: Lq = Lk = L, both splits L - D) -> ctx (B, Lq, H * 64), lse (B, H, Lq) over the visible keys.
+    Operands and their checks as in xattn_fwd; 0 <= split_q <= Lq and 1 <= split_k <= Lk, everything else raises before a launch."""
+    return _xattn_fwd(q, k, v, B, Lq, Lk, H, scale, (split_q, split_k))
+
+
+def xattn_prefix_bwd(q, k, v, ctx, d_ctx, lse, B, Lq, Lk, H, scale, split_q, split_k):
+    """-> (d_q, d_k, d_v) of xattn_prefix_fwd, as xattn_bwd returns them: fresh dense tensors, every element written by exactly one
+    workgroup, two calls give the same bits.  Keys no row sees (split_q == Lq, keys >= split_k) get zero gradients."""
+    return _xattn_bwd(q, k, v, ctx, d_ctx, lse, B, Lq, Lk, H, scale, (split_q, split_k))
 
 
 # ------------------------------------------------------------------ prompt propagation

@@ -529,7 +529,7 @@ int upp_attn_bwd(const float *qkv, const float *ctx, const float *d_ctx, const f
 /* (L <= 96: the register-resident 16x16x4 MFMA kernels of attn_flash16.hip; L <= 160: attn_long.hip, K and V resident in the LDS;
  *  L <= UPP_ATTN_MAX_L: attn_stream.hip, 64-row query blocks against K / V streamed in 64-key blocks, online softmax) */
 /* ---- cross-attention: queries and keys from two sequences -----------------------------------
- * softmax(q k^T * scale) v of CrossAttention.forward (reference models/Transformer.py:148-152) and its autograd; csrc/attn_cross.hip,
+ * softmax(q k^T * scale) v of CrossAttention.forward (reference models/Transformer.py:148-152) and its autograd; csrc/attn_stream.hip,
  * one streaming family (the structure and the summation order of attn_stream.hip) for every length in the range.
  *   q, d_q            (B, Lq, rs) arrays: head h lives in columns [64h, 64h+64) counted from the pointer
  *   k, v, d_k, d_v    (B, Lk, rs) arrays with the same head layout
@@ -554,7 +554,7 @@ int upp_xattn_bwd(const float *q, const float *k, const float *v, const float *c
                   long long dq_rs, long long dk_rs, long long dv_rs, float scale, void *stream);
 /* ---- denoising-query attention: cross-attention under a prefix-visibility mask --------------
  * The masked self-attention of AdaPoinTr's decoder in training (reference models/AdaPoinTr.py:217-229, Attention.forward(x, mask) at
- * models/Transformer_utils.py:100-120: masked_fill(-finfo.max) before the softmax); csrc/attn_prefix.hip.  Operands, strides, layouts,
+ * models/Transformer_utils.py:100-120: masked_fill(-finfo.max) before the softmax); csrc/attn_stream.hip.  Operands, strides, layouts,
  * refusals and the caller's duties are those of upp_xattn_fwd / upp_xattn_bwd ("Stride rule" above).  Two integers are added:
  *   query rows i <  split_q see the keys j < split_k;   query rows i >= split_q see all Lk keys.
  * AdaPoinTr: Lq = Lk = L, split_q = split_k = L - D for D denoising queries, q / k / v views of one packed qkv.

@@ -1,4 +1,4 @@
-"""The cross-attention kernels (csrc/attn_cross.hip: one streaming family for 1 <= Lq, Lk <= ATTN_MAX_L), their autograd node and their
+"""The cross-attention kernels (csrc/attn_stream.hip: one streaming family for 1 <= Lq, Lk <= ATTN_MAX_L), their autograd node and their
 first users, models.upp_layers.CrossAttention and DecoderBlock, on the GPU: parity of ctx, lse, d_q, d_k, d_v with the torch formulation
 under float64 arbitration, strided operands (bit-equal to contiguous copies and, for Lq = Lk beyond 160, to ops.attn_fwd / attn_bwd on the
 same packed qkv), the hazards of a softmax with the hot keys in the first and in the last 64-key block, independence of every (sample,

@@ -1,4 +1,4 @@
-"""The denoising-query (prefix-visibility) attention kernels (csrc/attn_prefix.hip) and their autograd node on the GPU: query rows
+"""The denoising-query (prefix-visibility) attention kernels (csrc/attn_stream.hip) and their autograd node on the GPU: query rows
 < split_q see the keys < split_k, the other rows see every key.  Parity of ctx, lse, d_q, d_k, d_v with the torch masked formulation
 (the reference's masked_fill(-finfo.max) + softmax, models/Transformer_utils.py:100-120) under float64 arbitration; the forward's bits
 against ops.xattn_fwd on the two row groups taken apart; the unmasked ends of both split ranges against ops.xattn_fwd / xattn_bwd bit

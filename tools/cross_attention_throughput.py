@@ -1,4 +1,4 @@
-"""Cross-attention core: ops.xattn_fwd / ops.xattn_bwd (csrc/attn_cross.hip) against the torch formulation (q k^T -> * scale -> softmax
+"""Cross-attention core: ops.xattn_fwd / ops.xattn_bwd (csrc/attn_stream.hip) against the torch formulation (q k^T -> * scale -> softmax
 -> @ v and its autograd, reference models/Transformer.py:144-152), which is what a decoder block runs without the kernels.  Shapes
 (B, H, Lq, Lk) in --shapes: PoinTr's decoder (224 queries over 128 proxies), AdaPoinTr's with its denoising queries (576 over 256) and
 64 over 64, the short case that the single streaming family serves worst.  head_dim 64, f32, three separate dense operands.  Times come

@@ -1,4 +1,4 @@
-"""Denoising-query attention core: ops.xattn_prefix_fwd / xattn_prefix_bwd (csrc/attn_prefix.hip) against  (i) the torch masked formulation
+"""Denoising-query attention core: ops.xattn_prefix_fwd / xattn_prefix_bwd (csrc/attn_stream.hip) against  (i) the torch masked formulation
 (q k^T -> * scale -> masked_fill(mask, -finfo.max) -> softmax -> @ v and its autograd, reference models/Transformer_utils.py:100-120),
 which is what AdaPoinTr's decoder runs in training without the kernels, and  (ii) ops.xattn_fwd / xattn_bwd without a mask on the same
 operands: the masked call has fewer blocks to walk and should not be slower.  Shapes (B, H, L, D) in --shapes: L tokens of which the last
