@@ -230,62 +230,50 @@ extern "C" int upp_chamfer_bwd(const float *xyz1, const float *xyz2, const int32
 // ---- the deterministic sibling ---------------------------------------------------------------------------------------------------
 // The same terms as the two kernels above, summed in a DEFINED order (include/upp_hip.h upp_chamfer_bwd_det): the target starts at
 // +0.0f (as the zero-filled accumulators above do), adds its own term, then subtracts the term of every point of the other cloud that
-// chose it, in ascending index of that point.  One lane per target, det_scan.h's ordered pull; the foreign terms of a chunk are
+// chose it, in ascending index of that point.  A job of det_scan.h's det_scatter_kernel: the foreign terms of a chunk are
 // computed once by the staging threads (the arithmetic of chamfer_grad_kernel: g = gd * 2, v = g * (pa - pb), the exact negation
 // stored) and read by 256 targets.  Worst case and cost: det_scan.h.
 namespace {
 
-__global__ __launch_bounds__(kDetThreads) void chamfer_grad_det_kernel(const float *__restrict__ xyz1, const float *__restrict__ xyz2,
-                                                                       const int32_t *__restrict__ idx1, const int32_t *__restrict__ idx2,
-                                                                       const float *__restrict__ gd1, const float *__restrict__ gd2,
-                                                                       float *__restrict__ g1, float *__restrict__ g2, int B, int n, int m) {
-    __shared__ __attribute__((aligned(16))) int32_t keys[kDetChunk];
-    __shared__ float vals[kDetChunk * 3];
-    const int tid = threadIdx.x;
-    const long long t1 = (n + kDetThreads - 1) / kDetThreads, t2 = (m + kDetThreads - 1) / kDetThreads;
-    const long long items = (long long)B * (t1 + t2);
-    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
-        const long long b = it / (t1 + t2), r = it - b * (t1 + t2);
+struct ChamferJob {
+    const float *__restrict__ xyz1, *__restrict__ xyz2;
+    const int32_t *__restrict__ idx1, *__restrict__ idx2;
+    const float *__restrict__ gd1, *__restrict__ gd2;
+    float *__restrict__ g1, *__restrict__ g2;
+    int B, n, m;
+    // a: the cloud of this workgroup's targets, b: the other one
+    struct Item { const float *pa, *pb; const int32_t *ia, *ib; const float *ga, *gb; long long b; bool dir1; long long row0; int T; long long S; };
+    __host__ __device__ long long items() const { return B * (det_tiles(n) + det_tiles(m)); }
+    __device__ __forceinline__ Item item(long long it) const {
+        const long long t1 = det_tiles(n), t2 = det_tiles(m), b = it / (t1 + t2), r = it - b * (t1 + t2);
         const bool dir1 = r < t1;
-        const int na = dir1 ? n : m, nb = dir1 ? m : n;                 // a: the cloud of this workgroup's targets, b: the other one
-        const float *pa = (dir1 ? xyz1 : xyz2) + (size_t)b * na * 3, *pb = (dir1 ? xyz2 : xyz1) + (size_t)b * nb * 3;
-        const int32_t *ia = (dir1 ? idx1 : idx2) + (size_t)b * na, *ib = (dir1 ? idx2 : idx1) + (size_t)b * nb;
-        const float *ga = (dir1 ? gd1 : gd2) + (size_t)b * na, *gb = (dir1 ? gd2 : gd1) + (size_t)b * nb;
-        const long long j = (dir1 ? r : r - t1) * kDetThreads + tid;
-        const int target = j < na ? (int)j : -2;
-        float acc[3] = {0.0f, 0.0f, 0.0f};
-        if (j < na) {
-            const int p = min(max(ia[j], 0), nb - 1);
-            const float g = __fmul_rn(ga[j], 2.0f);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) acc[c] = __fadd_rn(0.0f, __fmul_rn(g, __fsub_rn(pa[(size_t)j * 3 + c], pb[(size_t)p * 3 + c])));
-        }
-        for (int c0 = 0; c0 < nb; c0 += kDetChunk) {
-            const int len = min(kDetChunk, nb - c0), len4 = (len + 3) & ~3;
-            __syncthreads();
-#pragma unroll
-            for (int i = tid; i < kDetChunk; i += kDetThreads) {
-                if (i < len) {
-                    const size_t s = (size_t)c0 + i;
-                    const int key = ib[s];
-                    const int p = min(max(key, 0), na - 1);
-                    const float g = __fmul_rn(gb[s], 2.0f);
-                    keys[i] = key;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) vals[i * 3 + c] = -__fmul_rn(g, __fsub_rn(pb[s * 3 + c], pa[(size_t)p * 3 + c]));
-                } else if (i < len4) {
-                    keys[i] = -1;
-                }
-            }
-            __syncthreads();
-            det_pull<3>(keys, vals, len4, target, acc);
-        }
-        if (j < na) {
-            float *o = (dir1 ? g1 : g2) + ((size_t)b * na + j) * 3;
-            o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
-        }
+        const int na = dir1 ? n : m, nb = dir1 ? m : n;
+        return {(dir1 ? xyz1 : xyz2) + (size_t)b * na * 3, (dir1 ? xyz2 : xyz1) + (size_t)b * nb * 3,
+                (dir1 ? idx1 : idx2) + (size_t)b * na, (dir1 ? idx2 : idx1) + (size_t)b * nb,
+                (dir1 ? gd1 : gd2) + (size_t)b * na, (dir1 ? gd2 : gd1) + (size_t)b * nb,
+                b, dir1, (dir1 ? r : r - t1) * kDetThreads, na, nb};
     }
-}
+    __device__ __forceinline__ void first(const Item &w, long long j, float (&acc)[3]) const {
+        const int p = min(max(w.ia[j], 0), (int)w.S - 1);
+        const float g = __fmul_rn(w.ga[j], 2.0f);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] = __fadd_rn(0.0f, __fmul_rn(g, __fsub_rn(w.pa[(size_t)j * 3 + c], w.pb[(size_t)p * 3 + c])));
+    }
+    // the partner index goes through as the key; it is clamped for the coordinate read alone
+    __device__ __forceinline__ void stage(const Item &w, long long c0, int i, int32_t &key, float *v) const {
+        const int s = (int)c0 + i;                                      // (n and m are ints)
+        const int k = w.ib[s];
+        const int p = min(max(k, 0), w.T - 1);
+        const float g = __fmul_rn(w.gb[s], 2.0f);
+        key = k;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = -__fmul_rn(g, __fsub_rn(w.pb[(size_t)s * 3 + c], w.pa[(size_t)p * 3 + c]));
+    }
+    __device__ __forceinline__ void store(const Item &w, long long j, const float (&acc)[3]) const {
+        float *o = (w.dir1 ? g1 : g2) + ((size_t)w.b * w.T + j) * 3;
+        o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
+    }
+};
 
 }  // namespace
 
@@ -295,9 +283,7 @@ extern "C" int upp_chamfer_bwd_det(const float *xyz1, const float *xyz2, const i
     if (!xyz1 || !xyz2 || !idx1 || !idx2 || !grad_dist1 || !grad_dist2 || !g1 || !g2 || B < 0 || n < 1 || m < 1)
         return UPP_E_BADARG;
     if (B == 0) return 0;
-    const long long items = (long long)B * ((n + kDetThreads - 1) / kDetThreads + (m + kDetThreads - 1) / kDetThreads);
-    hipLaunchKernelGGL(chamfer_grad_det_kernel, dim3(det_grid(items)), dim3(kDetThreads), 0, (hipStream_t)stream, xyz1, xyz2, idx1, idx2,
-                       grad_dist1, grad_dist2, g1, g2, B, n, m);
+    det_launch<3>(ChamferJob{xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2, g1, g2, B, n, m}, stream);
     return upp_launch_status();
 }
 

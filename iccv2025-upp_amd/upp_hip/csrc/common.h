@@ -125,6 +125,12 @@ __device__ __forceinline__ void stage_floats(float *dst, const float *__restrict
 // argument.  Defined in abi.hip (relaxed atomics); the library never reads the environment.
 int upp_option(int key);
 
+// grid of a flat grid-stride kernel: one thread per element in workgroups of `block`, at most `cap` workgroups (the rest by the stride)
+static inline unsigned grid_for(long long total, int block, long long cap) {
+    const long long g = (total + block - 1) / block;
+    return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+
 static inline int upp_launch_status(void) {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;

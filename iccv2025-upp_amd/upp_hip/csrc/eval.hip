@@ -11,12 +11,7 @@ namespace {
 
 constexpr int kBlock = 256;
 
-inline int grid_for(long long total) {
-    long long g = (total + kBlock - 1) / kBlock;
-    if (g > 4096) g = 4096;
-    if (g < 1) g = 1;
-    return (int)g;
-}
+constexpr long long kGridCap = 4096;
 
 // out[(v*B + b), i, c] = superset[b, pick[v,i], c] * scale[v,b,c] + shift[v,b,c]   (two roundings: torch's `pc * s + t`)
 // A pick outside [0, S) is never dereferenced: its point is written as NaN.
@@ -93,7 +88,7 @@ extern "C" int upp_vote_points(const float *superset, const int32_t *pick, const
     if (!superset || !pick || !out || B < 1 || S < 1 || N < 1 || V < 1) return UPP_E_BADARG;
     if ((long long)V * B > 0x7fffffffLL) return UPP_E_RANGE;
     const long long total = (long long)V * B * N * 3;
-    hipLaunchKernelGGL(vote_points_kernel, dim3(grid_for(total)), dim3(kBlock), 0, (hipStream_t)stream, superset, pick, scale, shift,
+    hipLaunchKernelGGL(vote_points_kernel, dim3(grid_for(total, kBlock, kGridCap)), dim3(kBlock), 0, (hipStream_t)stream, superset, pick, scale, shift,
                        out, B, S, N, total);
     return upp_launch_status();
 }

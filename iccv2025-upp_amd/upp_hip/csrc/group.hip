@@ -12,13 +12,7 @@
 namespace {
 
 constexpr int kBlock = 256;
-
-inline int grid_for(long long total) {
-    long long g = (total + kBlock - 1) / kBlock;
-    if (g > 2048) g = 2048;  // 256 CUs x 8 blocks, grid-stride the rest
-    if (g < 1) g = 1;
-    return (int)g;
-}
+constexpr long long kGridCap = 2048;  // 256 CUs x 8 blocks, grid-stride the rest
 
 // out[b,c,j] = feat[b,c,idx[b,j]]
 __global__ void gather_fwd_kernel(const float *__restrict__ feat, const int32_t *__restrict__ idx, float *__restrict__ out,
@@ -98,83 +92,55 @@ __global__ __launch_bounds__(256) void fps_gather_bwd_kernel(const float *__rest
     }
 }
 
-// ---- the deterministic siblings (include/upp_hip.h "deterministic scatter-adds") ------------------------------------------------------
+// ---- the deterministic siblings (include/upp_hip.h "deterministic scatter-adds"): two jobs of det_scan.h's det_scatter_kernel -----------
 // out[b][r][0..2] = +0.0f, then + val[b][s][0..2] for every source s with idx[b][s] == r, in ascending s: the xyz gradient of the grouping
-// gather (IdxT = int64, s = g * K + k) and of the FPS centre gather (int32).  One lane per target row, det_scan.h's ordered pull; every
-// row is written (rows that nobody references: +0.0f), so the caller zero-fills nothing.  Indices outside [0, N) are skipped.
+// gather (IdxT = int64, s = g * K + k) and of the FPS centre gather (int32).  Every row is written (rows that nobody references: +0.0f),
+// so the caller zero-fills nothing.  Indices outside [0, N) are skipped.
 template <typename IdxT>
-__global__ __launch_bounds__(kDetThreads) void rows3_bwd_det_kernel(const float *__restrict__ val, const IdxT *__restrict__ idx,
-                                                                    float *__restrict__ out, int B, int N, long long S) {
-    __shared__ __attribute__((aligned(16))) int32_t keys[kDetChunk];
-    __shared__ float vals[kDetChunk * 3];
-    const int tid = threadIdx.x;
-    const long long tiles = (N + kDetThreads - 1) / kDetThreads, items = (long long)B * tiles;
-    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
-        const long long b = it / tiles, r = (it - b * tiles) * kDetThreads + tid;
-        const int target = r < N ? (int)r : -2;
-        const IdxT *ib = idx + (size_t)b * S;
-        const float *vb = val + (size_t)b * S * 3;
-        float acc[3] = {0.0f, 0.0f, 0.0f};
-        for (long long c0 = 0; c0 < S; c0 += kDetChunk) {
-            const int len = (int)min((long long)kDetChunk, S - c0), len4 = (len + 3) & ~3;
-            __syncthreads();
-#pragma unroll
-            for (int i = tid; i < kDetChunk; i += kDetThreads) {
-                if (i < len) { const IdxT k = ib[c0 + i]; keys[i] = (k >= 0 && k < (IdxT)N) ? (int32_t)k : -1; }
-                else if (i < len4) keys[i] = -1;
-            }
-            stage_floats(vals, vb + (size_t)c0 * 3, len * 3, tid, kDetThreads);
-            __syncthreads();
-            det_pull<3>(keys, vals, len4, target, acc);
-        }
-        if (r < N) {
-            float *o = out + ((size_t)b * N + r) * 3;
-            o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
-        }
+struct Rows3Job {
+    const float *__restrict__ val;
+    const IdxT *__restrict__ idx;
+    float *__restrict__ out;
+    int B, N;
+    long long S;
+    __host__ __device__ long long items() const { return B * det_tiles(N); }
+    __device__ __forceinline__ DetItem item(long long it) const { return det_item(it, 1, N, S); }
+    __device__ __forceinline__ void first(const DetItem &, long long, float (&)[3]) const {}
+    __device__ __forceinline__ void stage(const DetItem &w, long long c0, int i, int32_t &key, float *v) const {
+        const IdxT k = (idx + (size_t)w.b * S + c0)[i];
+        key = (k >= 0 && k < (IdxT)N) ? (int32_t)k : -1;
+        const float *p = val + ((size_t)w.b * S + c0) * 3 + i * 3;
+        v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
     }
-}
+    __device__ __forceinline__ void store(const DetItem &w, long long r, const float (&acc)[3]) const {
+        float *o = out + ((size_t)w.b * N + r) * 3;
+        o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
+    }
+};
 
 // grad_feat[b][ch][r] = +0.0f, then + grad_out[b][ch][j] for every j with idx[b][j] == r, in ascending j.  A workgroup owns 256 targets of
 // one cloud and kDetCh channels: the key chunk it stages serves all of them.
-constexpr int kDetCh = 4;
-__global__ __launch_bounds__(kDetThreads) void gather_bwd_det_kernel(const float *__restrict__ grad_out, const int32_t *__restrict__ idx,
-                                                                     float *__restrict__ grad_feat, int B, int C, int N, int M) {
-    __shared__ __attribute__((aligned(16))) int32_t keys[kDetChunk];
-    __shared__ float vals[kDetChunk * kDetCh];
-    const int tid = threadIdx.x;
-    const long long tiles = (N + kDetThreads - 1) / kDetThreads, groups = (C + kDetCh - 1) / kDetCh, items = (long long)B * groups * tiles;
-    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
-        const long long b = it / (groups * tiles), rest = it - b * groups * tiles;
-        const int ch0 = (int)(rest / tiles) * kDetCh;
-        const long long r = (rest % tiles) * kDetThreads + tid;
-        const int target = r < N ? (int)r : -2;
-        const int32_t *ib = idx + (size_t)b * M;
-        float acc[kDetCh] = {0.0f, 0.0f, 0.0f, 0.0f};
-        for (int c0 = 0; c0 < M; c0 += kDetChunk) {
-            const int len = min(kDetChunk, M - c0), len4 = (len + 3) & ~3;
-            __syncthreads();
+struct GatherJob {
+    const float *__restrict__ grad_out;
+    const int32_t *__restrict__ idx;
+    float *__restrict__ grad_feat;
+    int B, C, N, M;
+    __host__ __device__ long long items() const { return B * det_groups(C) * det_tiles(N); }
+    __device__ __forceinline__ DetItem item(long long it) const { return det_item(it, C, N, M); }
+    __device__ __forceinline__ void first(const DetItem &, long long, float (&)[kDetCh]) const {}
+    __device__ __forceinline__ void stage(const DetItem &w, long long c0, int i, int32_t &key, float *v) const {
+        const int s = (int)c0 + i;                                      // (M is an int)
+        const int k = (idx + (size_t)w.b * M)[s];
+        key = (k >= 0 && k < N) ? k : -1;
 #pragma unroll
-            for (int i = tid; i < kDetChunk; i += kDetThreads) {
-                if (i < len) {
-                    const int k = ib[c0 + i];
-                    keys[i] = (k >= 0 && k < N) ? k : -1;
-#pragma unroll
-                    for (int v = 0; v < kDetCh; ++v)
-                        vals[i * kDetCh + v] = ch0 + v < C ? grad_out[((size_t)b * C + ch0 + v) * M + c0 + i] : 0.0f;
-                } else if (i < len4) {
-                    keys[i] = -1;
-                }
-            }
-            __syncthreads();
-            det_pull<kDetCh>(keys, vals, len4, target, acc);
-        }
-        if (r < N) {
-#pragma unroll
-            for (int v = 0; v < kDetCh; ++v)
-                if (ch0 + v < C) grad_feat[((size_t)b * C + ch0 + v) * N + r] = acc[v];
-        }
+        for (int c = 0; c < kDetCh; ++c) v[c] = w.ch0 + c < C ? grad_out[((size_t)w.b * C + w.ch0 + c) * M + s] : 0.0f;
     }
-}
+    __device__ __forceinline__ void store(const DetItem &w, long long r, const float (&acc)[kDetCh]) const {
+#pragma unroll
+        for (int c = 0; c < kDetCh; ++c)
+            if (w.ch0 + c < C) grad_feat[((size_t)w.b * C + w.ch0 + c) * N + r] = acc[c];
+    }
+};
 
 }  // namespace
 
@@ -182,7 +148,7 @@ extern "C" int upp_gather_fwd(const float *feat, const int32_t *idx, float *out,
     if (!feat || !idx || !out || B < 0 || C < 0 || N < 1 || M < 0) return UPP_E_BADARG;
     const long long total = (long long)B * C * M;
     if (total == 0) return 0;
-    hipLaunchKernelGGL(gather_fwd_kernel, dim3(grid_for(total)), dim3(kBlock), 0, (hipStream_t)stream, feat, idx, out, C, N, M, total);
+    hipLaunchKernelGGL(gather_fwd_kernel, dim3(grid_for(total, kBlock, kGridCap)), dim3(kBlock), 0, (hipStream_t)stream, feat, idx, out, C, N, M, total);
     return upp_launch_status();
 }
 
@@ -190,7 +156,7 @@ extern "C" int upp_gather_bwd(const float *grad_out, const int32_t *idx, float *
     if (!grad_out || !idx || !grad_feat || B < 0 || C < 0 || N < 1 || M < 0) return UPP_E_BADARG;
     const long long total = (long long)B * C * M;
     if (total == 0) return 0;
-    hipLaunchKernelGGL(gather_bwd_kernel, dim3(grid_for(total)), dim3(kBlock), 0, (hipStream_t)stream, grad_out, idx, grad_feat, C, N, M, total);
+    hipLaunchKernelGGL(gather_bwd_kernel, dim3(grid_for(total, kBlock, kGridCap)), dim3(kBlock), 0, (hipStream_t)stream, grad_out, idx, grad_feat, C, N, M, total);
     return upp_launch_status();
 }
 
@@ -205,7 +171,7 @@ extern "C" int upp_group_fwd(const float *xyz, const float *center, const int64_
     if (!xyz || !center || !idx || !out || B < 0 || N < 1 || G < 0 || K < 0) return UPP_E_BADARG;
     const long long total = (long long)B * G * K * 3;
     if (total == 0) return 0;
-    hipLaunchKernelGGL(group_fwd_kernel, dim3(grid_for(total)), dim3(kBlock), 0, (hipStream_t)stream, xyz, center, idx, out, N, G, K, total);
+    hipLaunchKernelGGL(group_fwd_kernel, dim3(grid_for(total, kBlock, kGridCap)), dim3(kBlock), 0, (hipStream_t)stream, xyz, center, idx, out, N, G, K, total);
     return upp_launch_status();
 }
 
@@ -214,10 +180,10 @@ extern "C" int upp_group_bwd(const float *grad_out, const int64_t *idx, float *g
     const long long total = (long long)B * G * K * 3;
     if (total == 0) return 0;
     if (grad_xyz)
-        hipLaunchKernelGGL(group_bwd_xyz_kernel, dim3(grid_for(total)), dim3(kBlock), 0, (hipStream_t)stream, grad_out, idx, grad_xyz, N, G, K, total);
+        hipLaunchKernelGGL(group_bwd_xyz_kernel, dim3(grid_for(total, kBlock, kGridCap)), dim3(kBlock), 0, (hipStream_t)stream, grad_out, idx, grad_xyz, N, G, K, total);
     if (grad_center) {
         const long long tc = (long long)B * G * 3;
-        hipLaunchKernelGGL(group_bwd_center_kernel, dim3(grid_for(tc)), dim3(kBlock), 0, (hipStream_t)stream, grad_out, grad_center, K, tc);
+        hipLaunchKernelGGL(group_bwd_center_kernel, dim3(grid_for(tc, kBlock, kGridCap)), dim3(kBlock), 0, (hipStream_t)stream, grad_out, grad_center, K, tc);
     }
     return upp_launch_status();
 }
@@ -225,17 +191,14 @@ extern "C" int upp_group_bwd(const float *grad_out, const int64_t *idx, float *g
 extern "C" int upp_gather_bwd_det(const float *grad_out, const int32_t *idx, float *grad_feat, int B, int C, int N, int M, void *stream) {
     if (!grad_out || !idx || !grad_feat || B < 0 || C < 0 || N < 1 || M < 0) return UPP_E_BADARG;
     if (B == 0 || C == 0) return 0;
-    const long long items = (long long)B * ((C + kDetCh - 1) / kDetCh) * ((N + kDetThreads - 1) / kDetThreads);
-    hipLaunchKernelGGL(gather_bwd_det_kernel, dim3(det_grid(items)), dim3(kDetThreads), 0, (hipStream_t)stream, grad_out, idx, grad_feat, B, C, N, M);
+    det_launch<kDetCh>(GatherJob{grad_out, idx, grad_feat, B, C, N, M}, stream);
     return upp_launch_status();
 }
 
 extern "C" int upp_fps_gather_bwd_det(const float *g_centers, const int32_t *idx, float *g_xyz, int B, int N, int M, void *stream) {
     if (!g_centers || !idx || !g_xyz || B < 0 || N < 1 || M < 0) return UPP_E_BADARG;
     if (B == 0) return 0;
-    const long long items = (long long)B * ((N + kDetThreads - 1) / kDetThreads);
-    hipLaunchKernelGGL(rows3_bwd_det_kernel<int32_t>, dim3(det_grid(items)), dim3(kDetThreads), 0, (hipStream_t)stream, g_centers, idx, g_xyz, B, N,
-                       (long long)M);
+    det_launch<3>(Rows3Job<int32_t>{g_centers, idx, g_xyz, B, N, (long long)M}, stream);
     return upp_launch_status();
 }
 
@@ -243,13 +206,9 @@ extern "C" int upp_group_bwd_det(const float *grad_out, const int64_t *idx, floa
                                  void *stream) {
     if (!grad_out || !idx || B < 0 || N < 1 || G < 0 || K < 0) return UPP_E_BADARG;
     if (B == 0) return 0;
-    if (grad_xyz) {
-        const long long items = (long long)B * ((N + kDetThreads - 1) / kDetThreads);
-        hipLaunchKernelGGL(rows3_bwd_det_kernel<int64_t>, dim3(det_grid(items)), dim3(kDetThreads), 0, (hipStream_t)stream, grad_out, idx, grad_xyz, B, N,
-                           (long long)G * K);
-    }
+    if (grad_xyz) det_launch<3>(Rows3Job<int64_t>{grad_out, idx, grad_xyz, B, N, (long long)G * K}, stream);
     const long long tc = (long long)B * G * 3;
     if (grad_center && tc > 0 && K > 0)            // (k ascending already: the sibling's kernel, launched as the sibling launches it)
-        hipLaunchKernelGGL(group_bwd_center_kernel, dim3(grid_for(tc)), dim3(kBlock), 0, (hipStream_t)stream, grad_out, grad_center, K, tc);
+        hipLaunchKernelGGL(group_bwd_center_kernel, dim3(grid_for(tc, kBlock, kGridCap)), dim3(kBlock), 0, (hipStream_t)stream, grad_out, grad_center, K, tc);
     return upp_launch_status();
 }

@@ -22,11 +22,7 @@ constexpr int kKpFloats = 12288;          // floats of one staged chunk (48 KiB)
 constexpr int kKpPad = 64;
 constexpr int kKpMaxD = 32, kKpMaxK = 64;
 constexpr int kBlock = 256;
-
-static inline unsigned grid_for(long long total) {
-    const long long g = (total + kBlock - 1) / kBlock;
-    return (unsigned)(g < 1 ? 1 : (g > 65535LL * 16 ? 65535LL * 16 : g));
-}
+constexpr long long kGridCap = 65535LL * 16;
 
 // points per chunk and the row stride of the [d][point] image.  The stride's low bits spread the D rows over the banks for the staging
 // WRITES (32 consecutive floats of p2 are 32 / D points x D rows); the reads are consecutive words whatever the stride.
@@ -204,55 +200,46 @@ __global__ __launch_bounds__(kBlock) void knn_scatter_add_kernel(const float *__
 }
 
 // out[b][r][u] = +0.0f, then + (or -) src[b][l][k][u] for every (l, k) that takes part and has idx[b][l][k] == r, in ascending l * K + k
-// (include/upp_hip.h).  As gather_bwd_det_kernel (group.hip): a workgroup owns 256 target rows of one cloud and kDetCh of the U columns.
-constexpr int kDetCh = 4;
-__global__ __launch_bounds__(kDetThreads) void knn_scatter_add_det_kernel(const float *__restrict__ src, const int64_t *__restrict__ idx,
-                                                                          const int64_t *__restrict__ rows, const int64_t *__restrict__ slots,
-                                                                          float *__restrict__ out, int B, int M, int L, int K, int U,
-                                                                          int negate) {
-    __shared__ __attribute__((aligned(16))) int32_t keys[kDetChunk];
-    __shared__ float vals[kDetChunk * kDetCh];
-    const int tid = threadIdx.x;
-    const long long S = (long long)L * K;
-    const long long tiles = (M + kDetThreads - 1) / kDetThreads, groups = (U + kDetCh - 1) / kDetCh, items = (long long)B * groups * tiles;
-    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
-        const long long b = it / (groups * tiles), rest = it - b * groups * tiles;
-        const int ch0 = (int)(rest / tiles) * kDetCh;
-        const long long r = (rest % tiles) * kDetThreads + tid;
-        const int target = r < M ? (int)r : -2;
-        const int nrows = kp_len(rows, (int)b, L), nslots = kp_len(slots, (int)b, K);
-        const int64_t *ib = idx + (size_t)b * S;
-        const float *sb = src + (size_t)b * S * U;
-        float acc[kDetCh] = {0.0f, 0.0f, 0.0f, 0.0f};
-        for (long long c0 = 0; c0 < S; c0 += kDetChunk) {
-            const int len = (int)min((long long)kDetChunk, S - c0), len4 = (len + 3) & ~3;
-            __syncthreads();
+// (include/upp_hip.h): a job of det_scan.h's det_scatter_kernel.  As GatherJob (group.hip) a workgroup owns 256 target rows of one cloud
+// and kDetCh of the U columns.
+struct KnnScatterJob {
+    const float *__restrict__ src;
+    const int64_t *__restrict__ idx;
+    const int64_t *__restrict__ rows;
+    const int64_t *__restrict__ slots;
+    float *__restrict__ out;
+    int B, M, L, K, U, negate;
+    struct Item : DetItem { const int64_t *ib; const float *sb; int nrows, nslots; };          // (the cloud's idx and src)
+    __host__ __device__ long long items() const { return B * det_groups(U) * det_tiles(M); }
+    __device__ __forceinline__ Item item(long long it) const {
+        const DetItem w = det_item(it, U, M, (long long)L * K);
+        return {w, idx + (size_t)w.b * w.S, src + (size_t)w.b * w.S * U, len_of(rows, w.b, L), len_of(slots, w.b, K)};
+    }
+    // kp_len() read through the constant address space, as a `const __restrict__` kernel argument is read (one scalar load an item):
+    // nothing writes the lengths while a kernel runs, and `__restrict__` on a struct member does not tell the compiler so
+    __device__ static __forceinline__ int len_of(const int64_t *lengths, long long b, int P) {
+        if (!lengths) return P;
+        const int64_t v = ((const __attribute__((address_space(4))) int64_t *)lengths)[b];
+        return v < 0 ? 0 : (v > (int64_t)P ? P : (int)v);
+    }
+    __device__ __forceinline__ void first(const Item &, long long, float (&)[kDetCh]) const {}
+    __device__ __forceinline__ void stage(const Item &w, long long c0, int i, int32_t &key, float *v) const {
+        const long long s = c0 + i;
+        const int64_t j = w.ib[s];
+        const bool ok = (int)(s / K) < w.nrows && (int)(s % K) < w.nslots && j >= 0 && j < (int64_t)M;
+        key = ok ? (int32_t)j : -1;
 #pragma unroll
-            for (int i = tid; i < kDetChunk; i += kDetThreads) {
-                if (i < len) {
-                    const long long s = c0 + i;
-                    const int64_t j = ib[s];
-                    const bool ok = (int)(s / K) < nrows && (int)(s % K) < nslots && j >= 0 && j < (int64_t)M;
-                    keys[i] = ok ? (int32_t)j : -1;
-#pragma unroll
-                    for (int v = 0; v < kDetCh; ++v) {
-                        const float x = ch0 + v < U ? sb[(size_t)s * U + ch0 + v] : 0.0f;
-                        vals[i * kDetCh + v] = negate ? -x : x;
-                    }
-                } else if (i < len4) {
-                    keys[i] = -1;
-                }
-            }
-            __syncthreads();
-            det_pull<kDetCh>(keys, vals, len4, target, acc);
-        }
-        if (r < M) {
-#pragma unroll
-            for (int v = 0; v < kDetCh; ++v)
-                if (ch0 + v < U) out[((size_t)b * M + r) * U + ch0 + v] = acc[v];
+        for (int c = 0; c < kDetCh; ++c) {
+            const float x = w.ch0 + c < U ? w.sb[(size_t)s * U + w.ch0 + c] : 0.0f;
+            v[c] = negate ? -x : x;
         }
     }
-}
+    __device__ __forceinline__ void store(const Item &w, long long r, const float (&acc)[kDetCh]) const {
+#pragma unroll
+        for (int c = 0; c < kDetCh; ++c)
+            if (w.ch0 + c < U) out[((size_t)w.b * M + r) * U + w.ch0 + c] = acc[c];
+    }
+};
 
 // the shared argument checks of the gather / scatter entry points: (N, M, L, K, U)
 static int kp_rows_args(const void *a, const void *b, const void *c, int N, int M, int L, int K, int U) {
@@ -288,10 +275,10 @@ extern "C" int upp_knn_points_bwd(const float *p1, const float *p2, const int64_
     const long long total = (long long)N * P1 * D;
     hipStream_t st = (hipStream_t)stream;
     if (norm == 2)
-        hipLaunchKernelGGL((knn_points_bwd_kernel<2>), dim3(grid_for(total)), dim3(kBlock), 0, st, p1, p2, idx, grad_dists, lengths1, lengths2,
+        hipLaunchKernelGGL((knn_points_bwd_kernel<2>), dim3(grid_for(total, kBlock, kGridCap)), dim3(kBlock), 0, st, p1, p2, idx, grad_dists, lengths1, lengths2,
                            g_p1, t, P1, P2, D, K, total);
     else
-        hipLaunchKernelGGL((knn_points_bwd_kernel<1>), dim3(grid_for(total)), dim3(kBlock), 0, st, p1, p2, idx, grad_dists, lengths1, lengths2,
+        hipLaunchKernelGGL((knn_points_bwd_kernel<1>), dim3(grid_for(total, kBlock, kGridCap)), dim3(kBlock), 0, st, p1, p2, idx, grad_dists, lengths1, lengths2,
                            g_p1, t, P1, P2, D, K, total);
     return upp_launch_status();
 }
@@ -302,7 +289,7 @@ extern "C" int upp_knn_gather(const float *x, const int64_t *idx, const int64_t 
     if (rc) return rc;
     if (N == 0) return 0;
     const long long total = (long long)N * L * K * U;
-    hipLaunchKernelGGL(knn_gather_kernel, dim3(grid_for(total)), dim3(kBlock), 0, (hipStream_t)stream, x, idx, lengths, out, M, L, K, U, total);
+    hipLaunchKernelGGL(knn_gather_kernel, dim3(grid_for(total, kBlock, kGridCap)), dim3(kBlock), 0, (hipStream_t)stream, x, idx, lengths, out, M, L, K, U, total);
     return upp_launch_status();
 }
 
@@ -313,7 +300,7 @@ extern "C" int upp_knn_scatter_add(const float *src, const int64_t *idx, const i
     if (N == 0) return 0;
     upp_zero_async(out, (long long)N * M * U, (hipStream_t)stream);
     const long long total = (long long)N * L * K * U;
-    hipLaunchKernelGGL(knn_scatter_add_kernel, dim3(grid_for(total)), dim3(kBlock), 0, (hipStream_t)stream, src, idx, rows, slots, out, M, L, K,
+    hipLaunchKernelGGL(knn_scatter_add_kernel, dim3(grid_for(total, kBlock, kGridCap)), dim3(kBlock), 0, (hipStream_t)stream, src, idx, rows, slots, out, M, L, K,
                        U, negate ? 1 : 0, total);
     return upp_launch_status();
 }
@@ -323,8 +310,6 @@ extern "C" int upp_knn_scatter_add_det(const float *src, const int64_t *idx, con
     const int rc = kp_rows_args(src, idx, out, N, M, L, K, U);
     if (rc) return rc;
     if (N == 0) return 0;
-    const long long items = (long long)N * ((U + kDetCh - 1) / kDetCh) * ((M + kDetThreads - 1) / kDetThreads);
-    hipLaunchKernelGGL(knn_scatter_add_det_kernel, dim3(det_grid(items)), dim3(kDetThreads), 0, (hipStream_t)stream, src, idx, rows, slots, out,
-                       N, M, L, K, U, negate ? 1 : 0);
+    det_launch<kDetCh>(KnnScatterJob{src, idx, rows, slots, out, N, M, L, K, U, negate ? 1 : 0}, stream);
     return upp_launch_status();
 }

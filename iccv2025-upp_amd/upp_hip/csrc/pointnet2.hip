@@ -22,13 +22,7 @@ namespace {
 constexpr int kQueries = 128;      // queries per workgroup, one per lane (2 waves)
 constexpr int kTile = 1024;        // searched points per LDS tile (16 KiB as float4)
 constexpr int kBlock = 256;        // the flat kernels
-
-inline int grid_for(long long total) {
-    long long g = (total + kBlock - 1) / kBlock;
-    if (g > 2048) g = 2048;  // 256 CUs x 8 blocks, grid-stride the rest
-    if (g < 1) g = 1;
-    return (int)g;
-}
+constexpr long long kGridCap = 2048;  // 256 CUs x 8 blocks, grid-stride the rest
 
 // points [c0, c0 + len) of a (N,3) cloud -> tile[0 .. len) as (x, y, z, 0); 12 independent loads in flight per thread
 __device__ __forceinline__ void stage_points(float4 *tile, const float *__restrict__ cloud, int c0, int len, int tid) {
@@ -167,52 +161,32 @@ __global__ void three_interpolate_bwd_kernel(const float *__restrict__ grad_out,
 }
 
 // grad_feat[b][ch][r] = +0.0f, then + grad_out[b][ch][i] * weight[b][i][q] for every (i, q) with idx[b][i][q] == r, in ascending
-// i * 3 + q (include/upp_hip.h "deterministic scatter-adds").  As gather_bwd_det_kernel (group.hip): a workgroup owns 256 targets of one
-// cloud and kDetCh channels; the 3 n keys it stages serve all of them, the products are formed once per source while staging.
-constexpr int kDetCh = 4;
-__global__ __launch_bounds__(kDetThreads) void three_interpolate_bwd_det_kernel(const float *__restrict__ grad_out, const int32_t *__restrict__ idx,
-                                                                                const float *__restrict__ weight, float *__restrict__ grad_feat,
-                                                                                int B, int C, int m, int n) {
-    __shared__ __attribute__((aligned(16))) int32_t keys[kDetChunk];
-    __shared__ float vals[kDetChunk * kDetCh];
-    const int tid = threadIdx.x;
-    const long long S = 3LL * n;
-    const long long tiles = (m + kDetThreads - 1) / kDetThreads, groups = (C + kDetCh - 1) / kDetCh, items = (long long)B * groups * tiles;
-    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
-        const long long b = it / (groups * tiles), rest = it - b * groups * tiles;
-        const int ch0 = (int)(rest / tiles) * kDetCh;
-        const long long r = (rest % tiles) * kDetThreads + tid;
-        const int target = r < m ? (int)r : -2;
-        const int32_t *ib = idx + (size_t)b * S;
-        const float *wb = weight + (size_t)b * S;
-        float acc[kDetCh] = {0.0f, 0.0f, 0.0f, 0.0f};
-        for (long long c0 = 0; c0 < S; c0 += kDetChunk) {
-            const int len = (int)min((long long)kDetChunk, S - c0), len4 = (len + 3) & ~3;
-            __syncthreads();
+// i * 3 + q (include/upp_hip.h "deterministic scatter-adds"): a job of det_scan.h's det_scatter_kernel.  As GatherJob (group.hip) a
+// workgroup owns 256 targets of one cloud and kDetCh channels; the products are formed once per source while staging.
+struct InterpolateJob {
+    const float *__restrict__ grad_out;
+    const int32_t *__restrict__ idx;
+    const float *__restrict__ weight;
+    float *__restrict__ grad_feat;
+    int B, C, m, n;
+    __host__ __device__ long long items() const { return B * det_groups(C) * det_tiles(m); }
+    __device__ __forceinline__ DetItem item(long long it) const { return det_item(it, C, m, 3LL * n); }
+    __device__ __forceinline__ void first(const DetItem &, long long, float (&)[kDetCh]) const {}
+    __device__ __forceinline__ void stage(const DetItem &w, long long c0, int i, int32_t &key, float *v) const {
+        const long long s = c0 + i;
+        const int k = idx[(size_t)w.b * w.S + s];
+        const float wt = weight[(size_t)w.b * w.S + s];
+        key = (k >= 0 && k < m) ? k : -1;
 #pragma unroll
-            for (int i = tid; i < kDetChunk; i += kDetThreads) {
-                if (i < len) {
-                    const long long s = c0 + i;
-                    const int k = ib[s];
-                    const float w = wb[s];
-                    keys[i] = (k >= 0 && k < m) ? k : -1;
-#pragma unroll
-                    for (int v = 0; v < kDetCh; ++v)
-                        vals[i * kDetCh + v] = ch0 + v < C ? __fmul_rn(grad_out[((size_t)b * C + ch0 + v) * n + s / 3], w) : 0.0f;
-                } else if (i < len4) {
-                    keys[i] = -1;
-                }
-            }
-            __syncthreads();
-            det_pull<kDetCh>(keys, vals, len4, target, acc);
-        }
-        if (r < m) {
-#pragma unroll
-            for (int v = 0; v < kDetCh; ++v)
-                if (ch0 + v < C) grad_feat[((size_t)b * C + ch0 + v) * m + r] = acc[v];
-        }
+        for (int c = 0; c < kDetCh; ++c)
+            v[c] = w.ch0 + c < C ? __fmul_rn(grad_out[((size_t)w.b * C + w.ch0 + c) * n + s / 3], wt) : 0.0f;
     }
-}
+    __device__ __forceinline__ void store(const DetItem &w, long long r, const float (&acc)[kDetCh]) const {
+#pragma unroll
+        for (int c = 0; c < kDetCh; ++c)
+            if (w.ch0 + c < C) grad_feat[((size_t)w.b * C + w.ch0 + c) * m + r] = acc[c];
+    }
+};
 
 }  // namespace
 
@@ -242,7 +216,7 @@ extern "C" int upp_three_interpolate_fwd(const float *features, const int32_t *i
     if (!features || !idx || !weight || !out || B < 0 || C < 1 || m < 1 || n < 1) return UPP_E_BADARG;
     if (B == 0) return 0;
     const long long total = (long long)B * C * n;
-    hipLaunchKernelGGL(three_interpolate_fwd_kernel, dim3(grid_for(total)), dim3(kBlock), 0, (hipStream_t)stream, features, idx, weight, out, C,
+    hipLaunchKernelGGL(three_interpolate_fwd_kernel, dim3(grid_for(total, kBlock, kGridCap)), dim3(kBlock), 0, (hipStream_t)stream, features, idx, weight, out, C,
                        m, n, total);
     return upp_launch_status();
 }
@@ -252,7 +226,7 @@ extern "C" int upp_three_interpolate_bwd(const float *grad_out, const int32_t *i
     if (!grad_out || !idx || !weight || !grad_features || B < 0 || C < 1 || m < 1 || n < 1) return UPP_E_BADARG;
     if (B == 0) return 0;
     const long long total = (long long)B * C * n;
-    hipLaunchKernelGGL(three_interpolate_bwd_kernel, dim3(grid_for(total)), dim3(kBlock), 0, (hipStream_t)stream, grad_out, idx, weight,
+    hipLaunchKernelGGL(three_interpolate_bwd_kernel, dim3(grid_for(total, kBlock, kGridCap)), dim3(kBlock), 0, (hipStream_t)stream, grad_out, idx, weight,
                        grad_features, C, m, n, total);
     return upp_launch_status();
 }
@@ -261,9 +235,7 @@ extern "C" int upp_three_interpolate_bwd_det(const float *grad_out, const int32_
                                              int C, int m, int n, void *stream) {
     if (!grad_out || !idx || !weight || !grad_features || B < 0 || C < 1 || m < 1 || n < 1) return UPP_E_BADARG;
     if (B == 0) return 0;
-    const long long items = (long long)B * ((C + kDetCh - 1) / kDetCh) * ((m + kDetThreads - 1) / kDetThreads);
-    hipLaunchKernelGGL(three_interpolate_bwd_det_kernel, dim3(det_grid(items)), dim3(kDetThreads), 0, (hipStream_t)stream, grad_out, idx, weight,
-                       grad_features, B, C, m, n);
+    det_launch<kDetCh>(InterpolateJob{grad_out, idx, weight, grad_features, B, C, m, n}, stream);
     return upp_launch_status();
 }
 

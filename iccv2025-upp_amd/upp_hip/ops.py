@@ -221,18 +221,23 @@ def gather_fwd(features, idx):
     return out
 
 
+def _scatter_target(grad_out, shape, name, deterministic):
+    """-> the f32 array a scatter-add backward fills and the entry point that fills it: zeros for the f32 atomics of `name`, an
+    uninitialised array for `name`_det, which writes every element."""
+    if deterministic:
+        return torch.empty(shape, dtype=torch.float32, device=grad_out.device), name + "_det"
+    return torch.zeros(shape, dtype=torch.float32, device=grad_out.device), name
+
+
 def gather_bwd(grad_out, idx, N, deterministic=False):
     """deterministic: the sums in ascending source index (upp_gather_bwd_det, include/upp_hip.h) instead of f32 atomics."""
     _need(grad_out, "grad_out", torch.float32, 3)
     _need(idx, "idx", torch.int32, 2)
     B, C, M = grad_out.shape
-    if deterministic:
-        grad = torch.empty((B, C, N), dtype=torch.float32, device=grad_out.device)       # (overwritten in full)
-        if B and C:
-            _call(grad_out.device, "upp_gather_bwd_det", _abi.ptr(grad_out), _abi.ptr(idx), _abi.ptr(grad), B, C, N, M)
-        return grad
-    grad = torch.zeros((B, C, N), dtype=torch.float32, device=grad_out.device)
-    _call(grad_out.device, "upp_gather_bwd", _abi.ptr(grad_out), _abi.ptr(idx), _abi.ptr(grad), B, C, N, M)
+    grad, name = _scatter_target(grad_out, (B, C, N), "upp_gather_bwd", deterministic)
+    if deterministic and not (B and C):
+        return grad                                      # (nothing to write; the atomic entry point is called, and checks N, even so)
+    _call(grad_out.device, name, _abi.ptr(grad_out), _abi.ptr(idx), _abi.ptr(grad), B, C, N, M)
     return grad
 
 
@@ -366,13 +371,9 @@ def three_interpolate_bwd(grad_out, idx, weight, m, deterministic=False):
     if idx.shape[1] != n:
         raise RuntimeError("three_interpolate_bwd: grad_out must be (B, C, n) for idx (B, n, 3)")
     m = int(m)
-    if deterministic:
-        grad = torch.empty((B, C, m), dtype=torch.float32, device=grad_out.device)       # (overwritten in full)
-    else:
-        grad = torch.zeros((B, C, m), dtype=torch.float32, device=grad_out.device)
+    grad, name = _scatter_target(grad_out, (B, C, m), "upp_three_interpolate_bwd", deterministic)
     if B:
-        _call(grad_out.device, "upp_three_interpolate_bwd_det" if deterministic else "upp_three_interpolate_bwd",
-              _abi.ptr(grad_out), _abi.ptr(idx), _abi.ptr(weight), _abi.ptr(grad), B, C, m, n)
+        _call(grad_out.device, name, _abi.ptr(grad_out), _abi.ptr(idx), _abi.ptr(weight), _abi.ptr(grad), B, C, m, n)
     return grad
 
 
@@ -401,13 +402,9 @@ def grouping_bwd(grad_out, idx, N, deterministic=False):
     if tuple(idx.shape) != (B, P, S):
         raise RuntimeError("grouping_bwd: grad_out must be (B, C, P, S) for idx (B, P, S)")
     N = int(N)
-    if deterministic:
-        grad = torch.empty((B, C, N), dtype=torch.float32, device=grad_out.device)       # (overwritten in full)
-    else:
-        grad = torch.zeros((B, C, N), dtype=torch.float32, device=grad_out.device)
+    grad, name = _scatter_target(grad_out, (B, C, N), "upp_grouping_bwd", deterministic)
     if B:
-        _call(grad_out.device, "upp_grouping_bwd_det" if deterministic else "upp_grouping_bwd",
-              _abi.ptr(grad_out), _abi.ptr(idx), _abi.ptr(grad), B, C, N, P, S)
+        _call(grad_out.device, name, _abi.ptr(grad_out), _abi.ptr(idx), _abi.ptr(grad), B, C, N, P, S)
     return grad
 
 

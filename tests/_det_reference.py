@@ -80,6 +80,24 @@ def fps_gather_bwd(g_centers, idx, N, reverse=False):
     return rows_scatter(g_centers, idx, N, reverse)
 
 
+# ---- inputs at the edges of the kernels' shared body (csrc/det_scan.h): a second chunk of fewer than four sources (S = 1,027 / 1,029),
+# a second tile with one live lane (T = 257), a second channel group with one live channel (5 channels), keys of -1 and of T -----------
+def edge_indices(rng, B, S, T):
+    """(B,S) int64 drawn with repetition from [0, T).  Target T - 1 owns the first, a middle and the LAST source (chunk two, tile two);
+    sources 3 and S - 2 are -1 and sources 7 and S - 3 are T: outside [0, T), skipped by the `_det` kernels -- their atomic siblings do
+    not range-check and must not see these lists."""
+    idx = rng.integers(0, T, (B, S))
+    idx[:, [0, S // 2, S - 1]] = T - 1
+    idx[:, [3, S - 2]] = -1
+    idx[:, [7, S - 3]] = T
+    return idx
+
+
+def mixed_upstream(rng, shape):
+    """signed f32 gradients over seven decades of magnitude: a sum of three or more of them depends on the order in its last bits"""
+    return (rng.standard_normal(shape) * 10.0 ** rng.integers(-3, 4, shape)).astype(F)
+
+
 def ordered_sum(parts, reverse=False):
     """((+0.0f + p_0) + p_1) + ... along the last axis: the EMD cost from its tiles' partial costs."""
     parts = np.asarray(parts, F)

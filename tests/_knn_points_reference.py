@@ -6,6 +6,8 @@ The distance is a chain of fused multiply-adds.  numpy has none, so fma32 forms 
 sum TO ODD before the final rounding to float32 -- with 29 spare bits the double rounding is then the single rounding of a real fma."""
 import numpy as np
 
+from _det_reference import rows_scatter
+
 F = np.float32
 
 
@@ -112,15 +114,9 @@ def scatter_add_det(src, idx, M, rows=None, slots=None, negate=False, reverse=Fa
     src = np.asarray(src, F)
     N, L, K, U = src.shape
     nrows, nslots = clamp_lengths(rows, N, L), clamp_lengths(slots, N, K)
-    out = np.zeros((N, M, U), F)
-    for n in range(N):
-        walk = range(L * K - 1, -1, -1) if reverse else range(L * K)
-        for s in walk:
-            l, k = divmod(s, K)
-            r = int(idx[n, l, k])
-            if l < nrows[n] and k < nslots[n] and 0 <= r < M:
-                out[n, r] = (out[n, r] - src[n, l, k]).astype(F) if negate else (out[n, r] + src[n, l, k]).astype(F)
-    return out
+    live = (np.arange(L)[None, :, None] < nrows[:, None, None]) & (np.arange(K)[None, None, :] < nslots[:, None, None])
+    keys = np.where(live, np.asarray(idx, np.int64), -1)                                 # a slot that takes no part: a key nobody owns
+    return rows_scatter((-src if negate else src).reshape(N, L * K, U), keys.reshape(N, L * K), M, reverse)         # (adding -x IS subtracting x)
 
 
 def scatter_bound(src, idx, M, rows=None, slots=None):

@@ -10,6 +10,8 @@ the tests select in float64 (`sqdist64`) under preconditions checked on these ar
 relevant pair of distances more than 1e-5 apart relatively, an f32 evaluation (error < 1e-6 relative) selects the same indices."""
 import numpy as np
 
+from _det_reference import rows_scatter
+
 F = np.float32
 
 
@@ -131,38 +133,22 @@ def grouping(features, idx):
     return out
 
 
-def _order(n, reverse):
-    return range(n - 1, -1, -1) if reverse else range(n)
-
-
 def three_interpolate_bwd_det(grad_out, idx, weight, m, reverse=False):
     """grad_features[b][c][r] = +0.0f, then + (grad_out[b][c][i] * weight[b][i][j]) for every (i, j) with idx[b][i][j] == r, in ascending
     i * 3 + j: the product rounded, then the sum.  Indices outside [0, m) are skipped."""
     grad_out, weight = np.asarray(grad_out, F), np.asarray(weight, F)
     B, C, n = grad_out.shape
-    out = np.zeros((B, C, m), F)
-    for b in range(B):
-        for s in _order(3 * n, reverse):
-            i, j = divmod(s, 3)
-            r = int(idx[b, i, j])
-            if 0 <= r < m:
-                term = (grad_out[b, :, i] * weight[b, i, j]).astype(F)
-                out[b, :, r] = (out[b, :, r] + term).astype(F)
-    return out
+    terms = (grad_out.transpose(0, 2, 1)[:, :, None, :] * weight[:, :, :, None]).astype(F)          # (B,n,3,C): one rounded product each
+    out = rows_scatter(terms.reshape(B, 3 * n, C), np.asarray(idx).reshape(B, 3 * n), m, reverse)
+    return np.ascontiguousarray(out.transpose(0, 2, 1))
 
 
 def grouping_bwd_det(grad_out, idx, N, reverse=False):
     """grad_features[b][c][r] = +0.0f, then + grad_out[b][c][p][s] for every (p, s) with idx[b][p][s] == r, in ascending p * S + s."""
     grad_out = np.asarray(grad_out, F)
     B, C, P, S = grad_out.shape
-    go, ix = grad_out.reshape(B, C, P * S), np.asarray(idx).reshape(B, P * S)
-    out = np.zeros((B, C, N), F)
-    for b in range(B):
-        for s in _order(P * S, reverse):
-            r = int(ix[b, s])
-            if 0 <= r < N:
-                out[b, :, r] = (out[b, :, r] + go[b, :, s]).astype(F)
-    return out
+    out = rows_scatter(grad_out.reshape(B, C, P * S).transpose(0, 2, 1), np.asarray(idx).reshape(B, P * S), N, reverse)
+    return np.ascontiguousarray(out.transpose(0, 2, 1))
 
 
 # ---- the cases of the host and GPU tests: the smallest shapes that reach every branch (one and several tiles of 128 queries, clouds

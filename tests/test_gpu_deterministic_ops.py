@@ -123,6 +123,42 @@ def test_fps_gather_bwd_det_has_the_restated_bits():
     same(ops.fps_gather_bwd(dev(g), dev(idx), N, deterministic=True), R.fps_gather_bwd(g, idx, N), "g_xyz")
 
 
+def test_gather_bwd_det_at_the_edges_of_the_shared_body():
+    """5 channels (a second channel group with one live channel), 257 targets (a second tile with one live lane), 1,027 sources (a second
+    chunk of three), keys of -1 and of N.  deterministic=True only: the atomic sibling does not range-check."""
+    B, C, N, M = 2, 5, 257, 1027
+    rng = np.random.default_rng(C + N + M)
+    idx = R.edge_indices(rng, B, M, N).astype(np.int32)
+    go = R.mixed_upstream(rng, (B, C, M))
+    want = R.gather_bwd(go, idx, N)
+    assert not np.array_equal(bits(want), bits(R.gather_bwd(go, idx, N, reverse=True)))           # the order is visible
+    same(ops.gather_bwd(dev(go), dev(idx), N, deterministic=True), want, "grad_feat")
+
+
+def test_fps_gather_bwd_det_at_the_edges_of_the_shared_body():
+    """the (.., 3)-row kernel with int32 indices: two tiles, two chunks, keys of -1 and of N"""
+    B, N, M = 2, 257, 1027
+    rng = np.random.default_rng(N + M)
+    idx = R.edge_indices(rng, B, M, N).astype(np.int32)
+    g = R.mixed_upstream(rng, (B, M, 3))
+    want = R.fps_gather_bwd(g, idx, N)
+    assert not np.array_equal(bits(want), bits(R.fps_gather_bwd(g, idx, N, reverse=True)))
+    same(ops.fps_gather_bwd(dev(g), dev(idx), N, deterministic=True), want, "g_xyz")
+
+
+def test_fps_gather_bwd_det_beyond_the_grid_of_16384_workgroups():
+    """16,390 clouds of two points are 16,390 (cloud, tile) items: the last six are reached by the grid-stride loop alone.  With two
+    sources per cloud no order can show (two addends commute exactly), so this case is not asked to: it checks that every item is
+    served (the output is torch.empty: an unserved item keeps whatever was there)."""
+    B, N, M = 16390, 2, 2
+    rng = np.random.default_rng(B)
+    idx = rng.integers(0, N, (B, M)).astype(np.int32)
+    g = R.mixed_upstream(rng, (B, M, 3))
+    want = R.fps_gather_bwd(g, idx, N)
+    assert want[16384:].any()
+    same(ops.fps_gather_bwd(dev(g), dev(idx), N, deterministic=True), want, "g_xyz")
+
+
 @pytest.mark.parametrize("case", [(2, 200, 130), (2, 1024, 1024), (2, 50, 70)], ids=lambda c: "%dx%dx%d" % c)
 def test_emd_matchcost_det_sums_the_tiles_in_order(case):
     B, n, m = case

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import _det_reference as D
 import _knn_points_reference as R
 from upp_hip import ops
 import upp_hip.functional as HF
@@ -206,6 +207,22 @@ def test_knn_gather_and_its_gradient(lengths):
             np.testing.assert_array_equal(bits(gx), bits(R.scatter_add_det(go, idx, M, None, lengths)))
             res.setdefault("det", []).append(gx)
     assert np.array_equal(bits(res["det"][0]), bits(res["det"][1]))
+
+
+@pytest.mark.parametrize("negate", [False, True])
+def test_scatter_add_det_at_the_edges_of_the_shared_body(negate):
+    """5 columns (a second column group with one live column), 257 target rows (a second tile with one live lane), 1,027 sources (a second
+    chunk of three), keys of -1 and of M, one cloud with every slot and one with rows and slots cut short.  deterministic=True only: the
+    atomic sibling's index check is not under test here."""
+    N, L, K, U, M = 2, 79, 13, 5, 257
+    g = np.random.default_rng(L * K)
+    src = D.mixed_upstream(g, (N, L, K, U))
+    idx = D.edge_indices(g, N, L * K, M).reshape(N, L, K)
+    rows, slots = (79, 40), (13, 5)
+    want = R.scatter_add_det(src, idx, M, rows, slots, negate=negate)
+    assert not np.array_equal(bits(want), bits(R.scatter_add_det(src, idx, M, rows, slots, negate=negate, reverse=True)))   # the order is visible
+    got = ops.knn_scatter_add(dev(src), dev(idx), M, dev(np.array(rows, np.int64)), dev(np.array(slots, np.int64)), negate=negate, deterministic=True)
+    np.testing.assert_array_equal(bits(got.cpu().numpy()), bits(want))
 
 
 def test_forward_and_backward_in_one_captured_graph_replay_the_eager_bits():

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import _det_reference as D
 import _pointnet2_reference as R
 import _seeded
 from upp_hip import ops, functional as HF
@@ -204,6 +205,30 @@ def test_det_backward_with_one_loaded_target_and_untouched_targets(C):
     np.testing.assert_array_equal(bits(runs[0]), bits(runs[1]))
     rest = np.delete(runs[0], 3, axis=2)
     assert not rest.any() and not np.signbit(rest).any()
+
+
+def test_three_interpolate_det_backward_at_the_edges_of_the_shared_body():
+    """5 channels (a second channel group with one live channel), 257 targets (a second tile with one live lane), a second chunk of fewer
+    than four sources, keys of -1 and of the target count.  deterministic=True only: the atomic siblings do not range-check."""
+    g = np.random.default_rng(343)
+    B, C, n, m = 2, 5, 343, 257                                      # 1,029 sources: the row of source 1,024 straddles the chunk boundary
+    go, w = D.mixed_upstream(g, (B, C, n)), g.random((B, n, 3), dtype=np.float32)
+    idx = D.edge_indices(g, B, 3 * n, m).reshape(B, n, 3).astype(np.int32)
+    want = R.three_interpolate_bwd_det(go, idx, w, m)
+    assert not np.array_equal(bits(want), bits(R.three_interpolate_bwd_det(go, idx, w, m, reverse=True)))       # the order is visible
+    got = ops.three_interpolate_bwd(dev(go), dev(idx), dev(w), m, deterministic=True).cpu().numpy()
+    np.testing.assert_array_equal(bits(got), bits(want))
+
+
+def test_grouping_det_backward_at_the_edges_of_the_shared_body():
+    g = np.random.default_rng(1027)
+    B, C, N, P, S = 2, 5, 257, 13, 79                                # 1,027 sources: a second chunk of three
+    go4 = D.mixed_upstream(g, (B, C, P, S))
+    ix = D.edge_indices(g, B, P * S, N).reshape(B, P, S).astype(np.int32)
+    want = R.grouping_bwd_det(go4, ix, N)
+    assert not np.array_equal(bits(want), bits(R.grouping_bwd_det(go4, ix, N, reverse=True)))
+    got = ops.grouping_bwd(dev(go4), dev(ix), N, deterministic=True).cpu().numpy()
+    np.testing.assert_array_equal(bits(got), bits(want))
 
 
 @pytest.mark.parametrize("use_xyz,with_features", [(True, True), (False, True), (True, False)])

@@ -1,7 +1,7 @@
 """What the reproducible mode costs: every atomic scatter-add entry point against its `_det` sibling at the recipes' shapes, then the
 pre-task and stage-2 steps with the mode off and on.  RECORDED, not gated (the mode is opt-in).
 
-    python tools/determinism_cost.py [--out profiles/deterministic_cost.json] [--steps 30] [--only chamfer,group,gather,emd,steps]
+    python tools/determinism_cost.py [--out profiles/deterministic_cost.json] [--steps 30] [--only chamfer,group,gather,emd,three_interpolate,grouping,knn_scatter,steps]
 
 Every measurement is a child process of its own under `timeout -k 10` (a faulting or hanging child ends the run: nothing more is started
 on the device after it).  Kernel pairs: bench.time_kernel (the calls captured into a graph, the replay timed with device events), the two
@@ -21,6 +21,13 @@ PAIRS = {
     "group": [(32, 1096, 32, 16), (32, 1024, 64, 32), (32, 2048, 128, 32)],   # (B, N, G, K)
     "gather": [(32, 3, 8192, 1024)],                                          # (B, C, N, M)
     "emd": [(32, 1024, 1024)],                                                # (B, n, m)
+    # the deformable attention's interpolation, the call the operator serves (csrc/pointnet2.hip's header; no model of this repository
+    # calls it yet: 32 clouds x 2 groups, 192 channels a group, 256 tokens x 10 shifted positions), the DGCNN grouper's neighbourhood gather (tools/edge_conv_throughput.py: 512 queries x 16
+    # neighbours among 2,048 points, 32 channels), knn_points' g_p2 at the pre-task shape (tools/knn_points_throughput.py) and the edge
+    # convolution's g_A at the grouper's widest layer (64 channels)
+    "three_interpolate": [(64, 192, 256, 2560)],                              # (B, C, m, n)
+    "grouping": [(32, 32, 2048, 512, 16)],                                    # (B, C, N, P, S)
+    "knn_scatter": [(64, 72, 4, 3, 1024), (32, 512, 16, 64, 2048)],           # (N, L, K, U, M)
 }
 
 
@@ -51,6 +58,25 @@ def child(kind, shape):
         idx = ops.fps(rand(B, N, 3), M)
         go = rand(B, C, M)
         fn = lambda det: ops.gather_bwd(go, idx, N, deterministic=det)
+    elif kind == "three_interpolate":
+        B, C, m, n = shape
+        dist, idx = ops.three_nn(rand(B, n, 3), rand(B, m, 3))
+        w = 1.0 / (dist + 1e-8)
+        w = (w / w.sum(2, keepdim=True)).contiguous()
+        go = rand(B, C, n)
+        fn = lambda det: ops.three_interpolate_bwd(go, idx, w, m, deterministic=det)
+    elif kind == "grouping":
+        B, C, N, P, S = shape
+        x = rand(B, N, 3)
+        idx = ops.knn(x, x[:, :P].contiguous(), S, want_dist=False)[1].int()
+        go = rand(B, C, P, S)
+        fn = lambda det: ops.grouping_bwd(go, idx, N, deterministic=det)
+    elif kind == "knn_scatter":
+        N, L, K, U, M = shape
+        x = rand(N, M, 3)
+        idx = ops.knn_points(x[:, :L].contiguous(), x, K=K)[1]
+        src = rand(N, L, K, U)
+        fn = lambda det: ops.knn_scatter_add(src, idx, M, deterministic=det)
     else:
         B, n, m = shape
         a, b = rand(B, n, 3), rand(B, m, 3)
@@ -78,7 +104,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "deterministic_cost.json"))
     ap.add_argument("--steps", type=int, default=30)
-    ap.add_argument("--only", default="chamfer,group,gather,emd,steps")
+    ap.add_argument("--only", default="chamfer,group,gather,emd,three_interpolate,grouping,knn_scatter,steps")
     ap.add_argument("--child", nargs=2)
     args = ap.parse_args()
     if args.child:
