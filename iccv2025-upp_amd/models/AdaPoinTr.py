@@ -3,13 +3,15 @@ Class names and state-dict keys are the reference's, so its checkpoints load wit
 
 A block style is one or two tokens joined by '-'.  Served tokens: `attn` (global attention) and `graph` (DynamicGraphAttention), alone or
 paired, combined by `concat` (both on one normalised input, merged by a Linear over the concatenation) or `onebyone` (one residual
-branch each).  The tokens `rw_deform`, `deform` and `deform_graph` (the deformable local attentions) are not ported and raise ValueError
-at construction.
+branch each).  The token `deform` (Transformer_utils.DeformableLocalCrossAttention) is served behind the keyword deformable=True of the
+block APIs, the stacks and the two Point* classes -- `deformable: true` in a model config, which PCTransformer and the *Entry classes
+read; with the default False it raises ValueError at construction like `rw_deform` and `deform_graph`, which are not ported.
     LayerNorm                      HF.layer_norm (the row kernel; eps from the module, 1e-6 in the stacks)
     self-attention                 Transformer_utils.Attention; with denoise_length the fused prefix-visibility kernel -- CrossAttnBlockApi
                                    passes denoise_length on and never builds the reference's (N, N) mask tensor
     cross-attention                upp_layers.CrossAttention (HF.cross_attention)
     graph branches                 Transformer_utils.DynamicGraphAttention (HF.edge_conv_max)
+    deformable branches            Transformer_utils.DeformableLocalCrossAttention (HF.deform_offset, HF.three_nn, HF.deform_attention)
     merge maps                     HF.linear;  MLPs: upp_layers.Mlp (HF.mlp_gelu)
 TransformerEncoder / TransformerDecoder compute every neighbour list once per forward -- the denoise list included, which the reference
 recomputes inside every block; positions do not change between blocks, so the lists are the same -- and only the lists some block uses.
@@ -49,24 +51,35 @@ from .PoinTr import Fold  # noqa: F401  (the reference's models/AdaPoinTr.py:693
 from .Transformer import conv_bn_act_conv
 from .build import build_model_from_cfg
 from .dgcnn_group import DGCNN_Grouper
-from .Transformer_utils import Attention, CrossAttention, DropPath, DynamicGraphAttention, LayerScale, Mlp, denoise_knn, knn_point
+from .Transformer_utils import (Attention, CrossAttention, DeformableLocalCrossAttention, DropPath, DynamicGraphAttention, LayerScale, Mlp,
+                                denoise_knn, knn_point)
 
 SERVED_TOKENS = ('attn', 'graph')
 UNPORTED_TOKENS = ('rw_deform', 'deform', 'deform_graph')
 
 
-def _tokens(style, what):
-    """'attn-graph' -> ['attn', 'graph']: one token, or one global and one local one"""
+def _tokens(style, what, deformable=False):
+    """'attn-graph' -> ['attn', 'graph']: one token, or one global and one local one (`graph`, or `deform` where deformable)"""
     tokens = style.split('-')
     for t in tokens:
+        if t == 'deform' and deformable:
+            continue
         if t in UNPORTED_TOKENS:
-            raise ValueError("%s %r: the block token %r (a deformable local attention) is not ported; served tokens: %s"
-                             % (what, style, t, ', '.join(SERVED_TOKENS)))
+            raise ValueError("%s %r: the block token %r (a deformable local attention) is not ported; served tokens: %s%s"
+                             % (what, style, t, ', '.join(SERVED_TOKENS), " (and `deform` with deformable=True)" if t == 'deform' else ""))
         if t not in SERVED_TOKENS:
             raise ValueError("%s %r: unexpected block token %r" % (what, style, t))
-    if len(tokens) > 2 or (len(tokens) == 2 and tokens[0] == tokens[1]):
-        raise ValueError("%s %r: one token, or one `attn` and one `graph`" % (what, style))
+    if len(tokens) > 2 or (len(tokens) == 2 and (tokens[0] == tokens[1] or 'attn' not in tokens)):
+        raise ValueError("%s %r: one token, or one `attn` and one local token" % (what, style))
     return tokens
+
+
+def _local(token, dim, num_heads, qkv_bias, attn_drop, drop, k, n_group):
+    """the local branch of a token: `graph`, or `deform` (reference models/AdaPoinTr.py:57,170,203)"""
+    if token == 'deform':
+        return DeformableLocalCrossAttention(dim, num_heads=num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop, k=k,
+                                             n_group=n_group)
+    return DynamicGraphAttention(dim, k=k)
 
 
 def _combine_style(style, what):
@@ -91,7 +104,8 @@ class SelfAttnBlockApi(nn.Module):
     """reference models/AdaPoinTr.py:15-108.  forward(x (B,N,dim), pos (B,N,3), idx=None (B,N,k) rows of x)."""
 
     def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, drop=0., attn_drop=0., init_values=None, drop_path=0.,
-                 act_layer=nn.GELU, norm_layer=nn.LayerNorm, block_style='attn-deform', combine_style='concat', k=10, n_group=2):
+                 act_layer=nn.GELU, norm_layer=nn.LayerNorm, block_style='attn-deform', combine_style='concat', k=10, n_group=2,
+                 deformable=False):
         super().__init__()
         self.combine_style = _combine_style(combine_style, 'SelfAttnBlockApi')
         self.norm1 = norm_layer(dim)
@@ -100,7 +114,7 @@ class SelfAttnBlockApi(nn.Module):
         self.ls2 = LayerScale(dim, init_values=init_values) if init_values else nn.Identity()
         self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
         self.drop_path2 = DropPath(drop_path) if drop_path > 0. else nn.Identity()
-        tokens = _tokens(block_style, 'block_style')
+        tokens = _tokens(block_style, 'block_style', deformable)
         self.block_length = len(tokens)
         self.attn = None
         self.local_attn = None
@@ -108,7 +122,7 @@ class SelfAttnBlockApi(nn.Module):
             if token == 'attn':
                 self.attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop)
             else:
-                self.local_attn = DynamicGraphAttention(dim, k=k)
+                self.local_attn = _local(token, dim, num_heads, qkv_bias, attn_drop, drop, k, n_group)
         if self.block_length == 2:
             if combine_style == 'concat':
                 self.merge_map = nn.Linear(dim * 2, dim)
@@ -139,7 +153,7 @@ class CrossAttnBlockApi(nn.Module):
 
     def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, drop=0., attn_drop=0., init_values=None, drop_path=0.,
                  act_layer=nn.GELU, norm_layer=nn.LayerNorm, self_attn_block_style='attn-deform', self_attn_combine_style='concat',
-                 cross_attn_block_style='attn-deform', cross_attn_combine_style='concat', k=10, n_group=2):
+                 cross_attn_block_style='attn-deform', cross_attn_combine_style='concat', k=10, n_group=2, deformable=False):
         super().__init__()
         self.norm2 = norm_layer(dim)
         self.ls2 = LayerScale(dim, init_values=init_values) if init_values else nn.Identity()
@@ -149,7 +163,7 @@ class CrossAttnBlockApi(nn.Module):
         self.norm1 = norm_layer(dim)
         self.ls1, self.drop_path1 = _scale_and_path(dim, init_values, drop_path)
         self.self_attn_combine_style = _combine_style(self_attn_combine_style, 'CrossAttnBlockApi self-attention')
-        tokens = _tokens(self_attn_block_style, 'self_attn_block_style')
+        tokens = _tokens(self_attn_block_style, 'self_attn_block_style', deformable)
         self.self_attn_block_length = len(tokens)
         self.self_attn = None
         self.local_self_attn = None
@@ -157,7 +171,7 @@ class CrossAttnBlockApi(nn.Module):
             if token == 'attn':
                 self.self_attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop)
             else:
-                self.local_self_attn = DynamicGraphAttention(dim, k=k)
+                self.local_self_attn = _local(token, dim, num_heads, qkv_bias, attn_drop, drop, k, n_group)
         if self.self_attn_block_length == 2:
             if self_attn_combine_style == 'concat':
                 self.self_attn_merge_map = nn.Linear(dim * 2, dim)
@@ -169,7 +183,7 @@ class CrossAttnBlockApi(nn.Module):
         self.norm_v = norm_layer(dim)
         self.ls4, self.drop_path4 = _scale_and_path(dim, init_values, drop_path)
         self.cross_attn_combine_style = _combine_style(cross_attn_combine_style, 'CrossAttnBlockApi cross-attention')
-        tokens = _tokens(cross_attn_block_style, 'cross_attn_block_style')
+        tokens = _tokens(cross_attn_block_style, 'cross_attn_block_style', deformable)
         self.cross_attn_block_length = len(tokens)
         self.cross_attn = None
         self.local_cross_attn = None
@@ -177,7 +191,7 @@ class CrossAttnBlockApi(nn.Module):
             if token == 'attn':
                 self.cross_attn = CrossAttention(dim, dim, num_heads=num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop)
             else:
-                self.local_cross_attn = DynamicGraphAttention(dim, k=k)
+                self.local_cross_attn = _local(token, dim, num_heads, qkv_bias, attn_drop, drop, k, n_group)
         if self.cross_attn_block_length == 2:
             if cross_attn_combine_style == 'concat':
                 self.cross_attn_merge_map = nn.Linear(dim * 2, dim)
@@ -227,13 +241,13 @@ class TransformerEncoder(nn.Module):
 
     def __init__(self, embed_dim=256, depth=4, num_heads=4, mlp_ratio=4., qkv_bias=False, init_values=None, drop_rate=0.,
                  attn_drop_rate=0., drop_path_rate=0., act_layer=nn.GELU, norm_layer=nn.LayerNorm, block_style_list=['attn-deform'],
-                 combine_style='concat', k=10, n_group=2):
+                 combine_style='concat', k=10, n_group=2, deformable=False):
         super().__init__()
         self.k = k
         self.blocks = nn.ModuleList([SelfAttnBlockApi(
             dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, init_values=init_values, drop=drop_rate,
             attn_drop=attn_drop_rate, drop_path=_path_rate(drop_path_rate, i), act_layer=act_layer, norm_layer=norm_layer,
-            block_style=block_style_list[i], combine_style=combine_style, k=k, n_group=n_group) for i in range(depth)])
+            block_style=block_style_list[i], combine_style=combine_style, k=k, n_group=n_group, deformable=deformable) for i in range(depth)])
 
     def lists(self, pos):
         """-> idx (B,N,k) | None when no block has a graph branch"""
@@ -252,7 +266,7 @@ class TransformerDecoder(nn.Module):
     def __init__(self, embed_dim=256, depth=4, num_heads=4, mlp_ratio=4., qkv_bias=False, init_values=None, drop_rate=0.,
                  attn_drop_rate=0., drop_path_rate=0., act_layer=nn.GELU, norm_layer=nn.LayerNorm,
                  self_attn_block_style_list=['attn-deform'], self_attn_combine_style='concat',
-                 cross_attn_block_style_list=['attn-deform'], cross_attn_combine_style='concat', k=10, n_group=2):
+                 cross_attn_block_style_list=['attn-deform'], cross_attn_combine_style='concat', k=10, n_group=2, deformable=False):
         super().__init__()
         self.k = k
         self.blocks = nn.ModuleList([CrossAttnBlockApi(
@@ -260,7 +274,7 @@ class TransformerDecoder(nn.Module):
             attn_drop=attn_drop_rate, drop_path=_path_rate(drop_path_rate, i), act_layer=act_layer, norm_layer=norm_layer,
             self_attn_block_style=self_attn_block_style_list[i], self_attn_combine_style=self_attn_combine_style,
             cross_attn_block_style=cross_attn_block_style_list[i], cross_attn_combine_style=cross_attn_combine_style,
-            k=k, n_group=n_group) for i in range(depth)])
+            k=k, n_group=n_group, deformable=deformable) for i in range(depth)])
 
     def lists(self, q_pos, v_pos, denoise_length=None):
         """-> (self_attn_idx (B,N,k) rows of q, cross_attn_idx (B,N,k) rows of v), each None when no block uses it.  With denoise_length
@@ -295,7 +309,7 @@ class PointTransformerEncoder(nn.Module):
 
     def __init__(self, embed_dim=256, depth=12, num_heads=4, mlp_ratio=4., qkv_bias=True, init_values=None, drop_rate=0.,
                  attn_drop_rate=0., drop_path_rate=0., norm_layer=None, act_layer=None, block_style_list=['attn-deform'],
-                 combine_style='concat', k=10, n_group=2):
+                 combine_style='concat', k=10, n_group=2, deformable=False):
         super().__init__()
         norm_layer = norm_layer or partial(nn.LayerNorm, eps=1e-6)
         act_layer = act_layer or nn.GELU
@@ -307,7 +321,7 @@ class PointTransformerEncoder(nn.Module):
         self.blocks = TransformerEncoder(
             embed_dim=embed_dim, num_heads=num_heads, depth=depth, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, init_values=init_values,
             drop_rate=drop_rate, attn_drop_rate=attn_drop_rate, drop_path_rate=dpr, norm_layer=norm_layer, act_layer=act_layer,
-            block_style_list=block_style_list, combine_style=combine_style, k=k, n_group=n_group)
+            block_style_list=block_style_list, combine_style=combine_style, k=k, n_group=n_group, deformable=deformable)
         self.norm = norm_layer(embed_dim)
         self.apply(_init_weights)
 
@@ -321,7 +335,7 @@ class PointTransformerDecoder(nn.Module):
     def __init__(self, embed_dim=256, depth=12, num_heads=4, mlp_ratio=4., qkv_bias=True, init_values=None, drop_rate=0.,
                  attn_drop_rate=0., drop_path_rate=0., norm_layer=None, act_layer=None, self_attn_block_style_list=['attn-deform'],
                  self_attn_combine_style='concat', cross_attn_block_style_list=['attn-deform'], cross_attn_combine_style='concat',
-                 k=10, n_group=2):
+                 k=10, n_group=2, deformable=False):
         super().__init__()
         norm_layer = norm_layer or partial(nn.LayerNorm, eps=1e-6)
         act_layer = act_layer or nn.GELU
@@ -336,21 +350,28 @@ class PointTransformerDecoder(nn.Module):
             drop_rate=drop_rate, attn_drop_rate=attn_drop_rate, drop_path_rate=dpr, norm_layer=norm_layer, act_layer=act_layer,
             self_attn_block_style_list=self_attn_block_style_list, self_attn_combine_style=self_attn_combine_style,
             cross_attn_block_style_list=cross_attn_block_style_list, cross_attn_combine_style=cross_attn_combine_style,
-            k=k, n_group=n_group)
+            k=k, n_group=n_group, deformable=deformable)
         self.apply(_init_weights)
 
     def forward(self, q, v, q_pos, v_pos, denoise_length=None):
         return self.blocks(q, v, q_pos, v_pos, denoise_length=denoise_length)
 
 
+def _entry_kwargs(config, deformable):
+    """a stack's config section as keywords; `deformable` from the section itself or, failing that, from the model section"""
+    kw = dict(config)
+    kw['deformable'] = bool(config.get('deformable', False) or deformable)
+    return kw
+
+
 class PointTransformerEncoderEntry(PointTransformerEncoder):
-    def __init__(self, config, **kwargs):
-        super().__init__(**dict(config))
+    def __init__(self, config, deformable=False, **kwargs):
+        super().__init__(**_entry_kwargs(config, deformable))
 
 
 class PointTransformerDecoderEntry(PointTransformerDecoder):
-    def __init__(self, config, **kwargs):
-        super().__init__(**dict(config))
+    def __init__(self, config, deformable=False, **kwargs):
+        super().__init__(**_entry_kwargs(config, deformable))
 
 
 # ---------------------------------------------------------------------------------------------- PCTransformer and AdaPoinTr
@@ -431,7 +452,8 @@ class PCTransformer(nn.Module):
         self.grouper = DGCNN_Grouper(k=16)
         self.pos_embed = nn.Sequential(nn.Linear(in_chans, 128), nn.GELU(), nn.Linear(128, encoder_config.embed_dim))
         self.input_proj = nn.Sequential(nn.Linear(self.grouper.num_features, 512), nn.GELU(), nn.Linear(512, encoder_config.embed_dim))
-        self.encoder = PointTransformerEncoderEntry(encoder_config)
+        deformable = bool(config.get('deformable', False))          # opt-in: the block token `deform`
+        self.encoder = PointTransformerEncoderEntry(encoder_config, deformable=deformable)
         self.increase_dim = nn.Sequential(nn.Linear(encoder_config.embed_dim, 1024), nn.GELU(), nn.Linear(1024, global_feature_dim))
         self.coarse_pred = nn.Sequential(nn.Linear(global_feature_dim, 1024), nn.GELU(), nn.Linear(1024, 3 * query_num))
         self.mlp_query = nn.Sequential(nn.Linear(global_feature_dim + 3, 1024), nn.GELU(), nn.Linear(1024, 1024), nn.GELU(),
@@ -440,7 +462,7 @@ class PCTransformer(nn.Module):
             self.mem_link = nn.Identity()
         else:
             self.mem_link = nn.Linear(encoder_config.embed_dim, decoder_config.embed_dim)
-        self.decoder = PointTransformerDecoderEntry(decoder_config)
+        self.decoder = PointTransformerDecoderEntry(decoder_config, deformable=deformable)
         self.query_ranking = nn.Sequential(nn.Linear(3, 256), nn.GELU(), nn.Linear(256, 256), nn.GELU(), nn.Linear(256, 1), nn.Sigmoid())
         self.apply(_init_weights)
 

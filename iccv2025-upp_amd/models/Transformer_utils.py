@@ -11,6 +11,10 @@ reference's, so its checkpoints load with strict=True.
     DynamicGraphAttention                   max_k lrelu(Linear([f_j - f_i ; f_i])) over k listed neighbours: DecoderBlock.local_branch, i.e.
                                             two per-point products and HF.edge_conv_max without a norm (no (B, N, k, 2 dim) tensor)
     knn_point                               HF.knn_query
+    DeformableLocalCrossAttention           the deformable local attention (block token `deform`): the offset head and the key / value
+                                            projections taken through the gather as per-point products, HF.deform_offset, HF.three_nn and
+                                            HF.deform_attention -- no (B, N, k, C) tensor (README "Deformable local cross-attention")
+    DeformableAttnBlock, DeformableAttnDecoderBlock   the reference's fixed layouts around it
 The fused attention path is taken for HIP f32 tensors with head_dim 64, N <= HF.ATTN_MAX_L and no active attention dropout; otherwise
 the same module runs the torch formulation, and a HIP tensor that was declined is recorded by HF.note_declined.
 
@@ -18,14 +22,14 @@ Deliberate deviation (README "Denoising-query attention and the AdaPoinTr blocks
 topk(sorted=False) of |a|^2 + |b|^2 - 2ab; here the set is the library's ascending (distance, index) on the direct squared distance.  The
 sets agree wherever the k-th and (k+1)-th distances differ by more than rounding, and the order inside a set does not matter under the max.
 
-Not ported: DeformableLocalAttention, DeformableLocalCrossAttention, improvedDeformableLocalCrossAttention,
-improvedDeformableLocalGraphAttention (the block tokens rw_deform, deform, deform_graph) and the fixed-layout Block / DecoderBlock
-variants of the reference file, which models/AdaPoinTr.py does not use."""
+Not ported: DeformableLocalAttention, improvedDeformableLocalCrossAttention, improvedDeformableLocalGraphAttention (the block tokens
+rw_deform and deform_graph, and the `improved` variant of deform) and the other fixed-layout Block / DecoderBlock variants of the
+reference file, which models/AdaPoinTr.py does not use."""
 import torch
 import torch.nn as nn
 
 from upp_hip import functional as HF
-from upp_hip import torch_cpu
+from upp_hip import ops, torch_cpu
 from . import upp_layers as L
 from .upp_layers import CrossAttention, DecoderBlock, DropPath, Mlp, index_points, square_distance  # noqa: F401  (the reference's names)
 
@@ -125,3 +129,194 @@ class DynamicGraphAttention(nn.Module):
         if idx.shape != (q.shape[0], q.shape[1], self.k):
             raise ValueError("idx must be (B, N, k) = %s, got %s" % ((q.shape[0], q.shape[1], self.k), tuple(idx.shape)))
         return DecoderBlock.local_branch(self.knn_map, v, q, idx)
+
+
+def shifted_three_nn(shift, known):
+    """shift (R,n,3) the shifted neighbour positions, known (R,m,3) -> (dist (R,n,3) Euclidean ascending, idx3 (R,n,3) int32): HF.three_nn
+    for HIP f32 tensors, its torch formulation elsewhere (any device and dtype); no gradient."""
+    with torch.no_grad():
+        if shift.is_cuda and shift.dtype == torch.float32:
+            return HF.three_nn(shift.contiguous(), known.contiguous())
+        return torch_cpu.three_nn(shift, known)
+
+
+class DeformableLocalCrossAttention(nn.Module):
+    """reference models/Transformer_utils.py:269-491: every query attends over k neighbour slots whose keys and values are
+    interpolated at learned, shifted positions.  forward(q (B,N,dim), q_pos (B,N,3), v=None (B,NK,dim), v_pos=None (B,NK,3), idx=None
+    (B,N,k) rows of v, denoise_length=None) -> (B,N,dim); v / v_pos default to q / q_pos (the self form).  With denoise_length = D (self
+    form only; v, v_pos and idx must be None, as in the reference) the list is denoise_knn's.
+    State-dict keys: proj_q, proj_k, proj_v, proj_v_off, proj, linear_offset.{0,1,3}.
+
+    Per group g of dim / n_group channels (c = dim / n_group, W0 = linear_offset.0.weight = [Wa | Wb]):
+        offset head     Linear([v_off_g[idx] ; q_g]) = A_g[idx] + Bq_g with A_g = v_off_g Wa^T over the NK points, Bq_g = q_g Wb^T + b over
+                        the N queries; HF.deform_offset does gather, LayerNorm, GELU, the 3-row Linear, tanh and the shift
+        three_nn        HF.three_nn of the shifted positions among v_pos; weights by the reference's own r = 1 / (dist + 1e-8),
+                        r / r.sum(-1) in torch, so that they carry its rounding
+        keys, values    proj_k(interp)[n,s] = b_k + sum_g sum_j w[g,n,s,j] PK_g[idx3[g,n,s,j]] with PK_g = v_g Wk[:, g-slice]^T over the
+                        NK points, likewise proj_v; HF.deform_attention gathers, scores, normalises and sums
+    three_nn is not differentiable (as upstream marks dist and idx), so the offset branch -- proj_v_off, linear_offset -- and the
+    positions get no gradient: it runs under no_grad.  The fused path is taken for HIP f32 tensors in the served range (head_dim 64, at
+    most 16 heads, k <= 32) with no active attention dropout and upp_layers.POOL_TRACE unset; otherwise the torch formulation
+    (upp_hip.torch_cpu.deform_offset / deform_attention, which keep the (B,N,k,C) tensors) runs and a HIP tensor that was declined is
+    recorded by HF.note_declined.  The neighbour set is the library's ascending (distance, index), as for the other modules."""
+
+    def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_drop=0., proj_drop=0., k=10, n_group=2):
+        super().__init__()
+        if dim % num_heads or dim % n_group or num_heads % n_group:
+            raise ValueError("DeformableLocalCrossAttention: num_heads must divide dim and n_group must divide both, got dim %d, "
+                             "%d heads, %d groups" % (dim, num_heads, n_group))
+        self.num_heads = num_heads
+        self.dim = dim
+        self.head_dim = dim // num_heads
+        self.scale = qk_scale or self.head_dim ** -0.5
+        self.proj_q = nn.Linear(dim, dim, bias=qkv_bias)
+        self.proj_k = nn.Linear(dim, dim, bias=qkv_bias)
+        self.proj_v = nn.Linear(dim, dim, bias=qkv_bias)
+        self.proj_v_off = nn.Linear(dim, dim, bias=qkv_bias)
+        self.attn_drop = nn.Dropout(attn_drop)
+        self.proj = nn.Linear(dim, dim)
+        self.proj_drop = nn.Dropout(proj_drop)
+        self.k = k
+        self.n_group = n_group
+        self.group_dims = dim // n_group
+        self.linear_offset = nn.Sequential(nn.Linear(2 * self.group_dims, dim), nn.LayerNorm(dim), nn.GELU(), nn.Linear(dim, 3, bias=False))
+
+    def fusable(self, q, v):
+        """The kernels serve HIP f32 tensors, head_dim 64, <= 16 heads, k <= 32 and no active attention dropout."""
+        return (q.is_cuda and v.is_cuda and q.dtype == torch.float32 and v.dtype == torch.float32 and self.dim == 64 * self.num_heads
+                and not (self.training and self.attn_drop.p > 0) and L.POOL_TRACE is None
+                and ops.deform_attn_usable(q.shape[0], q.shape[1], v.shape[1], self.k, self.num_heads, self.n_group))
+
+    def _grouped(self, x):
+        """(B,M,dim) -> (G,B,M,c) contiguous: the channel groups as whole matrices"""
+        B, M, _ = x.shape
+        return x.view(B, M, self.n_group, self.group_dims).permute(2, 0, 1, 3).contiguous()
+
+    def _weights(self, dist):
+        r = 1.0 / (dist + 1e-8)
+        return r / torch.sum(r, dim=-1, keepdim=True)
+
+    def _fused(self, q, v, v_pos, idx):
+        B, N, C = q.shape
+        NK, G, c, lin0, ln = v.shape[1], self.n_group, self.group_dims, self.linear_offset[0], self.linear_offset[1]
+        qp = HF.linear(q, self.proj_q.weight, self.proj_q.bias)
+        with torch.no_grad():
+            v_off = HF.linear(v.detach(), self.proj_v_off.weight, self.proj_v_off.bias)
+            Wa, Wb = lin0.weight[:, :c].contiguous(), lin0.weight[:, c:].contiguous()
+            vg, qg = self._grouped(v_off), self._grouped(qp.detach())
+            A = torch.stack([HF.linear(vg[g], Wa) for g in range(G)], dim=1)                    # (B,G,NK,C)
+            Bq = torch.stack([HF.linear(qg[g], Wb, lin0.bias) for g in range(G)], dim=1)        # (B,G,N,C)
+            pos = v_pos.detach().contiguous()
+            shift = HF.deform_offset(A, Bq, idx, pos, ln.weight, ln.bias, ln.eps, self.linear_offset[3].weight)
+            known = pos.unsqueeze(1).expand(-1, G, -1, -1).reshape(B * G, NK, 3)
+            dist, idx3 = shifted_three_nn(shift.view(B * G, N * self.k, 3), known)
+            w3 = self._weights(dist).view(B, G, N * self.k, 3)
+            idx3 = idx3.view(B, G, N * self.k, 3)
+        vg = self._grouped(v)
+        Wk, Wv = self.proj_k.weight, self.proj_v.weight
+        PK = torch.stack([HF.linear(vg[g], Wk[:, g * c:(g + 1) * c].contiguous()) for g in range(G)], dim=1)
+        PV = torch.stack([HF.linear(vg[g], Wv[:, g * c:(g + 1) * c].contiguous()) for g in range(G)], dim=1)
+        ctx = HF.deform_attention(qp, PK, PV, self.proj_k.bias, self.proj_v.bias, idx3, w3, self.num_heads, self.scale)
+        return self.proj_drop(HF.linear(ctx, self.proj.weight, self.proj.bias))
+
+    def _torch(self, q, v, v_pos, idx):
+        """the same restatement as torch operators, any device and dtype"""
+        B, N, C = q.shape
+        NK, G, c, lin0, ln = v.shape[1], self.n_group, self.group_dims, self.linear_offset[0], self.linear_offset[1]
+        qp = self.proj_q(q)
+        with torch.no_grad():
+            pos = v_pos.detach()
+            vg = self.proj_v_off(v).view(B, NK, G, c).permute(0, 2, 1, 3)
+            qg = qp.view(B, N, G, c).permute(0, 2, 1, 3)
+            A = torch.matmul(vg, lin0.weight[:, :c].t())
+            Bq = torch.matmul(qg, lin0.weight[:, c:].t()) + lin0.bias
+            shift = torch_cpu.deform_offset(A, Bq, idx, pos, ln.weight, ln.bias, ln.eps, self.linear_offset[3].weight)
+            known = pos.unsqueeze(1).expand(-1, G, -1, -1).reshape(B * G, NK, 3)
+            flat = shift.reshape(B * G, N * self.k, 3)
+            dist, idx3 = shifted_three_nn(flat, known)
+            if L.POOL_TRACE is not None:
+                # the recorded choice replaces this run's, and the distances follow it (slots beyond NK < 3 points stay at +inf)
+                idx3 = L.trace_idx('deformable_attention.idx3', idx3)
+                near = torch.gather(known, 1, idx3.long().reshape(B * G, -1, 1).expand(-1, -1, 3)).view(B * G, -1, 3, 3)
+                d = (flat.unsqueeze(2) - near).pow(2).sum(-1).sqrt()
+                dist = torch.where(torch.arange(3, device=d.device) < NK, d, torch.full_like(d, float('inf')))
+            w3 = self._weights(dist).view(B, G, N * self.k, 3)
+            idx3 = idx3.view(B, G, N * self.k, 3)
+        vg = v.view(B, NK, G, c).permute(0, 2, 1, 3)
+        PK = torch.matmul(vg, self.proj_k.weight.view(C, G, c).permute(1, 2, 0))
+        PV = torch.matmul(vg, self.proj_v.weight.view(C, G, c).permute(1, 2, 0))
+        drop = self.attn_drop if self.training and self.attn_drop.p > 0 else None
+        ctx = torch_cpu.deform_attention(qp, PK, PV, self.proj_k.bias, self.proj_v.bias, idx3, w3, self.num_heads, self.scale, drop)
+        return self.proj_drop(self.proj(ctx))
+
+    def forward(self, q, q_pos, v=None, v_pos=None, idx=None, denoise_length=None):
+        if denoise_length is not None:
+            if idx is not None:
+                raise ValueError("denoise_length needs the list computed here, but idx is given")
+            if v is not None or v_pos is not None:
+                raise ValueError("denoise_length applies to the self form only, but v / v_pos is given")
+        v = q if v is None else v
+        v_pos = q_pos if v_pos is None else v_pos
+        if q_pos.dim() != 3 or q_pos.size(-1) != 3 or v_pos.dim() != 3 or v_pos.size(-1) != 3:
+            raise ValueError("q_pos and v_pos must be (B, N, 3), got %s and %s" % (tuple(q_pos.shape), tuple(v_pos.shape)))
+        if q.size(-1) != self.dim or v.size(-1) != self.dim:
+            raise ValueError("q and v must have %d channels, got %d and %d" % (self.dim, q.size(-1), v.size(-1)))
+        if idx is None:
+            idx = knn_point(self.k, v_pos, q_pos) if denoise_length is None else denoise_knn(self.k, q_pos, denoise_length)
+        if idx.shape != (q.shape[0], q.shape[1], self.k):
+            raise ValueError("idx must be (B, N, k) = %s, got %s" % ((q.shape[0], q.shape[1], self.k), tuple(idx.shape)))
+        idx = idx.long()
+        if self.fusable(q, v):
+            return self._fused(q, v, v_pos, idx)
+        if q.is_cuda and L.POOL_TRACE is None:
+            HF.note_declined("DeformableLocalCrossAttention (%d,%d) x (%d,%d), %d heads, k = %d"
+                             % (q.shape[1], self.dim, v.shape[1], self.dim, self.num_heads, self.k),
+                             "head_dim != 64 / more than 16 heads / k > 32 / dtype / attention dropout")
+        return self._torch(q, v, v_pos, idx)
+
+
+class DeformableAttnBlock(nn.Module):
+    """reference models/Transformer_utils.py:917-935: x + deformable self-attention, x + MLP.  forward(x (B,N,dim), pos (B,N,3))."""
+
+    def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, drop=0., attn_drop=0., init_values=None, drop_path=0.,
+                 act_layer=nn.GELU, norm_layer=nn.LayerNorm):
+        super().__init__()
+        self.norm1 = norm_layer(dim)
+        self.deformable_attn = DeformableLocalCrossAttention(dim, num_heads=num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop)
+        self.ls1 = LayerScale(dim, init_values=init_values) if init_values else nn.Identity()
+        self.drop_path1 = DropPath(drop_path) if drop_path > 0. else nn.Identity()
+        self.norm2 = norm_layer(dim)
+        self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
+        self.ls2 = LayerScale(dim, init_values=init_values) if init_values else nn.Identity()
+        self.drop_path2 = DropPath(drop_path) if drop_path > 0. else nn.Identity()
+
+    def forward(self, x, pos):
+        x = x + self.drop_path1(self.ls1(self.deformable_attn(HF.layer_norm(x, self.norm1), pos)))
+        return x + self.drop_path2(self.ls2(self.mlp(HF.layer_norm(x, self.norm2))))
+
+
+class DeformableAttnDecoderBlock(nn.Module):
+    """reference models/Transformer_utils.py:988-1015: self-attention over the queries, deformable cross-attention over the memory
+    tokens, an MLP.  forward(q (B,N,dim), v (B,NK,dim), q_pos (B,N,3), v_pos (B,NK,3))."""
+
+    def __init__(self, dim, num_heads, dim_q=None, mlp_ratio=4., qkv_bias=False, drop=0., attn_drop=0., init_values=None, drop_path=0.,
+                 act_layer=nn.GELU, norm_layer=nn.LayerNorm):
+        super().__init__()
+        self.norm1 = norm_layer(dim)
+        self.self_attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop)
+        self.norm_q = norm_layer(dim_q or dim)
+        self.norm_v = norm_layer(dim)
+        self.attn = DeformableLocalCrossAttention(dim, num_heads=num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop)
+        self.drop_path1 = DropPath(drop_path) if drop_path > 0. else nn.Identity()
+        self.norm2 = norm_layer(dim)
+        self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
+        self.drop_path2 = DropPath(drop_path) if drop_path > 0. else nn.Identity()
+        self.drop_path3 = DropPath(drop_path) if drop_path > 0. else nn.Identity()
+        self.ls1 = LayerScale(dim, init_values=init_values) if init_values else nn.Identity()
+        self.ls2 = LayerScale(dim, init_values=init_values) if init_values else nn.Identity()
+        self.ls3 = LayerScale(dim, init_values=init_values) if init_values else nn.Identity()
+
+    def forward(self, q, v, q_pos, v_pos):
+        q = q + self.drop_path1(self.ls1(self.self_attn(HF.layer_norm(q, self.norm1))))
+        q = q + self.drop_path2(self.ls2(self.attn(q=HF.layer_norm(q, self.norm_q), v=HF.layer_norm(v, self.norm_v), q_pos=q_pos, v_pos=v_pos)))
+        return q + self.drop_path3(self.ls3(self.mlp(HF.layer_norm(q, self.norm2))))

@@ -5,6 +5,7 @@
 //   upp_gather_bwd_det, upp_grouping_bwd_det             GatherJob           group.hip     (grouping IS gather on the flat index list)
 //   upp_three_interpolate_bwd_det                        InterpolateJob      pointnet2.hip
 //   upp_knn_scatter_add_det, upp_edge_conv_bwd's g_A     KnnScatterJob       knn_points.hip
+//   upp_deform_attn_bwd_det                              DeformJob           deform_attn.hip (values formed on the fly while staging)
 // (upp_emd_matchcost_det is an ordered sum of tile costs, not a scatter: emd.hip.)
 //
 // A scatter-add by f32 atomics sums each target's contributions in whatever order the hardware retires them.  Here every TARGET is

@@ -538,6 +538,89 @@ def query_select(score, cand, Q, extra=None):
     return _QuerySelect.apply(score.detach().contiguous(), cand.contiguous(), None if extra is None else extra.contiguous(), Q)
 
 
+# ------------------------------------------------------------------ deformable local cross-attention (README section of that name)
+class _DeformAttention(Function):
+    """softmax over the k interpolated neighbour rows of every query as one node (include/upp_hip.h "deformable local cross-attention"):
+    saves its inputs, ctx's companion p (B,N,H,k) and nothing of B N k C elements -- the key / value rows are recomputed.  The d_PK / d_PV
+    scatter-add follows the deterministic mode: `det` None reads DETERMINISTIC when the backward runs, True / False fixes it for this call.
+    idx3 and w3 get no gradient."""
+
+    @staticmethod
+    def forward(ctx, q, PK, PV, bk, bv, idx3, w3, num_heads, scale, det):
+        out, p = ops.deform_attn_fwd(q, PK, PV, bk, bv, idx3, w3, num_heads, scale)
+        ctx.save_for_backward(q, PK, PV, bk, bv, idx3, w3, p)
+        ctx.cfg = (num_heads, scale, det)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        q, PK, PV, bk, bv, idx3, w3, p = ctx.saved_tensors
+        num_heads, scale, det = ctx.cfg
+        need = ctx.needs_input_grad
+        g = g.contiguous()
+        want_bk = bk is not None and need[3]
+        d_q, d_PK, d_PV, _ds, d_krow = ops.deform_attn_bwd(q, PK, PV, bk, bv, idx3, w3, p, g, num_heads, scale,
+                                                           deterministic=DETERMINISTIC if det is None else det, want_krow=want_bk)
+        C = g.shape[-1]
+        return (d_q if need[0] else None, d_PK if need[1] else None, d_PV if need[2] else None,
+                ops.sum_rows(d_krow.view(-1, C)) if want_bk else None,
+                ops.sum_rows(g.view(-1, C)) if bv is not None and need[4] else None, None, None, None, None, None)
+
+
+def _deform_f32(*ts):
+    return all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 for t in ts)
+
+
+def deform_attention_usable(q, PK, PV, idx3, w3, num_heads):
+    """Do the fused kernels serve these operands (HIP f32 / int32 tensors, head_dim 64, the served sizes of include/upp_hip.h)?"""
+    if not (_deform_f32(q, PK, PV, w3) and isinstance(idx3, torch.Tensor) and idx3.is_cuda and idx3.dtype == torch.int32):
+        return False
+    if q.dim() != 3 or PK.dim() != 4 or PV.shape != PK.shape or idx3.dim() != 4 or idx3.shape != w3.shape:
+        return False
+    B, N, C = q.shape
+    G, NK = PK.shape[1], PK.shape[2]
+    H = int(num_heads)
+    if H < 1 or C != 64 * H or N < 1 or idx3.shape[2] % N or tuple(PK.shape) != (B, G, NK, C) or tuple(idx3.shape[:2]) != (B, G):
+        return False
+    return ops.deform_attn_usable(B, N, NK, idx3.shape[2] // N, H, G)
+
+
+def deform_offset(A, Bq, idx, pos, gamma, beta, eps, W3):
+    """A (B,G,NK,C) and Bq (B,G,N,C) the per-point halves of the offset head's first Linear, idx (B,N,k) int64 (HF.knn_query's list),
+    pos (B,NK,3), LayerNorm gamma / beta (C) and eps, W3 (3,C) -> shift (B,G,N k,3) = pos[idx] + tanh(W3 gelu(LayerNorm(A[idx] + Bq))).
+    No autograd node: it runs under no_grad (three_nn, its only consumer, is not differentiable).  HIP tensors outside the served range
+    (C = 64 H, H <= 16, k <= 32) take the torch formulation (note_declined records it); CPU tensors take it when upp_hip.torch_cpu is
+    enabled."""
+    from . import torch_cpu
+    with torch.no_grad():
+        if _torch_cpu(A, Bq, idx, pos):
+            return torch_cpu.deform_offset(A, Bq, idx, pos, gamma, beta, eps, W3)
+        if A.is_cuda and not (_deform_f32(A, Bq, pos, gamma, beta, W3) and A.dim() == 4 and A.shape[3] % 64 == 0 and idx.dim() == 3 and
+                              ops.deform_attn_usable(A.shape[0], idx.shape[1], A.shape[2], idx.shape[2], A.shape[3] // 64, A.shape[1])):
+            note_declined("deform_offset A %s, k = %d" % (tuple(A.shape), idx.shape[-1]), "outside the served range")
+            return torch_cpu.deform_offset(A, Bq, idx, pos, gamma, beta, eps, W3)
+        return ops.deform_offset_fwd(A.contiguous(), Bq.contiguous(), idx.long().contiguous(), pos.contiguous(), gamma.contiguous(),
+                                     beta.contiguous(), W3.contiguous(), float(eps))
+
+
+def deform_attention(q, PK, PV, bk, bv, idx3, w3, num_heads, scale, deterministic=None):
+    """q (B,N,C), PK / PV (B,G,NK,C) the per-group key / value products of the memory tokens, bk / bv (C) or None, idx3 int32 and w3 f32
+    (B,G,N k,3) (three_nn of the shifted positions and the reference's weights) -> ctx (B,N,C): per query and head the softmax over the
+    k interpolated neighbour rows (include/upp_hip.h "deformable local cross-attention").  q, PK, PV, bk, bv get gradients, idx3 and w3
+    none.  deterministic: None follows functional.DETERMINISTIC (read when the backward node runs), True / False per call.  HIP tensors
+    outside the served range (head_dim 64, H <= 16, G | H, k <= 32) take the torch formulation (note_declined records it); CPU tensors
+    take it when upp_hip.torch_cpu is enabled."""
+    from . import torch_cpu
+    if _torch_cpu(q, PK, PV, idx3, w3):
+        return torch_cpu.deform_attention(q, PK, PV, bk, bv, idx3, w3, num_heads, scale)
+    if q.is_cuda and not deform_attention_usable(q, PK, PV, idx3, w3, num_heads):
+        note_declined("deform_attention q %s, %d heads, PK %s" % (tuple(q.shape), num_heads, tuple(PK.shape)), "outside the served range")
+        return torch_cpu.deform_attention(q, PK, PV, bk, bv, idx3, w3, num_heads, scale)
+    return _DeformAttention.apply(q.contiguous(), PK.contiguous(), PV.contiguous(), None if bk is None else bk.contiguous(),
+                                  None if bv is None else bv.contiguous(), idx3.contiguous(), w3.detach().contiguous(), int(num_heads),
+                                  float(scale), None if deterministic is None else bool(deterministic))
+
+
 def _expand_norm(norm):
     if norm is None:
         return None
@@ -2161,7 +2244,7 @@ ADAPTER_FACTORS = True        # ... which inside a deferred scope writes per-row
 
 # Reproducible training (README "Reproducible training"): with DETERMINISTIC on, the autograd nodes whose backward (or forward: the EMD
 # cost) sums with f32 atomics -- GatherOperation, _FpsGather, _KnnGroup, _GroupPoints, ChamferFunction, _ChamferLoss,
-# EarthMoverDistanceFunction, ThreeInterpolate, GroupingOperation, KnnPoints, KnnGather, _EdgeConvMax -- call the library's `_det` siblings (a defined summation order: include/upp_hip.h "deterministic
+# EarthMoverDistanceFunction, ThreeInterpolate, GroupingOperation, KnnPoints, KnnGather, _EdgeConvMax, _DeformAttention -- call the library's `_det` siblings (a defined summation order: include/upp_hip.h "deterministic
 # scatter-adds").  Read at CALL time, also by the backward thread; a captured step keeps the choice it was captured under, whatever the
 # attribute says at replay.  UPP_DETERMINISTIC=1 sets it once, at import.
 DETERMINISTIC = os.environ.get("UPP_DETERMINISTIC", "").strip() not in ("", "0")

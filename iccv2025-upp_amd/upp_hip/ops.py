@@ -741,6 +741,125 @@ def query_select_bwd(g_out, order, M):
     return g_cand, g_extra
 
 
+# ------------------------------------------------------------------ deformable local cross-attention (include/upp_hip.h)
+DEFORM_MAX_H = 16
+DEFORM_MAX_K = 32
+
+
+def deform_attn_usable(B, N, NK, k, H, G):
+    """The served range of upp_deform_offset_fwd / upp_deform_attn_* (head_dim 64 is the caller's C == 64 H)."""
+    if min(B, N, NK, k, H, G) < 1 or H > DEFORM_MAX_H or k > DEFORM_MAX_K or H % G or B > 65535:
+        return False
+    C = 64 * H
+    return max(B * N * k * H, B * G * NK * C, B * G * N * C, B * G * N * k * 3) < 2 ** 31
+
+
+def _deform_sizes(who, B, N, NK, k, H, G):
+    if min(B, N, NK, k, H, G) < 1:
+        raise RuntimeError("%s: every size must be positive, got B = %d, N = %d, NK = %d, k = %d, H = %d, G = %d" % (who, B, N, NK, k, H, G))
+    if not deform_attn_usable(B, N, NK, k, H, G):
+        raise RuntimeError("%s: B = %d, N = %d, NK = %d, k = %d, H = %d, G = %d is outside the served range head_dim 64, 1 <= H <= %d, "
+                           "G | H, 1 <= k <= %d, B <= 65535, every array below 2^31 elements (UPP_E_RANGE)"
+                           % (who, B, N, NK, k, H, G, DEFORM_MAX_H, DEFORM_MAX_K))
+
+
+def _aligned16(who, **tensors):
+    for name, t in tensors.items():
+        if t is not None and t.data_ptr() % 16:
+            raise RuntimeError("%s: %s must be 16-byte aligned" % (who, name))
+
+
+def _positive(who, name, v):
+    v = float(v)
+    if not (v > 0.0 and v != float("inf")):
+        raise RuntimeError("%s: %s must be finite and positive, got %r" % (who, name, v))
+    return v
+
+
+def deform_offset_fwd(A, Bq, idx, pos, gamma, beta, W3, eps):
+    """A (B,G,NK,C), Bq (B,G,N,C), idx (B,N,k) int64, pos (B,NK,3), gamma / beta (C), W3 (3,C) -> shift (B,G,N k,3) =
+    pos[idx] + tanh(W3 gelu(LayerNorm(A[idx] + Bq))): upp_deform_offset_fwd, 1 launch, no (B,G,N,k,C) tensor."""
+    _need(A, "A", torch.float32, 4)
+    B, G, NK, C = A.shape
+    _need(Bq, "Bq", torch.float32, 4)
+    N = Bq.shape[2]
+    _need_f32(Bq, "Bq", (B, G, N, C))
+    _need(idx, "idx", torch.int64, 3)
+    k = idx.shape[2]
+    if tuple(idx.shape) != (B, N, k):
+        raise RuntimeError("deform_offset: idx must be (B, N, k) = (%d, %d, k), got %s" % (B, N, tuple(idx.shape)))
+    _need_f32(pos, "pos", (B, NK, 3))
+    _need_f32(gamma, "gamma", (C,))
+    _need_f32(beta, "beta", (C,))
+    _need_f32(W3, "W3", (3, C))
+    _same_device(A, Bq, idx, pos, gamma, beta, W3)
+    eps = _positive("deform_offset", "eps", eps)
+    if C % 64:
+        raise RuntimeError("deform_offset: C = %d is outside the served range (a multiple of 64: UPP_E_RANGE)" % C)
+    _deform_sizes("deform_offset", B, N, NK, k, C // 64, G)
+    _aligned16("deform_offset", A=A, Bq=Bq, idx=idx, pos=pos, gamma=gamma, beta=beta, W3=W3)
+    shift = torch.empty((B, G, N * k, 3), dtype=torch.float32, device=A.device)
+    _call(A.device, "upp_deform_offset_fwd", _abi.ptr(A), _abi.ptr(Bq), _abi.ptr(idx), _abi.ptr(pos), _abi.ptr(gamma), _abi.ptr(beta),
+          _abi.ptr(W3), _abi.ptr(shift), eps, B, G, N, NK, k, C)
+    return shift
+
+
+def _deform_attn_args(who, q, PK, PV, bk, bv, idx3, w3, H, scale):
+    _need(q, "q", torch.float32, 3)
+    B, N, C = q.shape
+    _need(PK, "PK", torch.float32, 4)
+    G, NK = PK.shape[1], PK.shape[2]
+    _need_f32(PK, "PK", (B, G, NK, C))
+    _need_f32(PV, "PV", (B, G, NK, C))
+    _need_f32(bk, "bk", (C,), optional=True)
+    _need_f32(bv, "bv", (C,), optional=True)
+    _need(idx3, "idx3", torch.int32, 4, 3)
+    _need(w3, "w3", torch.float32, 4, 3)
+    if idx3.shape != w3.shape or idx3.shape[0] != B or idx3.shape[1] != G or idx3.shape[2] % N:
+        raise RuntimeError("%s: idx3 and w3 must both be (B, G, N k, 3) = (%d, %d, %d k, 3), got %s and %s"
+                           % (who, B, G, N, tuple(idx3.shape), tuple(w3.shape)))
+    k = idx3.shape[2] // N
+    _same_device(q, PK, PV, idx3, w3, *[t for t in (bk, bv) if t is not None])
+    H = int(H)
+    scale = _positive(who, "scale", scale)
+    if H < 1 or C != 64 * H:
+        raise RuntimeError("%s: C = %d with %d heads is outside the served range (head_dim 64: UPP_E_RANGE)" % (who, C, H))
+    _deform_sizes(who, B, N, NK, k, H, G)
+    _aligned16(who, q=q, PK=PK, PV=PV, bk=bk, bv=bv, idx3=idx3, w3=w3)
+    return B, N, NK, k, H, G, C, scale
+
+
+def deform_attn_fwd(q, PK, PV, bk, bv, idx3, w3, H, scale):
+    """q (B,N,C), PK / PV (B,G,NK,C), bk / bv (C) | None, idx3 int32 and w3 (B,G,N k,3) -> ctx (B,N,C), p (B,N,H,k): upp_deform_attn_fwd."""
+    B, N, NK, k, H, G, C, scale = _deform_attn_args("deform_attention", q, PK, PV, bk, bv, idx3, w3, H, scale)
+    ctx = torch.empty((B, N, C), dtype=torch.float32, device=q.device)
+    p = torch.empty((B, N, H, k), dtype=torch.float32, device=q.device)
+    _call(q.device, "upp_deform_attn_fwd", _abi.ptr(q), _abi.ptr(PK), _abi.ptr(PV), _abi.ptr(bk), _abi.ptr(bv), _abi.ptr(idx3), _abi.ptr(w3),
+          _abi.ptr(ctx), _abi.ptr(p), scale, B, N, NK, k, H, G)
+    return ctx, p
+
+
+def deform_attn_bwd(q, PK, PV, bk, bv, idx3, w3, p, d_ctx, H, scale, deterministic=False, want_krow=False):
+    """-> d_q (B,N,C), d_PK, d_PV (B,G,NK,C), ds (B,N,H,k), d_krow (B,N,C) | None (the rows whose column sums are d_bk).  d_PK / d_PV by
+    f32 atomics into arrays the entry point zeroes with a kernel (upp_deform_attn_bwd) or, deterministic, in ascending (n k + s) 3 + j
+    (upp_deform_attn_bwd_det, include/upp_hip.h)."""
+    B, N, NK, k, H, G, C, scale = _deform_attn_args("deform_attention_bwd", q, PK, PV, bk, bv, idx3, w3, H, scale)
+    _need_f32(p, "p", (B, N, H, k))
+    _need_f32(d_ctx, "d_ctx", (B, N, C))
+    _same_device(q, p, d_ctx)
+    _aligned16("deform_attention_bwd", p=p, d_ctx=d_ctx)
+    dev = q.device
+    d_q = torch.empty((B, N, C), dtype=torch.float32, device=dev)
+    d_PK = torch.empty((B, G, NK, C), dtype=torch.float32, device=dev)
+    d_PV = torch.empty((B, G, NK, C), dtype=torch.float32, device=dev)
+    ds = torch.empty((B, N, H, k), dtype=torch.float32, device=dev)
+    d_krow = torch.empty((B, N, C), dtype=torch.float32, device=dev) if want_krow else None
+    _call(dev, "upp_deform_attn_bwd_det" if deterministic else "upp_deform_attn_bwd", _abi.ptr(q), _abi.ptr(PK), _abi.ptr(PV), _abi.ptr(bk),
+          _abi.ptr(bv), _abi.ptr(idx3), _abi.ptr(w3), _abi.ptr(p), _abi.ptr(d_ctx), _abi.ptr(d_q), _abi.ptr(d_PK), _abi.ptr(d_PV),
+          _abi.ptr(d_krow), _abi.ptr(ds), scale, B, N, NK, k, H, G)
+    return d_q, d_PK, d_PV, ds, d_krow
+
+
 # ------------------------------------------------------------------ Chamfer
 def chamfer_fwd(xyz1, xyz2):
     _need(xyz1, "xyz1", torch.float32, 3, 3)

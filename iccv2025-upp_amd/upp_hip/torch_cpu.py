@@ -254,6 +254,51 @@ def prefix_attention(q, k, v, num_heads, scale, split_q, split_k):
     return (attn @ vh).transpose(1, 2).reshape(B, Lq, C)
 
 
+def deform_offset(A, Bq, idx, pos, gamma, beta, eps, W3):
+    """The offset head of include/upp_hip.h "deformable local cross-attention" as torch operators (any device and dtype): A (B,G,NK,C),
+    Bq (B,G,N,C), idx (B,N,k) rows of the NK points, pos (B,NK,3), LayerNorm gamma / beta (C) and eps, W3 (3,C) -> shift (B,G,N k,3) =
+    pos[idx] + tanh(W3 gelu(LayerNorm(A[idx] + Bq))).  It keeps the (B,G,N,k,C) tensor the kernel avoids."""
+    import torch.nn.functional as F
+    B, G, NK, C = A.shape
+    N, k = idx.shape[1], idx.shape[2]
+    flat = idx.long().reshape(B, 1, N * k, 1)
+    y = torch.gather(A, 2, flat.expand(-1, G, -1, C)).view(B, G, N, k, C) + Bq.unsqueeze(3)
+    h = F.gelu(F.layer_norm(y, (C,), gamma, beta, float(eps)))
+    off = torch.tanh(torch.matmul(h, W3.t()))                                          # (B,G,N,k,3)
+    local = torch.gather(pos, 1, flat.view(B, N * k, 1).expand(-1, -1, 3)).view(B, 1, N, k, 3)
+    return (local + off).reshape(B, G, N * k, 3)
+
+
+def deform_attention(q, PK, PV, bk, bv, idx3, w3, num_heads, scale, drop=None):
+    """The gather-attend core of include/upp_hip.h "deformable local cross-attention" as torch operators (any device, dtype and
+    head_dim; differentiable in q, PK, PV, bk, bv): q (B,N,C), PK / PV (B,G,NK,C), bk / bv (C) | None, idx3 and w3 (B,G,N k,3) ->
+    ctx (B,N,C); drop: the module's attention dropout or None.  key_s = bk + sum_g sum_j w3 PK_g[idx3] (g, then j ascending), val_s likewise; softmax over the k slots per head.  It
+    keeps the (B,N,k,C) rows the kernels avoid."""
+    B, N, C = q.shape
+    G, NK = PK.shape[1], PK.shape[2]
+    H = int(num_heads)
+    k = idx3.shape[2] // N
+    flat = idx3.long().reshape(B, G, N * k * 3, 1).expand(-1, -1, -1, C)
+    w = w3.detach().unsqueeze(-1)
+
+    def rows(P, bias):
+        t = torch.gather(P, 2, flat).view(B, G, N * k, 3, C) * w
+        r = None
+        for g in range(G):
+            for j in range(3):
+                r = t[:, g, :, j] if r is None else r + t[:, g, :, j]
+        if bias is not None:
+            r = r + bias
+        return r.view(B, N, k, H, C // H)
+
+    key, val = rows(PK, bk), rows(PV, bv)
+    score = (q.view(B, N, 1, H, C // H) * key).sum(-1) * scale                        # (B,N,k,H)
+    p = score.softmax(dim=2)
+    if drop is not None:
+        p = drop(p)
+    return (p.unsqueeze(-1) * val).sum(2).reshape(B, N, C)
+
+
 def chamfer(xyz1, xyz2):
     """-> (dist1 (B,N), dist2 (B,M)) squared nearest-neighbour distances, differentiable (reference extensions/chamfer_dist)."""
     d = ((xyz1.unsqueeze(2) - xyz2.unsqueeze(1)) ** 2).sum(-1)

@@ -354,6 +354,60 @@ int upp_query_select_fwd(const float *score, const float *cand, const float *ext
                          void *stream);
 int upp_query_select_bwd(const float *g_out, const int *order, float *g_cand, float *g_extra, int B, int M, int Q, int D, void *stream);
 
+/* ---- deformable local cross-attention: the offset head and the gather-attend core (additions to ABI 5) -------------------------
+ * What is left of DeformableLocalCrossAttention (reference models/Transformer_utils.py:269-491) once its three tall products are
+ * taken through the gather (README "Deformable local cross-attention"): per (sample, query, neighbour slot) work with no GEMM in it.
+ * C = 64 H channels, H heads of 64, G channel groups (G divides H), k neighbour slots, N queries, NK memory points.
+ *
+ * upp_deform_offset_fwd (forward only: nothing downstream of it is differentiable)
+ *   A (B,G,NK,C), Bq (B,G,N,C) the per-point halves of the offset head's first Linear (bias in Bq); idx (B,N,k) int64 rows of the NK
+ *   points (the list of upp_knn); pos (B,NK,3); gamma, beta (C) and eps of the LayerNorm; W3 (3,C)
+ *   -> shift (B,G,N k,3): per row (b,g,n,s), with j = idx[b,n,s]:  y = A[b,g,j] + Bq[b,g,n] (one f32 addition per channel, never
+ *      stored); LayerNorm over the C values (mean, then the BIASED variance of y - mean: two passes over the registers); exact (erf)
+ *      GELU; three dot products with the rows of W3; shift = pos[b,j] + tanh(.).
+ *   One wave per row, channel 64 i + lane in register i of the lane.  Every reduction (mean, variance, the three dot products) is the
+ *   lane's partial over i ascending, then the fixed tree of the wave sum (xor 1, xor 2, half-row mirror, row mirror, (r0 + r1) +
+ *   (r2 + r3)): the same bits on every run and for every batch size.  Each output element is written by one wave: no atomics, no
+ *   scratch, nothing zeroed.  A row whose idx lies outside [0, NK) is never read through and gets NaN.  1 launch.
+ *
+ * upp_deform_attn_fwd
+ *   q (B,N,C); PK, PV (B,G,NK,C) the per-group key / value products of the memory tokens; bk, bv (C) or NULL (= 0); idx3 int32 and
+ *   w3 f32 (B,G,N k,3): the three nearest memory points of every shifted position and their interpolation weights; scale
+ *   -> per (b, n, head h with channels [64 h, 64 h + 64)), for every slot s:
+ *        key_s[ch] = bk[ch], then fma(w3[b,g,n k + s,j], PK[b,g,idx3[b,g,n k + s,j],ch], key_s[ch]) for ascending g, then ascending j;
+ *        val_s likewise from PV and bv;  score_s = scale * sum_ch q[ch] key_s[ch] (the wave sum above);
+ *        p = softmax over s with the maximum subtracted (expf, the sum by the wave sum, one division per slot);
+ *        ctx[b,n,ch] = fma(p_s, val_s[ch], .) from +0 in ascending s.
+ *      ctx (B,N,C) and p (B,N,H,k), which the backward reads.  The rows key_s / val_s live in registers only.  One wave per (b,n,h),
+ *      lane = channel: every row read is one coalesced 256-byte segment.  Deterministic.  idx3 values are the caller's duty; one
+ *      outside [0, NK) contributes nothing (never read or written through).  1 launch.
+ *
+ * upp_deform_attn_bwd / upp_deform_attn_bwd_det
+ *   + p, d_ctx (B,N,C) -> d_q (B,N,C), d_PK, d_PV (B,G,NK,C), ds (B,N,H,k), d_krow (B,N,C) or NULL.  The rows are recomputed:
+ *        dp_s = d_ctx . val_s;  ds_s = p_s (dp_s - sum_s p_s dp_s);  d_q = scale * (fma(ds_s, key_s, .) from +0 in ascending s);
+ *        d_key_s = (scale * ds_s) * q, d_val_s = p_s * d_ctx (each product rounded once);  d_krow[b,n] = sum_s d_key_s in ascending s
+ *        (its column sums are the gradient of bk; that of bv is the column sums of d_ctx);
+ *        d_PK[b,g,idx3[..,j]] += w3[..,j] * d_key_s, d_PV likewise with d_val_s.  w3 and idx3 get no gradient.
+ *      d_q, ds and d_krow have a fixed order in both forms.  upp_deform_attn_bwd: d_PK / d_PV are zeroed here by a kernel (no memset)
+ *      and summed by f32 atomics, 256 contiguous bytes per wave instruction, in the order the hardware retires them: 3 launches.
+ *      upp_deform_attn_bwd_det: d_PK[b,g,r,ch] = +0.0f, then + the rounded product of every source (n, s, j) with idx3 == r in ascending
+ *      (n k + s) 3 + j, one rounded addition each; a job of the one `_det` kernel body (csrc/det_scan.h) whose sources are formed on
+ *      the fly from w3, p, ds, q and d_ctx.  Every element is overwritten: nothing to zero.  2 launches.
+ *
+ * Limits: 1 <= H <= 16 (C a multiple of 64 for the offset), G divides H, 1 <= k <= 32, N, NK >= 1, B <= 65535 and every array below
+ *   2^31 elements -- UPP_E_RANGE beyond.  A null pointer (bk, bv, d_krow excepted), a non-positive size, a scale or eps that is not
+ *   finite and positive: UPP_E_BADARG.  Both before any launch. */
+int upp_deform_offset_fwd(const float *A, const float *Bq, const int64_t *idx, const float *pos, const float *gamma, const float *beta,
+                          const float *W3, float *shift, float eps, int B, int G, int N, int NK, int k, int C, void *stream);
+int upp_deform_attn_fwd(const float *q, const float *PK, const float *PV, const float *bk, const float *bv, const int32_t *idx3,
+                        const float *w3, float *ctx, float *p, float scale, int B, int N, int NK, int k, int H, int G, void *stream);
+int upp_deform_attn_bwd(const float *q, const float *PK, const float *PV, const float *bk, const float *bv, const int32_t *idx3,
+                        const float *w3, const float *p, const float *d_ctx, float *d_q, float *d_PK, float *d_PV, float *d_krow,
+                        float *ds, float scale, int B, int N, int NK, int k, int H, int G, void *stream);
+int upp_deform_attn_bwd_det(const float *q, const float *PK, const float *PV, const float *bk, const float *bv, const int32_t *idx3,
+                            const float *w3, const float *p, const float *d_ctx, float *d_q, float *d_PK, float *d_PV, float *d_krow,
+                            float *ds, float scale, int B, int N, int NK, int k, int H, int G, void *stream);
+
 /* ---- Chamfer distance ----------------------------------------------------------
  * Replaces chamfer.forward / chamfer.backward (reference
  * extensions/chamfer_dist/chamfer_cuda.cpp:36-39, kernels chamfer.cu:15-145 and
@@ -425,7 +479,9 @@ int upp_emd_matchcost_bwd(const float *grad_cost, const float *xyz1, const float
  *                           [0, m) are skipped; grad_features needs NO zero-fill.
  *   upp_grouping_bwd_det    grad_features[b][ch][r] = +0.0f, then + grad_out[b][ch][p][s] for every (p, s) with idx[b][p][s] == r,
  *                           in ascending p * S + s; grad_features needs NO zero-fill (upp_gather_bwd_det on the flattened list).
- *   upp_knn_scatter_add_det stated and declared with its sibling under "the pytorch3d.ops surface" above: ascending l * K + k. */
+ *   upp_knn_scatter_add_det stated and declared with its sibling under "the pytorch3d.ops surface" above: ascending l * K + k.
+ *   upp_deform_attn_bwd_det stated and declared with its sibling under "deformable local cross-attention" above: ascending
+ *                           (n k + s) 3 + j. */
 int upp_chamfer_bwd_det(const float *xyz1, const float *xyz2, const int32_t *idx1, const int32_t *idx2,
                         const float *grad_dist1, const float *grad_dist2, float *g1, float *g2,
                         int B, int n, int m, void *stream);
