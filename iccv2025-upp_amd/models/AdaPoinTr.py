@@ -3,15 +3,24 @@ Class names and state-dict keys are the reference's, so its checkpoints load wit
 
 A block style is one or two tokens joined by '-'.  Served tokens: `attn` (global attention) and `graph` (DynamicGraphAttention), alone or
 paired, combined by `concat` (both on one normalised input, merged by a Linear over the concatenation) or `onebyone` (one residual
-branch each).  The token `deform` (Transformer_utils.DeformableLocalCrossAttention) is served behind the keyword deformable=True of the
-block APIs, the stacks and the two Point* classes -- `deformable: true` in a model config, which PCTransformer and the *Entry classes
-read; with the default False it raises ValueError at construction like `rw_deform` and `deform_graph`, which are not ported.
+branch each).  The tokens `deform` (Transformer_utils.DeformableLocalCrossAttention) and `deform_graph`
+(Transformer_utils.improvedDeformableLocalGraphAttention) are served behind the keyword `deformable` of the block APIs, the stacks and
+the two Point* classes, which PCTransformer and the *Entry classes read from a model config:
+    token           built as                                   opted in by
+    attn, graph     Attention / CrossAttention, DynamicGraphAttention          always served
+    deform          DeformableLocalCrossAttention              deformable=True, or a collection that names it (`deformable: true`)
+    deform_graph    improvedDeformableLocalGraphAttention      a collection that names it (`deformable: [deform, deform_graph]`)
+    rw_deform       not ported                                 raises ValueError everywhere
+True means exactly {'deform'}; a name outside ('deform', 'deform_graph') raises ValueError; with the default False every one of the
+three deformable tokens raises ValueError at construction.
     LayerNorm                      HF.layer_norm (the row kernel; eps from the module, 1e-6 in the stacks)
     self-attention                 Transformer_utils.Attention; with denoise_length the fused prefix-visibility kernel -- CrossAttnBlockApi
                                    passes denoise_length on and never builds the reference's (N, N) mask tensor
     cross-attention                upp_layers.CrossAttention (HF.cross_attention)
     graph branches                 Transformer_utils.DynamicGraphAttention (HF.edge_conv_max)
     deformable branches            Transformer_utils.DeformableLocalCrossAttention (HF.deform_offset, HF.three_nn, HF.deform_attention)
+    deformable graph branches      Transformer_utils.improvedDeformableLocalGraphAttention (HF.deform_offset(ball=True), HF.three_nn,
+                                   HF.interp_edge_max)
     merge maps                     HF.linear;  MLPs: upp_layers.Mlp (HF.mlp_gelu)
 TransformerEncoder / TransformerDecoder compute every neighbour list once per forward -- the denoise list included, which the reference
 recomputes inside every block; positions do not change between blocks, so the lists are the same -- and only the lists some block uses.
@@ -52,17 +61,35 @@ from .Transformer import conv_bn_act_conv
 from .build import build_model_from_cfg
 from .dgcnn_group import DGCNN_Grouper
 from .Transformer_utils import (Attention, CrossAttention, DeformableLocalCrossAttention, DropPath, DynamicGraphAttention, LayerScale, Mlp,
-                                denoise_knn, knn_point)
+                                denoise_knn, improvedDeformableLocalGraphAttention, knn_point)
 
 SERVED_TOKENS = ('attn', 'graph')
 UNPORTED_TOKENS = ('rw_deform', 'deform', 'deform_graph')
 
 
+OPT_IN_TOKENS = ('deform', 'deform_graph')
+
+
+def _opted_in(deformable):
+    """the keyword `deformable` -> the frozenset of opted-in tokens: False / None nothing, True exactly {'deform'}, otherwise a collection
+    of names drawn from OPT_IN_TOKENS (a config's `deformable: [deform, deform_graph]`)"""
+    if deformable is None or isinstance(deformable, bool):
+        return frozenset(('deform',)) if deformable else frozenset()
+    if isinstance(deformable, str) or not hasattr(deformable, '__iter__'):
+        raise ValueError("deformable: a bool or a collection of token names drawn from %s, got %r" % (OPT_IN_TOKENS, deformable))
+    names = list(deformable)
+    for t in names:
+        if t not in OPT_IN_TOKENS:
+            raise ValueError("deformable: unexpected token %r; the opt-in tokens are %s" % (t, ', '.join(OPT_IN_TOKENS)))
+    return frozenset(names)
+
+
 def _tokens(style, what, deformable=False):
-    """'attn-graph' -> ['attn', 'graph']: one token, or one global and one local one (`graph`, or `deform` where deformable)"""
+    """'attn-graph' -> ['attn', 'graph']: one token, or one global and one local one (`graph`, or an opted-in `deform` / `deform_graph`)"""
     tokens = style.split('-')
+    opted = _opted_in(deformable)
     for t in tokens:
-        if t == 'deform' and deformable:
+        if t in opted:
             continue
         if t in UNPORTED_TOKENS:
             raise ValueError("%s %r: the block token %r (a deformable local attention) is not ported; served tokens: %s%s"
@@ -75,7 +102,9 @@ def _tokens(style, what, deformable=False):
 
 
 def _local(token, dim, num_heads, qkv_bias, attn_drop, drop, k, n_group):
-    """the local branch of a token: `graph`, or `deform` (reference models/AdaPoinTr.py:57,170,203)"""
+    """the local branch of a token: `graph`, `deform` or `deform_graph` (reference models/AdaPoinTr.py:57-60,170-173,203-206)"""
+    if token == 'deform_graph':
+        return improvedDeformableLocalGraphAttention(dim, k=k)
     if token == 'deform':
         return DeformableLocalCrossAttention(dim, num_heads=num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop, k=k,
                                              n_group=n_group)
@@ -358,9 +387,10 @@ class PointTransformerDecoder(nn.Module):
 
 
 def _entry_kwargs(config, deformable):
-    """a stack's config section as keywords; `deformable` from the section itself or, failing that, from the model section"""
+    """a stack's config section as keywords; `deformable` (a bool or a list of token names) from the section itself or, failing that,
+    from the model section"""
     kw = dict(config)
-    kw['deformable'] = bool(config.get('deformable', False) or deformable)
+    kw['deformable'] = config.get('deformable', False) or deformable
     return kw
 
 
@@ -452,7 +482,7 @@ class PCTransformer(nn.Module):
         self.grouper = DGCNN_Grouper(k=16)
         self.pos_embed = nn.Sequential(nn.Linear(in_chans, 128), nn.GELU(), nn.Linear(128, encoder_config.embed_dim))
         self.input_proj = nn.Sequential(nn.Linear(self.grouper.num_features, 512), nn.GELU(), nn.Linear(512, encoder_config.embed_dim))
-        deformable = bool(config.get('deformable', False))          # opt-in: the block token `deform`
+        deformable = config.get('deformable', False)                # opt-in: true (the token `deform`) or a list of token names
         self.encoder = PointTransformerEncoderEntry(encoder_config, deformable=deformable)
         self.increase_dim = nn.Sequential(nn.Linear(encoder_config.embed_dim, 1024), nn.GELU(), nn.Linear(1024, global_feature_dim))
         self.coarse_pred = nn.Sequential(nn.Linear(global_feature_dim, 1024), nn.GELU(), nn.Linear(1024, 3 * query_num))

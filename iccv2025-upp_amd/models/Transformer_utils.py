@@ -14,6 +14,10 @@ reference's, so its checkpoints load with strict=True.
     DeformableLocalCrossAttention           the deformable local attention (block token `deform`): the offset head and the key / value
                                             projections taken through the gather as per-point products, HF.deform_offset, HF.three_nn and
                                             HF.deform_attention -- no (B, N, k, C) tensor (README "Deformable local cross-attention")
+    improvedDeformableLocalCrossAttention   the same with the offset scaled to the local ball: HF.deform_offset(ball=True)
+    improvedDeformableLocalGraphAttention   the deformable graph feature (block token `deform_graph`): the ball-scaled offset head with
+                                            G = 1, HF.three_nn and HF.interp_edge_max -- max over the slots of three interpolated rows
+                                            plus the query half, no (B, N, k, C) tensor (README "Deformable graph attention")
     DeformableAttnBlock, DeformableAttnDecoderBlock   the reference's fixed layouts around it
 The fused attention path is taken for HIP f32 tensors with head_dim 64, N <= HF.ATTN_MAX_L and no active attention dropout; otherwise
 the same module runs the torch formulation, and a HIP tensor that was declined is recorded by HF.note_declined.
@@ -22,9 +26,8 @@ Deliberate deviation (README "Denoising-query attention and the AdaPoinTr blocks
 topk(sorted=False) of |a|^2 + |b|^2 - 2ab; here the set is the library's ascending (distance, index) on the direct squared distance.  The
 sets agree wherever the k-th and (k+1)-th distances differ by more than rounding, and the order inside a set does not matter under the max.
 
-Not ported: DeformableLocalAttention, improvedDeformableLocalCrossAttention, improvedDeformableLocalGraphAttention (the block tokens
-rw_deform and deform_graph, and the `improved` variant of deform) and the other fixed-layout Block / DecoderBlock variants of the
-reference file, which models/AdaPoinTr.py does not use."""
+Not ported: DeformableLocalAttention (the block token rw_deform, a k x k attention per query) and the other fixed-layout Block /
+DecoderBlock variants of the reference file, which models/AdaPoinTr.py does not use."""
 import torch
 import torch.nn as nn
 
@@ -160,6 +163,8 @@ class DeformableLocalCrossAttention(nn.Module):
     (upp_hip.torch_cpu.deform_offset / deform_attention, which keep the (B,N,k,C) tensors) runs and a HIP tensor that was declined is
     recorded by HF.note_declined.  The neighbour set is the library's ascending (distance, index), as for the other modules."""
 
+    ball = False        # improvedDeformableLocalCrossAttention: the offset is scaled by half the extent of the k listed positions
+
     def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_drop=0., proj_drop=0., k=10, n_group=2):
         super().__init__()
         if dim % num_heads or dim % n_group or num_heads % n_group:
@@ -207,7 +212,7 @@ class DeformableLocalCrossAttention(nn.Module):
             A = torch.stack([HF.linear(vg[g], Wa) for g in range(G)], dim=1)                    # (B,G,NK,C)
             Bq = torch.stack([HF.linear(qg[g], Wb, lin0.bias) for g in range(G)], dim=1)        # (B,G,N,C)
             pos = v_pos.detach().contiguous()
-            shift = HF.deform_offset(A, Bq, idx, pos, ln.weight, ln.bias, ln.eps, self.linear_offset[3].weight)
+            shift = HF.deform_offset(A, Bq, idx, pos, ln.weight, ln.bias, ln.eps, self.linear_offset[3].weight, ball=self.ball)
             known = pos.unsqueeze(1).expand(-1, G, -1, -1).reshape(B * G, NK, 3)
             dist, idx3 = shifted_three_nn(shift.view(B * G, N * self.k, 3), known)
             w3 = self._weights(dist).view(B, G, N * self.k, 3)
@@ -230,7 +235,7 @@ class DeformableLocalCrossAttention(nn.Module):
             qg = qp.view(B, N, G, c).permute(0, 2, 1, 3)
             A = torch.matmul(vg, lin0.weight[:, :c].t())
             Bq = torch.matmul(qg, lin0.weight[:, c:].t()) + lin0.bias
-            shift = torch_cpu.deform_offset(A, Bq, idx, pos, ln.weight, ln.bias, ln.eps, self.linear_offset[3].weight)
+            shift = torch_cpu.deform_offset(A, Bq, idx, pos, ln.weight, ln.bias, ln.eps, self.linear_offset[3].weight, ball=self.ball)
             known = pos.unsqueeze(1).expand(-1, G, -1, -1).reshape(B * G, NK, 3)
             flat = shift.reshape(B * G, N * self.k, 3)
             dist, idx3 = shifted_three_nn(flat, known)
@@ -272,6 +277,121 @@ class DeformableLocalCrossAttention(nn.Module):
             HF.note_declined("DeformableLocalCrossAttention (%d,%d) x (%d,%d), %d heads, k = %d"
                              % (q.shape[1], self.dim, v.shape[1], self.dim, self.num_heads, self.k),
                              "head_dim != 64 / more than 16 heads / k > 32 / dtype / attention dropout")
+        return self._torch(q, v, v_pos, idx)
+
+
+class improvedDeformableLocalCrossAttention(DeformableLocalCrossAttention):
+    """reference models/Transformer_utils.py:493-621: DeformableLocalCrossAttention whose offsets stay within the local ball --
+    shift = pos[idx] + tanh(.) * 0.5 (max_s pos[idx] - min_s pos[idx]) (HF.deform_offset(ball=True)) -- and, as in the reference, without
+    a denoise_length argument.  forward(q, q_pos, v=None, v_pos=None, idx=None).  The same 15 state-dict keys."""
+
+    ball = True
+
+    def forward(self, q, q_pos, v=None, v_pos=None, idx=None):
+        return super().forward(q, q_pos, v, v_pos, idx)
+
+
+class improvedDeformableLocalGraphAttention(nn.Module):
+    """reference models/Transformer_utils.py:623-775 (block token `deform_graph`): the graph feature of every query over k neighbour
+    slots whose features are interpolated at learned positions, shifted within the local ball.  forward(q (B,N,dim), q_pos (B,N,3),
+    v=None (B,NK,dim), v_pos=None (B,NK,3), idx=None (B,N,k) rows of v, denoise_length=None) -> (B,N,dim); v / v_pos default to q / q_pos
+    (the self form).  With denoise_length = D (self form only; v, v_pos and idx must be None, as the reference asserts) the list is
+    denoise_knn's.  State-dict keys: proj_v_off, linear_offset.{0,1,3}, knn_map.0.
+
+    With linear_offset.0.weight = [Wa | Wb] and knn_map.0.weight = [W1 | W2] (no proj_q, no heads, no channel groups: G = 1):
+        offset head     Linear([v_off[idx] ; q]) = A[idx] + Bq with A = v_off Wa^T over the NK points and Bq = q Wb^T + b over the N
+                        queries (the RAW q); HF.deform_offset(ball=True) does gather, LayerNorm, GELU, the 3-row Linear, tanh, the scale
+                        0.5 (max_s pos[idx] - min_s pos[idx]) and the shift
+        three_nn        HF.three_nn of the shifted positions among v_pos; weights by the reference's own r = 1 / (dist + 1e-8),
+                        r / r.sum(-1) in torch, so that they carry its rounding
+        graph feature   knn_map([f - q ; q]) = W1 f + (W2 - W1) q + b and f = sum_j w3 v[idx3], so y[n,s] = Bq'[n] + sum_j w3[n,s,j]
+                        PW[idx3[n,s,j]] with PW = v W1^T over the NK points and Bq' = q (W2 - W1)^T + b over the N queries;
+                        HF.interp_edge_max gathers, interpolates in registers, takes the max over the slots and applies the LeakyReLU
+    three_nn is not differentiable, so the offset branch -- proj_v_off, linear_offset -- and the positions get no gradient: it runs under
+    no_grad.  The fused path is taken for HIP f32 tensors in the served range (dim a multiple of 64 up to 1024, k <= 32) with
+    upp_layers.POOL_TRACE unset; otherwise the torch formulation (upp_hip.torch_cpu.deform_offset / interp_edge_max, which keep the
+    (B,N,k,C) tensors) runs, and a HIP tensor that was declined is recorded by HF.note_declined.  Under POOL_TRACE the torch formulation
+    records and replays idx3 and the arg of the max.  The neighbour set is the library's ascending (distance, index)."""
+
+    _weights = DeformableLocalCrossAttention._weights
+
+    def __init__(self, dim, k=10):
+        super().__init__()
+        self.dim = dim
+        self.proj_v_off = nn.Linear(dim, dim)
+        self.k = k
+        self.linear_offset = nn.Sequential(nn.Linear(2 * dim, dim), nn.LayerNorm(dim), nn.GELU(), nn.Linear(dim, 3, bias=False))
+        self.knn_map = nn.Sequential(nn.Linear(dim * 2, dim), nn.LeakyReLU(negative_slope=0.2))
+
+    def fusable(self, q, v):
+        """The kernels serve HIP f32 tensors, dim = 64 H <= 1024 and k <= 32."""
+        return (q.is_cuda and v.is_cuda and q.dtype == torch.float32 and v.dtype == torch.float32 and self.dim % 64 == 0
+                and L.POOL_TRACE is None and ops.deform_attn_usable(q.shape[0], q.shape[1], v.shape[1], self.k, self.dim // 64, 1)
+                and ops.interp_max_usable(q.shape[0], q.shape[1], v.shape[1], self.k, self.dim))
+
+    def _fused(self, q, v, v_pos, idx):
+        B, N, C = q.shape
+        lin0, ln, lin, act = self.linear_offset[0], self.linear_offset[1], self.knn_map[0], self.knn_map[1]
+        with torch.no_grad():
+            v_off = HF.linear(v.detach(), self.proj_v_off.weight, self.proj_v_off.bias)
+            A = HF.linear(v_off, lin0.weight[:, :C].contiguous()).unsqueeze(1)                   # (B,1,NK,C)
+            Bq = HF.linear(q.detach(), lin0.weight[:, C:].contiguous(), lin0.bias).unsqueeze(1)  # (B,1,N,C)
+            pos = v_pos.detach().contiguous()
+            shift = HF.deform_offset(A, Bq, idx, pos, ln.weight, ln.bias, ln.eps, self.linear_offset[3].weight, ball=True)
+            dist, idx3 = shifted_three_nn(shift.view(B, N * self.k, 3), pos)
+            w3 = self._weights(dist)
+        W = lin.weight
+        PW = HF.linear(v, W[:, :C].contiguous())
+        Bm = HF.linear(q, W[:, C:] - W[:, :C], lin.bias)
+        return HF.interp_edge_max(PW, Bm, idx3, w3, act.negative_slope)
+
+    def _torch(self, q, v, v_pos, idx):
+        """the same restatement as torch operators, any device and dtype"""
+        B, N, C = q.shape
+        NK = v.shape[1]
+        lin0, ln, lin, act = self.linear_offset[0], self.linear_offset[1], self.knn_map[0], self.knn_map[1]
+        with torch.no_grad():
+            pos = v_pos.detach()
+            A = torch.matmul(self.proj_v_off(v), lin0.weight[:, :C].t()).unsqueeze(1)
+            Bq = (torch.matmul(q, lin0.weight[:, C:].t()) + lin0.bias).unsqueeze(1)
+            shift = torch_cpu.deform_offset(A, Bq, idx, pos, ln.weight, ln.bias, ln.eps, self.linear_offset[3].weight, ball=True)
+            flat = shift.reshape(B, N * self.k, 3)
+            dist, idx3 = shifted_three_nn(flat, pos)
+            if L.POOL_TRACE is not None:
+                # the recorded choice replaces this run's, and the distances follow it (slots beyond NK < 3 points stay at +inf)
+                idx3 = L.trace_idx('deformable_graph.idx3', idx3)
+                near = torch.gather(pos, 1, idx3.long().reshape(B, -1, 1).expand(-1, -1, 3)).view(B, -1, 3, 3)
+                d = (flat.unsqueeze(2) - near).pow(2).sum(-1).sqrt()
+                dist = torch.where(torch.arange(3, device=d.device) < NK, d, torch.full_like(d, float('inf')))
+            w3 = self._weights(dist)
+        W = lin.weight
+        PW = torch.matmul(v, W[:, :C].t())
+        Bm = torch.matmul(q, (W[:, C:] - W[:, :C]).t()) + lin.bias
+        pool = None if L.POOL_TRACE is None else (lambda y: L.max_over(y, 2, 'deformable_graph.max'))
+        return torch_cpu.interp_edge_max(PW, Bm, idx3, w3, act.negative_slope, pool)
+
+    def forward(self, q, q_pos, v=None, v_pos=None, idx=None, denoise_length=None):
+        if denoise_length is not None:
+            if idx is not None:
+                raise ValueError("denoise_length needs the list computed here, but idx is given")
+            if v is not None or v_pos is not None:
+                raise ValueError("denoise_length applies to the self form only, but v / v_pos is given")
+        v = q if v is None else v
+        v_pos = q_pos if v_pos is None else v_pos
+        if q_pos.dim() != 3 or q_pos.size(-1) != 3 or v_pos.dim() != 3 or v_pos.size(-1) != 3:
+            raise ValueError("q_pos and v_pos must be (B, N, 3), got %s and %s" % (tuple(q_pos.shape), tuple(v_pos.shape)))
+        if q.size(-1) != self.dim or v.size(-1) != self.dim:
+            raise ValueError("q and v must have %d channels, got %d and %d" % (self.dim, q.size(-1), v.size(-1)))
+        if idx is None:
+            idx = knn_point(self.k, v_pos, q_pos) if denoise_length is None else denoise_knn(self.k, q_pos, denoise_length)
+        if idx.shape != (q.shape[0], q.shape[1], self.k):
+            raise ValueError("idx must be (B, N, k) = %s, got %s" % ((q.shape[0], q.shape[1], self.k), tuple(idx.shape)))
+        idx = idx.long()
+        if self.fusable(q, v):
+            return self._fused(q, v, v_pos, idx)
+        if q.is_cuda and L.POOL_TRACE is None:
+            HF.note_declined("improvedDeformableLocalGraphAttention (%d,%d) x (%d,%d), k = %d" % (q.shape[1], self.dim, v.shape[1], self.dim, self.k),
+                             "dim not a multiple of 64 / beyond 1024 / k > 32 / dtype")
         return self._torch(q, v, v_pos, idx)
 
 

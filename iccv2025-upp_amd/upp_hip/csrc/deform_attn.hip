@@ -2,7 +2,8 @@
 // cross-attention"; reference models/Transformer_utils.py:269-491).  What is left of the module after its per-point products is
 // gather-bound and has no GEMM in it:
 //   da_offset_kernel   shift = pos[idx] + tanh(W3 gelu(LayerNorm(A[idx] + Bq))): one wave per (b, g, n, s) row, the C = 64 H values of
-//                      the row in H registers per lane (channel = 64 i + lane), nothing but the three coordinates stored
+//                      the row in H registers per lane (channel = 64 i + lane), nothing but the three coordinates stored; <true> scales
+//                      the tanh by half the extent of the k listed positions (the `improved` modules: deformable within a local ball)
 //   da_fwd_kernel      one wave per (b, n, head), lane = channel of the head: the key and value rows of a neighbour slot are 3 G
 //                      weighted 256-byte row reads each and live in registers only; scores by a wave sum, softmax over the <= 32 slots
 //                      on the lanes, ctx by an fma chain over the slots
@@ -23,7 +24,10 @@ __device__ __forceinline__ int da_wave() { return __builtin_amdgcn_readfirstlane
 __device__ __forceinline__ float da_lane(float v, int l) { return __uint_as_float(readlane_u32(__float_as_uint(v), l)); }
 
 // blockIdx.x * 4 + wave = row (b, g, n, s), grid-stride.  LayerNorm: biased variance, two passes over the registers; every sum is the
-// lane's partial over its H channels in ascending channel, then wave_sum_f32's fixed tree.
+// lane's partial over its H channels in ascending channel, then wave_sum_f32's fixed tree.  kBall (upp_deform_offset_ball_fwd): the tanh is
+// scaled by half the extent of the k listed positions of (b, n), whose slots sit on lanes 0 ... k-1; one slot outside the cloud and
+// every row of that (b, n) is NaN.
+template <bool kBall>
 __global__ __launch_bounds__(256) void da_offset_kernel(const float *__restrict__ A, const float *__restrict__ Bq, const long long *__restrict__ idx,
                                                         const float *__restrict__ pos, const float *__restrict__ gamma,
                                                         const float *__restrict__ beta, const float *__restrict__ W3, float *__restrict__ shift,
@@ -47,8 +51,19 @@ __global__ __launch_bounds__(256) void da_offset_kernel(const float *__restrict_
         const int n = (int)(t % N);
         const long long bg = t / N, b = bg / G;
         const long long j0 = idx[(b * N + n) * k + s];
-        const bool valid = (unsigned long long)j0 < (unsigned long long)NK;      // (a row outside the cloud is never read through)
+        bool valid = (unsigned long long)j0 < (unsigned long long)NK;            // (a row outside the cloud is never read through)
         const long long j = valid ? j0 : 0;
+        float half = 1.0f;                                                       // lane d < 3: 0.5 (max_s - min_s) of coordinate d
+        if (kBall) {
+            const long long jl0 = idx[(b * N + n) * k + min(lane, k - 1)];
+            const bool ok = (unsigned long long)jl0 < (unsigned long long)NK;
+            valid = __ballot(!ok) == 0;
+            const float *pl = pos + (b * NK + (ok ? jl0 : 0)) * 3;
+            const float r0 = wave_max_f32(pl[0]) - -wave_max_f32(-pl[0]);        // (the lanes beyond k repeat slot k - 1)
+            const float r1 = wave_max_f32(pl[1]) - -wave_max_f32(-pl[1]);
+            const float r2 = wave_max_f32(pl[2]) - -wave_max_f32(-pl[2]);
+            half = __fmul_rn(0.5f, lane == 0 ? r0 : (lane == 1 ? r1 : r2));
+        }
         const float *a = A + (bg * NK + j) * C, *bq = Bq + (bg * N + n) * C;
         float y[kDaMaxH], part = 0.0f;
 #pragma unroll
@@ -77,7 +92,8 @@ __global__ __launch_bounds__(256) void da_offset_kernel(const float *__restrict_
         d2 = wave_sum_f32(d2);
         if (lane < 3) {
             const float d = lane == 0 ? d0 : (lane == 1 ? d1 : d2);
-            shift[row * 3 + lane] = valid ? pos[(b * NK + j) * 3 + lane] + tanhf(d) : __builtin_nanf("");
+            const float off = kBall ? __fmul_rn(tanhf(d), half) : tanhf(d);
+            shift[row * 3 + lane] = valid ? __fadd_rn(pos[(b * NK + j) * 3 + lane], off) : __builtin_nanf("");
         }
     }
 }
@@ -255,19 +271,36 @@ static int da_bwd(bool det, const float *q, const float *PK, const float *PV, co
     return upp_launch_status();
 }
 
-}  // namespace
-
-extern "C" int upp_deform_offset_fwd(const float *A, const float *Bq, const int64_t *idx, const float *pos, const float *gamma,
-                                     const float *beta, const float *W3, float *shift, float eps, int B, int G, int N, int NK, int k, int C,
-                                     void *stream) {
+static int da_offset(bool ball, const float *A, const float *Bq, const int64_t *idx, const float *pos, const float *gamma, const float *beta,
+                     const float *W3, float *shift, float eps, int B, int G, int N, int NK, int k, int C, void *stream) {
     if (!A || !Bq || !idx || !pos || !gamma || !beta || !W3 || !shift || !da_positive(eps) || C < 1) return UPP_E_BADARG;
     if (C % 64) return UPP_E_RANGE;
     const int rc = da_sizes(B, N, NK, k, C / 64, G);
     if (rc) return rc;
     const long long rows = (long long)B * G * N * k;
-    hipLaunchKernelGGL(da_offset_kernel, dim3(grid_for(rows, kDaWaves, kDaGridCap)), dim3(256), 0, (hipStream_t)stream, A, Bq,
-                       reinterpret_cast<const long long *>(idx), pos, gamma, beta, W3, shift, eps, G, N, NK, k, C / 64, rows);
+    const dim3 grid(grid_for(rows, kDaWaves, kDaGridCap));
+    const long long *list = reinterpret_cast<const long long *>(idx);
+    if (ball)
+        hipLaunchKernelGGL(da_offset_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, A, Bq, list, pos, gamma, beta, W3, shift, eps, G, N,
+                           NK, k, C / 64, rows);
+    else
+        hipLaunchKernelGGL(da_offset_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, A, Bq, list, pos, gamma, beta, W3, shift, eps, G, N,
+                           NK, k, C / 64, rows);
     return upp_launch_status();
+}
+
+}  // namespace
+
+extern "C" int upp_deform_offset_fwd(const float *A, const float *Bq, const int64_t *idx, const float *pos, const float *gamma,
+                                     const float *beta, const float *W3, float *shift, float eps, int B, int G, int N, int NK, int k, int C,
+                                     void *stream) {
+    return da_offset(false, A, Bq, idx, pos, gamma, beta, W3, shift, eps, B, G, N, NK, k, C, stream);
+}
+
+extern "C" int upp_deform_offset_ball_fwd(const float *A, const float *Bq, const int64_t *idx, const float *pos, const float *gamma,
+                                          const float *beta, const float *W3, float *shift, float eps, int B, int G, int N, int NK, int k,
+                                          int C, void *stream) {
+    return da_offset(true, A, Bq, idx, pos, gamma, beta, W3, shift, eps, B, G, N, NK, k, C, stream);
 }
 
 extern "C" int upp_deform_attn_fwd(const float *q, const float *PK, const float *PV, const float *bk, const float *bv, const int32_t *idx3,

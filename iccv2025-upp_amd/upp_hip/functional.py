@@ -585,22 +585,24 @@ def deform_attention_usable(q, PK, PV, idx3, w3, num_heads):
     return ops.deform_attn_usable(B, N, NK, idx3.shape[2] // N, H, G)
 
 
-def deform_offset(A, Bq, idx, pos, gamma, beta, eps, W3):
+def deform_offset(A, Bq, idx, pos, gamma, beta, eps, W3, ball=False):
     """A (B,G,NK,C) and Bq (B,G,N,C) the per-point halves of the offset head's first Linear, idx (B,N,k) int64 (HF.knn_query's list),
     pos (B,NK,3), LayerNorm gamma / beta (C) and eps, W3 (3,C) -> shift (B,G,N k,3) = pos[idx] + tanh(W3 gelu(LayerNorm(A[idx] + Bq))).
-    No autograd node: it runs under no_grad (three_nn, its only consumer, is not differentiable).  HIP tensors outside the served range
-    (C = 64 H, H <= 16, k <= 32) take the torch formulation (note_declined records it); CPU tensors take it when upp_hip.torch_cpu is
-    enabled."""
+    ball: the tanh is scaled by 0.5 (max_s pos[idx] - min_s pos[idx]) over the k slots of the query (upp_deform_offset_ball_fwd, the
+    `improved` modules).  No autograd node: it runs under no_grad (three_nn, its only consumer, is not differentiable).  HIP tensors
+    outside the served range (C = 64 H, H <= 16, k <= 32) take the torch formulation (note_declined records it); CPU tensors take it
+    when upp_hip.torch_cpu is enabled."""
     from . import torch_cpu
+    ball = bool(ball)
     with torch.no_grad():
         if _torch_cpu(A, Bq, idx, pos):
-            return torch_cpu.deform_offset(A, Bq, idx, pos, gamma, beta, eps, W3)
+            return torch_cpu.deform_offset(A, Bq, idx, pos, gamma, beta, eps, W3, ball)
         if A.is_cuda and not (_deform_f32(A, Bq, pos, gamma, beta, W3) and A.dim() == 4 and A.shape[3] % 64 == 0 and idx.dim() == 3 and
                               ops.deform_attn_usable(A.shape[0], idx.shape[1], A.shape[2], idx.shape[2], A.shape[3] // 64, A.shape[1])):
             note_declined("deform_offset A %s, k = %d" % (tuple(A.shape), idx.shape[-1]), "outside the served range")
-            return torch_cpu.deform_offset(A, Bq, idx, pos, gamma, beta, eps, W3)
+            return torch_cpu.deform_offset(A, Bq, idx, pos, gamma, beta, eps, W3, ball)
         return ops.deform_offset_fwd(A.contiguous(), Bq.contiguous(), idx.long().contiguous(), pos.contiguous(), gamma.contiguous(),
-                                     beta.contiguous(), W3.contiguous(), float(eps))
+                                     beta.contiguous(), W3.contiguous(), float(eps), ball)
 
 
 def deform_attention(q, PK, PV, bk, bv, idx3, w3, num_heads, scale, deterministic=None):
@@ -619,6 +621,60 @@ def deform_attention(q, PK, PV, bk, bv, idx3, w3, num_heads, scale, deterministi
     return _DeformAttention.apply(q.contiguous(), PK.contiguous(), PV.contiguous(), None if bk is None else bk.contiguous(),
                                   None if bv is None else bv.contiguous(), idx3.contiguous(), w3.detach().contiguous(), int(num_heads),
                                   float(scale), None if deterministic is None else bool(deterministic))
+
+
+# ------------------------------------------------------------------ deformable graph attention (README section of that name)
+class _InterpEdgeMax(Function):
+    """lrelu(max_s (Bq + sum_j w3 PW[idx3])) as one node (include/upp_hip.h "deformable graph attention"): saves out, the arg bytes, idx3
+    and w3 -- never a (B,N,k,O) tensor, and no row is read again in the backward.  The d_PW scatter-add follows the deterministic mode:
+    `det` None reads DETERMINISTIC when the backward runs, True / False fixes it for this call.  idx3 and w3 get no gradient."""
+
+    @staticmethod
+    def forward(ctx, PW, Bq, idx3, w3, slope, det):
+        out, arg = ops.interp_max_fwd(PW, Bq, idx3, w3, slope)
+        ctx.save_for_backward(out, arg, idx3, w3)
+        ctx.cfg = (PW.shape[1], slope, det)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        out, arg, idx3, w3 = ctx.saved_tensors
+        NK, slope, det = ctx.cfg
+        d_Bq, d_PW = ops.interp_max_bwd(g.contiguous(), out, arg, idx3, w3, NK, slope,
+                                        deterministic=DETERMINISTIC if det is None else det)
+        need = ctx.needs_input_grad
+        return d_PW if need[0] else None, d_Bq if need[1] else None, None, None, None, None
+
+
+def interp_edge_max_usable(PW, Bq, idx3, w3):
+    """Do the fused kernels serve these operands (HIP f32 / int32 tensors of the served sizes of include/upp_hip.h)?"""
+    if not (_deform_f32(PW, Bq, w3) and isinstance(idx3, torch.Tensor) and idx3.is_cuda and idx3.dtype == torch.int32):
+        return False
+    if PW.dim() != 3 or Bq.dim() != 3 or idx3.dim() != 3 or idx3.shape != w3.shape or idx3.shape[2] != 3:
+        return False
+    B, N, O = Bq.shape
+    if N < 1 or idx3.shape[0] != B or idx3.shape[1] % N or PW.shape[0] != B or PW.shape[2] != O:
+        return False
+    return ops.interp_max_usable(B, N, PW.shape[1], idx3.shape[1] // N, O)
+
+
+def interp_edge_max(PW, Bq, idx3, w3, slope=0.2, deterministic=None):
+    """PW (B,NK,O) the key-side product of the memory points, Bq (B,N,O) the query-side product (+ bias), idx3 int32 and w3 f32
+    (B, N k, 3) (three_nn of the shifted positions and the reference's weights) -> (B,N,O) = leaky_relu(max_s (Bq[b,n] +
+    sum_j w3[b,n k+s,j] PW[b, idx3[b,n k+s,j]]), slope) (include/upp_hip.h "deformable graph attention").  PW and Bq get gradients, idx3
+    and w3 none.  deterministic: None follows functional.DETERMINISTIC (read when the backward node runs), True / False per call.  HIP
+    tensors outside the served range (k <= 32, O <= 1024) take the torch formulation (note_declined records it); CPU tensors take it
+    when upp_hip.torch_cpu is enabled."""
+    if not 0.0 <= float(slope) <= 1.0:
+        raise ValueError("interp_edge_max: slope must be in [0, 1]")
+    from . import torch_cpu
+    if _torch_cpu(PW, Bq, idx3, w3):
+        return torch_cpu.interp_edge_max(PW, Bq, idx3, w3, slope)
+    if PW.is_cuda and not interp_edge_max_usable(PW, Bq, idx3, w3):
+        note_declined("interp_edge_max PW %s, Bq %s, idx3 %s" % (tuple(PW.shape), tuple(Bq.shape), tuple(idx3.shape)), "outside the served range")
+        return torch_cpu.interp_edge_max(PW, Bq, idx3, w3, slope)
+    return _InterpEdgeMax.apply(PW.contiguous(), Bq.contiguous(), idx3.contiguous(), w3.detach().contiguous(), float(slope),
+                                None if deterministic is None else bool(deterministic))
 
 
 def _expand_norm(norm):

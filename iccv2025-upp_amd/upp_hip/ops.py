@@ -776,9 +776,10 @@ def _positive(who, name, v):
     return v
 
 
-def deform_offset_fwd(A, Bq, idx, pos, gamma, beta, W3, eps):
+def deform_offset_fwd(A, Bq, idx, pos, gamma, beta, W3, eps, ball=False):
     """A (B,G,NK,C), Bq (B,G,N,C), idx (B,N,k) int64, pos (B,NK,3), gamma / beta (C), W3 (3,C) -> shift (B,G,N k,3) =
-    pos[idx] + tanh(W3 gelu(LayerNorm(A[idx] + Bq))): upp_deform_offset_fwd, 1 launch, no (B,G,N,k,C) tensor."""
+    pos[idx] + tanh(W3 gelu(LayerNorm(A[idx] + Bq))): upp_deform_offset_fwd, 1 launch, no (B,G,N,k,C) tensor.  ball: the tanh is scaled by
+    0.5 (max_s pos[idx] - min_s pos[idx]) over the k slots of the query (upp_deform_offset_ball_fwd)."""
     _need(A, "A", torch.float32, 4)
     B, G, NK, C = A.shape
     _need(Bq, "Bq", torch.float32, 4)
@@ -799,8 +800,8 @@ def deform_offset_fwd(A, Bq, idx, pos, gamma, beta, W3, eps):
     _deform_sizes("deform_offset", B, N, NK, k, C // 64, G)
     _aligned16("deform_offset", A=A, Bq=Bq, idx=idx, pos=pos, gamma=gamma, beta=beta, W3=W3)
     shift = torch.empty((B, G, N * k, 3), dtype=torch.float32, device=A.device)
-    _call(A.device, "upp_deform_offset_fwd", _abi.ptr(A), _abi.ptr(Bq), _abi.ptr(idx), _abi.ptr(pos), _abi.ptr(gamma), _abi.ptr(beta),
-          _abi.ptr(W3), _abi.ptr(shift), eps, B, G, N, NK, k, C)
+    _call(A.device, "upp_deform_offset_ball_fwd" if ball else "upp_deform_offset_fwd", _abi.ptr(A), _abi.ptr(Bq), _abi.ptr(idx), _abi.ptr(pos),
+          _abi.ptr(gamma), _abi.ptr(beta), _abi.ptr(W3), _abi.ptr(shift), eps, B, G, N, NK, k, C)
     return shift
 
 
@@ -858,6 +859,70 @@ def deform_attn_bwd(q, PK, PV, bk, bv, idx3, w3, p, d_ctx, H, scale, determinist
           _abi.ptr(bv), _abi.ptr(idx3), _abi.ptr(w3), _abi.ptr(p), _abi.ptr(d_ctx), _abi.ptr(d_q), _abi.ptr(d_PK), _abi.ptr(d_PV),
           _abi.ptr(d_krow), _abi.ptr(ds), scale, B, N, NK, k, H, G)
     return d_q, d_PK, d_PV, ds, d_krow
+
+
+# ------------------------------------------------------------------ deformable graph attention (include/upp_hip.h)
+INTERP_MAX_K, INTERP_MAX_O = 32, 1024
+
+
+def interp_max_usable(B, N, NK, k, O):
+    """The served range of upp_interp_max_fwd / _bwd / _bwd_det (sizes only)."""
+    if min(B, N, NK, k, O) < 1 or k > INTERP_MAX_K or O > INTERP_MAX_O or B > 65535:
+        return False
+    return max(B * NK * O, B * N * O, B * N * k * 3) < 2 ** 31
+
+
+def _interp_max_args(who, a, a_name, b, b_name, idx3, w3, slope, NK=None):
+    """a (B,NK,O) for the forward (NK None) or (B,N,O) for the backward, b (B,N,O), idx3 / w3 (B, N k, 3) -> B, N, NK, k, O, slope"""
+    _need(a, a_name, torch.float32, 3)
+    _need(b, b_name, torch.float32, 3)
+    B, N, O = b.shape
+    NK = a.shape[1] if NK is None else int(NK)
+    _need_f32(a, a_name, (B, a.shape[1], O))
+    _need(idx3, "idx3", torch.int32, 3, 3)
+    _need(w3, "w3", torch.float32, 3, 3)
+    if idx3.shape != w3.shape or idx3.shape[0] != B or N < 1 or idx3.shape[1] % N:
+        raise RuntimeError("%s: idx3 and w3 must both be (B, N k, 3) = (%d, %d k, 3), got %s and %s"
+                           % (who, B, N, tuple(idx3.shape), tuple(w3.shape)))
+    k = idx3.shape[1] // N
+    _same_device(a, b, idx3, w3)
+    slope = float(slope)
+    if not 0.0 <= slope <= 1.0:
+        raise RuntimeError("%s: slope must be in [0, 1], got %r (UPP_E_BADARG)" % (who, slope))
+    if min(B, N, NK, k, O) < 1:
+        raise RuntimeError("%s: every size must be positive, got B = %d, N = %d, NK = %d, k = %d, O = %d" % (who, B, N, NK, k, O))
+    if not interp_max_usable(B, N, NK, k, O):
+        raise RuntimeError("%s: B = %d, N = %d, NK = %d, k = %d, O = %d is outside the served range 1 <= k <= %d, 1 <= O <= %d, B <= 65535, "
+                           "every array below 2^31 elements (UPP_E_RANGE)" % (who, B, N, NK, k, O, INTERP_MAX_K, INTERP_MAX_O))
+    _aligned16(who, **{a_name: a, b_name: b, "idx3": idx3, "w3": w3})
+    return B, N, NK, k, O, slope
+
+
+def interp_max_fwd(PW, Bq, idx3, w3, slope=0.2):
+    """PW (B,NK,O), Bq (B,N,O), idx3 int32 and w3 (B, N k, 3) -> out (B,N,O) = lrelu(max_s (Bq + sum_j w3 PW[idx3])), arg (B,N,O) uint8:
+    upp_interp_max_fwd, 1 launch, no (B,N,k,O) tensor."""
+    B, N, NK, k, O, slope = _interp_max_args("interp_edge_max", PW, "PW", Bq, "Bq", idx3, w3, slope)
+    out = torch.empty((B, N, O), dtype=torch.float32, device=PW.device)
+    arg = torch.empty((B, N, O), dtype=torch.uint8, device=PW.device)
+    _call(PW.device, "upp_interp_max_fwd", _abi.ptr(PW), _abi.ptr(Bq), _abi.ptr(idx3), _abi.ptr(w3), _abi.ptr(out), _abi.ptr(arg), slope,
+          B, N, NK, k, O)
+    return out, arg
+
+
+def interp_max_bwd(g_out, out, arg, idx3, w3, NK, slope=0.2, deterministic=False):
+    """g_out, out (B,N,O), arg (B,N,O) uint8 -> d_Bq (B,N,O), d_PW (B,NK,O).  d_PW by f32 atomics into an array the entry point zeroes with
+    a kernel (upp_interp_max_bwd) or, deterministic, in ascending 3 n + j (upp_interp_max_bwd_det, include/upp_hip.h)."""
+    B, N, NK, k, O, slope = _interp_max_args("interp_edge_max_bwd", g_out, "g_out", out, "out", idx3, w3, slope, NK=NK)
+    _need(arg, "arg", torch.uint8, 3)
+    if tuple(g_out.shape) != (B, N, O) or tuple(arg.shape) != (B, N, O):
+        raise RuntimeError("interp_edge_max_bwd: g_out and arg must be (B, N, O) = %s" % ((B, N, O),))
+    _same_device(g_out, arg)
+    _aligned16("interp_edge_max_bwd", arg=arg)
+    d_Bq = torch.empty((B, N, O), dtype=torch.float32, device=g_out.device)
+    d_PW = torch.empty((B, NK, O), dtype=torch.float32, device=g_out.device)
+    _call(g_out.device, "upp_interp_max_bwd_det" if deterministic else "upp_interp_max_bwd", _abi.ptr(g_out), _abi.ptr(out), _abi.ptr(arg),
+          _abi.ptr(idx3), _abi.ptr(w3), _abi.ptr(d_Bq), _abi.ptr(d_PW), slope, B, N, NK, k, O)
+    return d_Bq, d_PW
 
 
 # ------------------------------------------------------------------ Chamfer

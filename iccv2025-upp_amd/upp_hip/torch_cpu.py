@@ -254,10 +254,11 @@ def prefix_attention(q, k, v, num_heads, scale, split_q, split_k):
     return (attn @ vh).transpose(1, 2).reshape(B, Lq, C)
 
 
-def deform_offset(A, Bq, idx, pos, gamma, beta, eps, W3):
+def deform_offset(A, Bq, idx, pos, gamma, beta, eps, W3, ball=False):
     """The offset head of include/upp_hip.h "deformable local cross-attention" as torch operators (any device and dtype): A (B,G,NK,C),
     Bq (B,G,N,C), idx (B,N,k) rows of the NK points, pos (B,NK,3), LayerNorm gamma / beta (C) and eps, W3 (3,C) -> shift (B,G,N k,3) =
-    pos[idx] + tanh(W3 gelu(LayerNorm(A[idx] + Bq))).  It keeps the (B,G,N,k,C) tensor the kernel avoids."""
+    pos[idx] + tanh(W3 gelu(LayerNorm(A[idx] + Bq))).  ball ("deformable graph attention"): the tanh is scaled by
+    0.5 (max_s pos[idx] - min_s pos[idx]) over the k slots of the query.  It keeps the (B,G,N,k,C) tensor the kernel avoids."""
     import torch.nn.functional as F
     B, G, NK, C = A.shape
     N, k = idx.shape[1], idx.shape[2]
@@ -266,7 +267,28 @@ def deform_offset(A, Bq, idx, pos, gamma, beta, eps, W3):
     h = F.gelu(F.layer_norm(y, (C,), gamma, beta, float(eps)))
     off = torch.tanh(torch.matmul(h, W3.t()))                                          # (B,G,N,k,3)
     local = torch.gather(pos, 1, flat.view(B, N * k, 1).expand(-1, -1, 3)).view(B, 1, N, k, 3)
+    if ball:
+        off = off * ((local.max(dim=3, keepdim=True)[0] - local.min(dim=3, keepdim=True)[0]) * 0.5)
     return (local + off).reshape(B, G, N * k, 3)
+
+
+def interp_edge_max(PW, Bq, idx3, w3, slope=0.2, pool=None):
+    """The interpolate-max of include/upp_hip.h "deformable graph attention" as torch operators (any device and dtype; differentiable in
+    PW and Bq): PW (B,NK,O), Bq (B,N,O), idx3 and w3 (B, N k, 3) -> (B,N,O) = leaky_relu(max_s (Bq + sum_j w3 PW[idx3])), j ascending; an
+    index outside [0, NK) contributes nothing.  pool: None, or a callable y (B,N,k,O) -> (B,N,O) that takes the place of y.max(2)[0] (the
+    modules' arg-max instrument).  It keeps the (B,N,k,O) tensor the kernels avoid."""
+    import torch.nn.functional as F
+    B, N, O = Bq.shape
+    NK = PW.shape[1]
+    k = idx3.shape[1] // N
+    i = idx3.long()
+    inside = ((i >= 0) & (i < NK)).unsqueeze(-1)
+    rows = torch.gather(PW, 1, i.clamp(0, NK - 1).reshape(B, N * k * 3, 1).expand(-1, -1, O)).view(B, N * k, 3, O)
+    t = torch.where(inside, rows * w3.detach().unsqueeze(-1), torch.zeros((), dtype=PW.dtype, device=PW.device))
+    y = Bq.unsqueeze(2)
+    for j in range(3):
+        y = y + t[:, :, j].view(B, N, k, O)
+    return F.leaky_relu(y.max(dim=2)[0] if pool is None else pool(y), float(slope))
 
 
 def deform_attention(q, PK, PV, bk, bv, idx3, w3, num_heads, scale, drop=None):

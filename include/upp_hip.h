@@ -408,6 +408,50 @@ int upp_deform_attn_bwd_det(const float *q, const float *PK, const float *PV, co
                             const float *w3, const float *p, const float *d_ctx, float *d_q, float *d_PK, float *d_PV, float *d_krow,
                             float *ds, float scale, int B, int N, int NK, int k, int H, int G, void *stream);
 
+/* ---- deformable graph attention: the ball-scaled offset head and the interpolate-max (additions to ABI 5) --------------------------
+ * What is left of improvedDeformableLocalGraphAttention (reference models/Transformer_utils.py:623-775) once its Linear layers are
+ * taken through the gather (README "Deformable graph attention"), and the offset head of improvedDeformableLocalCrossAttention
+ * (:493-621).  O channels, k neighbour slots, N queries, NK memory points.
+ *
+ * upp_deform_offset_ball_fwd (forward only)
+ *   The operands, shapes, limits, error codes, mapping and reduction order of upp_deform_offset_fwd; only the last step differs.  With
+ *   j_s = idx[b,n,s]:  r[d] = max_s pos[b,j_s,d] - min_s pos[b,j_s,d] over the k slots of (b,n), one f32 subtraction;
+ *   shift = pos[b,j,d] + (tanh(.) * (0.5f * r[d])), each operation rounded once, none contracted.  A slot outside [0, NK) makes every
+ *   row of its (b,n) NaN and is never read through.  k == 1 gives r = 0 and shift = pos[idx] exactly.  1 launch.
+ *
+ * upp_interp_max_fwd
+ *   PW (B,NK,O) the key-side product of the memory points, Bq (B,N,O) the query-side product (+ bias); idx3 int32 and w3 f32
+ *   (B, N k, 3): the three nearest memory points of every shifted position and their interpolation weights; slope of the LeakyReLU
+ *   -> per (b,n,o), for every slot s:  y_s = Bq[b,n,o], then y_s = fma(w3[b,n k + s,j], PW[b,idx3[b,n k + s,j],o], y_s) for ascending
+ *      j; an index outside [0, NK) contributes nothing (never read through).  m = max_s y_s, arg[b,n,o] = the lowest s that attains it
+ *      (a NaN never wins; no y above -inf leaves m = -inf and arg 0, as the norm-free upp_edge_conv_fwd);  out = m > 0 ? m : m * slope.
+ *      out (B,N,O) f32 and arg (B,N,O) uint8.  y is never stored.  One wave per (b, n, chunk of 64 channels), lane = channel: every
+ *      row read is one coalesced 256-byte segment.  No atomics, nothing zeroed, deterministic.  1 launch.
+ *
+ * upp_interp_max_bwd / upp_interp_max_bwd_det
+ *   g_out, out (B,N,O), arg, idx3, w3 -> d_Bq (B,N,O), d_PW (B,NK,O).  g = g_out * (m > 0 ? 1 : slope), where the sign of m is read
+ *   off OUT (out > 0 exactly where m > 0, for every slope in [0, 1]): no row is read again.  d_Bq[b,n,o] = g, written once.
+ *   d_PW[b, idx3[b, n k + arg, j], o] += w3[b, n k + arg, j] * g, the product rounded once (an arg beyond k - 1 counts as k - 1; an
+ *   index outside [0, NK) is skipped).  w3 and idx3 get no gradient.
+ *      upp_interp_max_bwd: d_PW is zeroed here by a kernel (no memset) and summed by f32 atomics in the order the hardware retires
+ *      them: 2 launches + the zero fill.
+ *      upp_interp_max_bwd_det: d_PW[b,r,o] = +0.0f, then + the rounded product of every source (n, j) with
+ *      idx3[b, n k + arg[b,n,o], j] == r in ascending 3 n + j, one rounded addition each; a job of the one `_det` kernel body
+ *      (csrc/det_scan.h).  The walk that was built: ALL (n k + s) 3 + j sources of the cloud in ascending order, a channel whose arg is
+ *      another slot contributing +0.0f (x + 0.0f == x from a +0.0f start: the same bits), a source that none of the workgroup's
+ *      channels chose taking no part.  Every element is overwritten: nothing to zero.  2 launches.
+ *
+ * Limits (interpolate-max): 1 <= k <= 32, 1 <= O <= 1024, N, NK >= 1, B <= 65535 and every array below 2^31 elements -- UPP_E_RANGE
+ *   beyond.  A null pointer, a non-positive size, a slope outside [0, 1] or not finite: UPP_E_BADARG.  Both before any launch. */
+int upp_deform_offset_ball_fwd(const float *A, const float *Bq, const int64_t *idx, const float *pos, const float *gamma, const float *beta,
+                               const float *W3, float *shift, float eps, int B, int G, int N, int NK, int k, int C, void *stream);
+int upp_interp_max_fwd(const float *PW, const float *Bq, const int32_t *idx3, const float *w3, float *out, uint8_t *arg, float slope,
+                       int B, int N, int NK, int k, int O, void *stream);
+int upp_interp_max_bwd(const float *g_out, const float *out, const uint8_t *arg, const int32_t *idx3, const float *w3, float *d_Bq,
+                       float *d_PW, float slope, int B, int N, int NK, int k, int O, void *stream);
+int upp_interp_max_bwd_det(const float *g_out, const float *out, const uint8_t *arg, const int32_t *idx3, const float *w3, float *d_Bq,
+                           float *d_PW, float slope, int B, int N, int NK, int k, int O, void *stream);
+
 /* ---- Chamfer distance ----------------------------------------------------------
  * Replaces chamfer.forward / chamfer.backward (reference
  * extensions/chamfer_dist/chamfer_cuda.cpp:36-39, kernels chamfer.cu:15-145 and
@@ -481,7 +525,8 @@ int upp_emd_matchcost_bwd(const float *grad_cost, const float *xyz1, const float
  *                           in ascending p * S + s; grad_features needs NO zero-fill (upp_gather_bwd_det on the flattened list).
  *   upp_knn_scatter_add_det stated and declared with its sibling under "the pytorch3d.ops surface" above: ascending l * K + k.
  *   upp_deform_attn_bwd_det stated and declared with its sibling under "deformable local cross-attention" above: ascending
- *                           (n k + s) 3 + j. */
+ *                           (n k + s) 3 + j.
+ *   upp_interp_max_bwd_det  stated and declared with its sibling under "deformable graph attention" above: ascending 3 n + j. */
 int upp_chamfer_bwd_det(const float *xyz1, const float *xyz2, const int32_t *idx1, const int32_t *idx2,
                         const float *grad_dist1, const float *grad_dist2, float *g1, float *g2,
                         int B, int n, int m, void *stream);
