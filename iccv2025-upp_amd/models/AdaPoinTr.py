@@ -10,9 +10,13 @@ the two Point* classes, which PCTransformer and the *Entry classes read from a m
     attn, graph     Attention / CrossAttention, DynamicGraphAttention          always served
     deform          DeformableLocalCrossAttention              deformable=True, or a collection that names it (`deformable: true`)
     deform_graph    improvedDeformableLocalGraphAttention      a collection that names it (`deformable: [deform, deform_graph]`)
-    rw_deform       not ported                                 raises ValueError everywhere
-True means exactly {'deform'}; a name outside ('deform', 'deform_graph') raises ValueError; with the default False every one of the
-three deformable tokens raises ValueError at construction.
+    rw_deform       DeformableLocalAttention                   the separate keyword region_wise=True (`region_wise: true`)
+True means exactly {'deform'}; a name outside ('deform', 'deform_graph') raises ValueError; with the defaults every one of the three
+deformable tokens raises ValueError at construction.  `rw_deform` is a self-attention only: with region_wise=True it is built in
+SelfAttnBlockApi and in CrossAttnBlockApi's self position (k, n_group from the block) and raises ValueError in the cross position, as
+the reference asserts.  The module has no denoising form: in the decoder's self position a non-None denoise_length raises ValueError.
+Deliberate deviation: the reference passes denoise_length to the module unconditionally there and would raise TypeError even for None;
+serving denoise_length=None is this repository's.  `deformable` never opts `rw_deform` in.
     LayerNorm                      HF.layer_norm (the row kernel; eps from the module, 1e-6 in the stacks)
     self-attention                 Transformer_utils.Attention; with denoise_length the fused prefix-visibility kernel -- CrossAttnBlockApi
                                    passes denoise_length on and never builds the reference's (N, N) mask tensor
@@ -21,6 +25,7 @@ three deformable tokens raises ValueError at construction.
     deformable branches            Transformer_utils.DeformableLocalCrossAttention (HF.deform_offset, HF.three_nn, HF.deform_attention)
     deformable graph branches      Transformer_utils.improvedDeformableLocalGraphAttention (HF.deform_offset(ball=True), HF.three_nn,
                                    HF.interp_edge_max)
+    region-wise branches           Transformer_utils.DeformableLocalAttention (HF.deform_offset, HF.three_nn, HF.region_attention)
     merge maps                     HF.linear;  MLPs: upp_layers.Mlp (HF.mlp_gelu)
 TransformerEncoder / TransformerDecoder compute every neighbour list once per forward -- the denoise list included, which the reference
 recomputes inside every block; positions do not change between blocks, so the lists are the same -- and only the lists some block uses.
@@ -60,7 +65,7 @@ from .PoinTr import Fold  # noqa: F401  (the reference's models/AdaPoinTr.py:693
 from .Transformer import conv_bn_act_conv
 from .build import build_model_from_cfg
 from .dgcnn_group import DGCNN_Grouper
-from .Transformer_utils import (Attention, CrossAttention, DeformableLocalCrossAttention, DropPath, DynamicGraphAttention, LayerScale, Mlp,
+from .Transformer_utils import (Attention, CrossAttention, DeformableLocalAttention, DeformableLocalCrossAttention, DropPath, DynamicGraphAttention, LayerScale, Mlp,
                                 denoise_knn, improvedDeformableLocalGraphAttention, knn_point)
 
 SERVED_TOKENS = ('attn', 'graph')
@@ -84,12 +89,17 @@ def _opted_in(deformable):
     return frozenset(names)
 
 
-def _tokens(style, what, deformable=False):
-    """'attn-graph' -> ['attn', 'graph']: one token, or one global and one local one (`graph`, or an opted-in `deform` / `deform_graph`)"""
+def _tokens(style, what, deformable=False, region_wise=False, cross=False):
+    """'attn-graph' -> ['attn', 'graph']: one token, or one global and one local one (`graph`, an opted-in `deform` / `deform_graph`, or
+    -- region_wise, outside the cross position -- `rw_deform`)"""
     tokens = style.split('-')
     opted = _opted_in(deformable)
     for t in tokens:
         if t in opted:
+            continue
+        if t == 'rw_deform' and region_wise:
+            if cross:
+                raise ValueError("%s %r: the block token 'rw_deform' is a self-attention only and cannot serve as a cross-attention" % (what, style))
             continue
         if t in UNPORTED_TOKENS:
             raise ValueError("%s %r: the block token %r (a deformable local attention) is not ported; served tokens: %s%s"
@@ -102,7 +112,9 @@ def _tokens(style, what, deformable=False):
 
 
 def _local(token, dim, num_heads, qkv_bias, attn_drop, drop, k, n_group):
-    """the local branch of a token: `graph`, `deform` or `deform_graph` (reference models/AdaPoinTr.py:57-60,170-173,203-206)"""
+    """the local branch of a token: `graph`, `deform`, `deform_graph` or `rw_deform` (reference models/AdaPoinTr.py:54-60,167-173,203-206)"""
+    if token == 'rw_deform':
+        return DeformableLocalAttention(dim, num_heads=num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop, k=k, n_group=n_group)
     if token == 'deform_graph':
         return improvedDeformableLocalGraphAttention(dim, k=k)
     if token == 'deform':
@@ -134,7 +146,7 @@ class SelfAttnBlockApi(nn.Module):
 
     def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, drop=0., attn_drop=0., init_values=None, drop_path=0.,
                  act_layer=nn.GELU, norm_layer=nn.LayerNorm, block_style='attn-deform', combine_style='concat', k=10, n_group=2,
-                 deformable=False):
+                 deformable=False, region_wise=False):
         super().__init__()
         self.combine_style = _combine_style(combine_style, 'SelfAttnBlockApi')
         self.norm1 = norm_layer(dim)
@@ -143,7 +155,7 @@ class SelfAttnBlockApi(nn.Module):
         self.ls2 = LayerScale(dim, init_values=init_values) if init_values else nn.Identity()
         self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
         self.drop_path2 = DropPath(drop_path) if drop_path > 0. else nn.Identity()
-        tokens = _tokens(block_style, 'block_style', deformable)
+        tokens = _tokens(block_style, 'block_style', deformable, region_wise)
         self.block_length = len(tokens)
         self.attn = None
         self.local_attn = None
@@ -182,7 +194,8 @@ class CrossAttnBlockApi(nn.Module):
 
     def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, drop=0., attn_drop=0., init_values=None, drop_path=0.,
                  act_layer=nn.GELU, norm_layer=nn.LayerNorm, self_attn_block_style='attn-deform', self_attn_combine_style='concat',
-                 cross_attn_block_style='attn-deform', cross_attn_combine_style='concat', k=10, n_group=2, deformable=False):
+                 cross_attn_block_style='attn-deform', cross_attn_combine_style='concat', k=10, n_group=2, deformable=False,
+                 region_wise=False):
         super().__init__()
         self.norm2 = norm_layer(dim)
         self.ls2 = LayerScale(dim, init_values=init_values) if init_values else nn.Identity()
@@ -192,7 +205,7 @@ class CrossAttnBlockApi(nn.Module):
         self.norm1 = norm_layer(dim)
         self.ls1, self.drop_path1 = _scale_and_path(dim, init_values, drop_path)
         self.self_attn_combine_style = _combine_style(self_attn_combine_style, 'CrossAttnBlockApi self-attention')
-        tokens = _tokens(self_attn_block_style, 'self_attn_block_style', deformable)
+        tokens = _tokens(self_attn_block_style, 'self_attn_block_style', deformable, region_wise)
         self.self_attn_block_length = len(tokens)
         self.self_attn = None
         self.local_self_attn = None
@@ -212,7 +225,7 @@ class CrossAttnBlockApi(nn.Module):
         self.norm_v = norm_layer(dim)
         self.ls4, self.drop_path4 = _scale_and_path(dim, init_values, drop_path)
         self.cross_attn_combine_style = _combine_style(cross_attn_combine_style, 'CrossAttnBlockApi cross-attention')
-        tokens = _tokens(cross_attn_block_style, 'cross_attn_block_style', deformable)
+        tokens = _tokens(cross_attn_block_style, 'cross_attn_block_style', deformable, region_wise, cross=True)
         self.cross_attn_block_length = len(tokens)
         self.cross_attn = None
         self.local_cross_attn = None
@@ -230,6 +243,11 @@ class CrossAttnBlockApi(nn.Module):
                 self.ls5, self.drop_path5 = _scale_and_path(dim, init_values, drop_path)
 
     def _local_self(self, x, q_pos, idx, denoise_length):
+        if isinstance(self.local_self_attn, DeformableLocalAttention):
+            if denoise_length is not None:
+                raise ValueError("the block token 'rw_deform' (DeformableLocalAttention) has no denoising form, got denoise_length = %r"
+                                 % (denoise_length,))
+            return self.local_self_attn(x, q_pos, idx=idx)
         # with a list the branch is the same in both modes (the list already is the denoise list); without one it searches
         return self.local_self_attn(x, q_pos, idx=idx, denoise_length=denoise_length if idx is None else None)
 
@@ -270,13 +288,14 @@ class TransformerEncoder(nn.Module):
 
     def __init__(self, embed_dim=256, depth=4, num_heads=4, mlp_ratio=4., qkv_bias=False, init_values=None, drop_rate=0.,
                  attn_drop_rate=0., drop_path_rate=0., act_layer=nn.GELU, norm_layer=nn.LayerNorm, block_style_list=['attn-deform'],
-                 combine_style='concat', k=10, n_group=2, deformable=False):
+                 combine_style='concat', k=10, n_group=2, deformable=False, region_wise=False):
         super().__init__()
         self.k = k
         self.blocks = nn.ModuleList([SelfAttnBlockApi(
             dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, init_values=init_values, drop=drop_rate,
             attn_drop=attn_drop_rate, drop_path=_path_rate(drop_path_rate, i), act_layer=act_layer, norm_layer=norm_layer,
-            block_style=block_style_list[i], combine_style=combine_style, k=k, n_group=n_group, deformable=deformable) for i in range(depth)])
+            block_style=block_style_list[i], combine_style=combine_style, k=k, n_group=n_group, deformable=deformable,
+            region_wise=region_wise) for i in range(depth)])
 
     def lists(self, pos):
         """-> idx (B,N,k) | None when no block has a graph branch"""
@@ -295,7 +314,8 @@ class TransformerDecoder(nn.Module):
     def __init__(self, embed_dim=256, depth=4, num_heads=4, mlp_ratio=4., qkv_bias=False, init_values=None, drop_rate=0.,
                  attn_drop_rate=0., drop_path_rate=0., act_layer=nn.GELU, norm_layer=nn.LayerNorm,
                  self_attn_block_style_list=['attn-deform'], self_attn_combine_style='concat',
-                 cross_attn_block_style_list=['attn-deform'], cross_attn_combine_style='concat', k=10, n_group=2, deformable=False):
+                 cross_attn_block_style_list=['attn-deform'], cross_attn_combine_style='concat', k=10, n_group=2, deformable=False,
+                 region_wise=False):
         super().__init__()
         self.k = k
         self.blocks = nn.ModuleList([CrossAttnBlockApi(
@@ -303,7 +323,7 @@ class TransformerDecoder(nn.Module):
             attn_drop=attn_drop_rate, drop_path=_path_rate(drop_path_rate, i), act_layer=act_layer, norm_layer=norm_layer,
             self_attn_block_style=self_attn_block_style_list[i], self_attn_combine_style=self_attn_combine_style,
             cross_attn_block_style=cross_attn_block_style_list[i], cross_attn_combine_style=cross_attn_combine_style,
-            k=k, n_group=n_group, deformable=deformable) for i in range(depth)])
+            k=k, n_group=n_group, deformable=deformable, region_wise=region_wise) for i in range(depth)])
 
     def lists(self, q_pos, v_pos, denoise_length=None):
         """-> (self_attn_idx (B,N,k) rows of q, cross_attn_idx (B,N,k) rows of v), each None when no block uses it.  With denoise_length
@@ -338,7 +358,7 @@ class PointTransformerEncoder(nn.Module):
 
     def __init__(self, embed_dim=256, depth=12, num_heads=4, mlp_ratio=4., qkv_bias=True, init_values=None, drop_rate=0.,
                  attn_drop_rate=0., drop_path_rate=0., norm_layer=None, act_layer=None, block_style_list=['attn-deform'],
-                 combine_style='concat', k=10, n_group=2, deformable=False):
+                 combine_style='concat', k=10, n_group=2, deformable=False, region_wise=False):
         super().__init__()
         norm_layer = norm_layer or partial(nn.LayerNorm, eps=1e-6)
         act_layer = act_layer or nn.GELU
@@ -350,7 +370,8 @@ class PointTransformerEncoder(nn.Module):
         self.blocks = TransformerEncoder(
             embed_dim=embed_dim, num_heads=num_heads, depth=depth, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, init_values=init_values,
             drop_rate=drop_rate, attn_drop_rate=attn_drop_rate, drop_path_rate=dpr, norm_layer=norm_layer, act_layer=act_layer,
-            block_style_list=block_style_list, combine_style=combine_style, k=k, n_group=n_group, deformable=deformable)
+            block_style_list=block_style_list, combine_style=combine_style, k=k, n_group=n_group, deformable=deformable,
+            region_wise=region_wise)
         self.norm = norm_layer(embed_dim)
         self.apply(_init_weights)
 
@@ -364,7 +385,7 @@ class PointTransformerDecoder(nn.Module):
     def __init__(self, embed_dim=256, depth=12, num_heads=4, mlp_ratio=4., qkv_bias=True, init_values=None, drop_rate=0.,
                  attn_drop_rate=0., drop_path_rate=0., norm_layer=None, act_layer=None, self_attn_block_style_list=['attn-deform'],
                  self_attn_combine_style='concat', cross_attn_block_style_list=['attn-deform'], cross_attn_combine_style='concat',
-                 k=10, n_group=2, deformable=False):
+                 k=10, n_group=2, deformable=False, region_wise=False):
         super().__init__()
         norm_layer = norm_layer or partial(nn.LayerNorm, eps=1e-6)
         act_layer = act_layer or nn.GELU
@@ -379,29 +400,30 @@ class PointTransformerDecoder(nn.Module):
             drop_rate=drop_rate, attn_drop_rate=attn_drop_rate, drop_path_rate=dpr, norm_layer=norm_layer, act_layer=act_layer,
             self_attn_block_style_list=self_attn_block_style_list, self_attn_combine_style=self_attn_combine_style,
             cross_attn_block_style_list=cross_attn_block_style_list, cross_attn_combine_style=cross_attn_combine_style,
-            k=k, n_group=n_group, deformable=deformable)
+            k=k, n_group=n_group, deformable=deformable, region_wise=region_wise)
         self.apply(_init_weights)
 
     def forward(self, q, v, q_pos, v_pos, denoise_length=None):
         return self.blocks(q, v, q_pos, v_pos, denoise_length=denoise_length)
 
 
-def _entry_kwargs(config, deformable):
-    """a stack's config section as keywords; `deformable` (a bool or a list of token names) from the section itself or, failing that,
-    from the model section"""
+def _entry_kwargs(config, deformable, region_wise=False):
+    """a stack's config section as keywords; `deformable` (a bool or a list of token names) and `region_wise` (a bool) from the section
+    itself or, failing that, from the model section"""
     kw = dict(config)
     kw['deformable'] = config.get('deformable', False) or deformable
+    kw['region_wise'] = bool(config.get('region_wise', False) or region_wise)
     return kw
 
 
 class PointTransformerEncoderEntry(PointTransformerEncoder):
-    def __init__(self, config, deformable=False, **kwargs):
-        super().__init__(**_entry_kwargs(config, deformable))
+    def __init__(self, config, deformable=False, region_wise=False, **kwargs):
+        super().__init__(**_entry_kwargs(config, deformable, region_wise))
 
 
 class PointTransformerDecoderEntry(PointTransformerDecoder):
-    def __init__(self, config, deformable=False, **kwargs):
-        super().__init__(**_entry_kwargs(config, deformable))
+    def __init__(self, config, deformable=False, region_wise=False, **kwargs):
+        super().__init__(**_entry_kwargs(config, deformable, region_wise))
 
 
 # ---------------------------------------------------------------------------------------------- PCTransformer and AdaPoinTr
@@ -483,7 +505,8 @@ class PCTransformer(nn.Module):
         self.pos_embed = nn.Sequential(nn.Linear(in_chans, 128), nn.GELU(), nn.Linear(128, encoder_config.embed_dim))
         self.input_proj = nn.Sequential(nn.Linear(self.grouper.num_features, 512), nn.GELU(), nn.Linear(512, encoder_config.embed_dim))
         deformable = config.get('deformable', False)                # opt-in: true (the token `deform`) or a list of token names
-        self.encoder = PointTransformerEncoderEntry(encoder_config, deformable=deformable)
+        region_wise = config.get('region_wise', False)              # opt-in: true serves the token `rw_deform` in the self positions
+        self.encoder = PointTransformerEncoderEntry(encoder_config, deformable=deformable, region_wise=region_wise)
         self.increase_dim = nn.Sequential(nn.Linear(encoder_config.embed_dim, 1024), nn.GELU(), nn.Linear(1024, global_feature_dim))
         self.coarse_pred = nn.Sequential(nn.Linear(global_feature_dim, 1024), nn.GELU(), nn.Linear(1024, 3 * query_num))
         self.mlp_query = nn.Sequential(nn.Linear(global_feature_dim + 3, 1024), nn.GELU(), nn.Linear(1024, 1024), nn.GELU(),
@@ -492,7 +515,7 @@ class PCTransformer(nn.Module):
             self.mem_link = nn.Identity()
         else:
             self.mem_link = nn.Linear(encoder_config.embed_dim, decoder_config.embed_dim)
-        self.decoder = PointTransformerDecoderEntry(decoder_config, deformable=deformable)
+        self.decoder = PointTransformerDecoderEntry(decoder_config, deformable=deformable, region_wise=region_wise)
         self.query_ranking = nn.Sequential(nn.Linear(3, 256), nn.GELU(), nn.Linear(256, 256), nn.GELU(), nn.Linear(256, 1), nn.Sigmoid())
         self.apply(_init_weights)
 

@@ -18,7 +18,11 @@ reference's, so its checkpoints load with strict=True.
     improvedDeformableLocalGraphAttention   the deformable graph feature (block token `deform_graph`): the ball-scaled offset head with
                                             G = 1, HF.three_nn and HF.interp_edge_max -- max over the slots of three interpolated rows
                                             plus the query half, no (B, N, k, C) tensor (README "Deformable graph attention")
-    DeformableAttnBlock, DeformableAttnDecoderBlock   the reference's fixed layouts around it
+    DeformableLocalAttention                the region-wise deformable self-attention (block token `rw_deform`): the same offset head,
+                                            HF.three_nn and per-point products, then HF.region_attention -- a k x k attention per token
+                                            and head and the max over its rows, no (B, N, k, C) tensor and no (B H N, k, k) scores (README
+                                            "Region-wise deformable attention")
+    DeformableAttnBlock, DeformableAttnDecoderBlock, RegionWiseBlock   the reference's fixed layouts around them
 The fused attention path is taken for HIP f32 tensors with head_dim 64, N <= HF.ATTN_MAX_L and no active attention dropout; otherwise
 the same module runs the torch formulation, and a HIP tensor that was declined is recorded by HF.note_declined.
 
@@ -26,8 +30,7 @@ Deliberate deviation (README "Denoising-query attention and the AdaPoinTr blocks
 topk(sorted=False) of |a|^2 + |b|^2 - 2ab; here the set is the library's ascending (distance, index) on the direct squared distance.  The
 sets agree wherever the k-th and (k+1)-th distances differ by more than rounding, and the order inside a set does not matter under the max.
 
-Not ported: DeformableLocalAttention (the block token rw_deform, a k x k attention per query) and the other fixed-layout Block /
-DecoderBlock variants of the reference file, which models/AdaPoinTr.py does not use."""
+Not ported: the other fixed-layout Block / DecoderBlock variants of the reference file, which models/AdaPoinTr.py does not use."""
 import torch
 import torch.nn as nn
 
@@ -164,6 +167,7 @@ class DeformableLocalCrossAttention(nn.Module):
     recorded by HF.note_declined.  The neighbour set is the library's ascending (distance, index), as for the other modules."""
 
     ball = False        # improvedDeformableLocalCrossAttention: the offset is scaled by half the extent of the k listed positions
+    trace_site = 'deformable_attention.idx3'
 
     def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_drop=0., proj_drop=0., k=10, n_group=2):
         super().__init__()
@@ -201,7 +205,8 @@ class DeformableLocalCrossAttention(nn.Module):
         r = 1.0 / (dist + 1e-8)
         return r / torch.sum(r, dim=-1, keepdim=True)
 
-    def _fused(self, q, v, v_pos, idx):
+    def _fused_operands(self, q, v, v_pos, idx):
+        """-> (proj_q(q), PK, PV, idx3, w3): everything in front of the attention core, on the library's kernels"""
         B, N, C = q.shape
         NK, G, c, lin0, ln = v.shape[1], self.n_group, self.group_dims, self.linear_offset[0], self.linear_offset[1]
         qp = HF.linear(q, self.proj_q.weight, self.proj_q.bias)
@@ -221,11 +226,15 @@ class DeformableLocalCrossAttention(nn.Module):
         Wk, Wv = self.proj_k.weight, self.proj_v.weight
         PK = torch.stack([HF.linear(vg[g], Wk[:, g * c:(g + 1) * c].contiguous()) for g in range(G)], dim=1)
         PV = torch.stack([HF.linear(vg[g], Wv[:, g * c:(g + 1) * c].contiguous()) for g in range(G)], dim=1)
+        return qp, PK, PV, idx3, w3
+
+    def _fused(self, q, v, v_pos, idx):
+        qp, PK, PV, idx3, w3 = self._fused_operands(q, v, v_pos, idx)
         ctx = HF.deform_attention(qp, PK, PV, self.proj_k.bias, self.proj_v.bias, idx3, w3, self.num_heads, self.scale)
         return self.proj_drop(HF.linear(ctx, self.proj.weight, self.proj.bias))
 
-    def _torch(self, q, v, v_pos, idx):
-        """the same restatement as torch operators, any device and dtype"""
+    def _torch_operands(self, q, v, v_pos, idx):
+        """the same operands as torch operators, any device and dtype"""
         B, N, C = q.shape
         NK, G, c, lin0, ln = v.shape[1], self.n_group, self.group_dims, self.linear_offset[0], self.linear_offset[1]
         qp = self.proj_q(q)
@@ -241,7 +250,7 @@ class DeformableLocalCrossAttention(nn.Module):
             dist, idx3 = shifted_three_nn(flat, known)
             if L.POOL_TRACE is not None:
                 # the recorded choice replaces this run's, and the distances follow it (slots beyond NK < 3 points stay at +inf)
-                idx3 = L.trace_idx('deformable_attention.idx3', idx3)
+                idx3 = L.trace_idx(self.trace_site, idx3)
                 near = torch.gather(known, 1, idx3.long().reshape(B * G, -1, 1).expand(-1, -1, 3)).view(B * G, -1, 3, 3)
                 d = (flat.unsqueeze(2) - near).pow(2).sum(-1).sqrt()
                 dist = torch.where(torch.arange(3, device=d.device) < NK, d, torch.full_like(d, float('inf')))
@@ -250,6 +259,11 @@ class DeformableLocalCrossAttention(nn.Module):
         vg = v.view(B, NK, G, c).permute(0, 2, 1, 3)
         PK = torch.matmul(vg, self.proj_k.weight.view(C, G, c).permute(1, 2, 0))
         PV = torch.matmul(vg, self.proj_v.weight.view(C, G, c).permute(1, 2, 0))
+        return qp, PK, PV, idx3, w3
+
+    def _torch(self, q, v, v_pos, idx):
+        """the same restatement as torch operators, any device and dtype"""
+        qp, PK, PV, idx3, w3 = self._torch_operands(q, v, v_pos, idx)
         drop = self.attn_drop if self.training and self.attn_drop.p > 0 else None
         ctx = torch_cpu.deform_attention(qp, PK, PV, self.proj_k.bias, self.proj_v.bias, idx3, w3, self.num_heads, self.scale, drop)
         return self.proj_drop(self.proj(ctx))
@@ -289,6 +303,58 @@ class improvedDeformableLocalCrossAttention(DeformableLocalCrossAttention):
 
     def forward(self, q, q_pos, v=None, v_pos=None, idx=None):
         return super().forward(q, q_pos, v, v_pos, idx)
+
+
+class DeformableLocalAttention(DeformableLocalCrossAttention):
+    """reference models/Transformer_utils.py:159-266 (block token `rw_deform`): region-wise deformable SELF attention.  Every token
+    gathers the projected query rows of its k neighbours, runs a full k x k softmax attention per head of those k rows against k keys
+    and values interpolated at learned, shifted positions, and keeps the per-channel maximum over the k context rows.
+    forward(x (B,N,dim), pos (B,N,3), idx=None (B,N,k) rows of x) -> (B,N,dim).  The reference's 15 state-dict keys: proj_q, proj_k,
+    proj_v, proj_v_off, proj, linear_offset.{0,1,3}.
+
+    Everything in front of the core is DeformableLocalCrossAttention's self form (v = x, q = proj_q(x), ball = False) and is shared
+    with it, not copied: the offset head through the gather (HF.deform_offset), HF.three_nn with the reference's weights, and the
+    commuted per-point products PK / PV.  The core is HF.region_attention: Q_t = proj_q(x)[idx[., t]], S = scale Q K^T over the k x k
+    pairs, softmax over s, ctx = p V, max over t -- no (B,N,k,C) tensor and no (B H N, k, k) scores in memory.  The offset branch --
+    proj_v_off, linear_offset -- and the positions get no gradient (three_nn is not differentiable): it runs under no_grad.  The fused
+    path is taken for HIP f32 tensors in the served range (head_dim 64, at most 16 heads, k <= 32) with no active attention dropout
+    and upp_layers.POOL_TRACE unset; otherwise the torch formulation (upp_hip.torch_cpu.region_attention, which keeps the (B,N,k,C)
+    tensors) runs and a HIP tensor that was declined is recorded by HF.note_declined.  Under POOL_TRACE the torch formulation records
+    and replays idx3 and the arg of the max.  The module has no denoising form (the reference's has no denoise_length argument)."""
+
+    trace_site = 'region_attention.idx3'
+
+    def fusable(self, q, v):
+        return (super().fusable(q, v) and ops.region_attn_usable(q.shape[0], q.shape[1], v.shape[1], self.k, self.num_heads, self.n_group))
+
+    def _fused(self, q, v, v_pos, idx):
+        qp, PK, PV, idx3, w3 = self._fused_operands(q, v, v_pos, idx)
+        out = HF.region_attention(qp, idx, PK, PV, self.proj_k.bias, self.proj_v.bias, idx3, w3, self.num_heads, self.scale)
+        return self.proj_drop(HF.linear(out, self.proj.weight, self.proj.bias))
+
+    def _torch(self, q, v, v_pos, idx):
+        qp, PK, PV, idx3, w3 = self._torch_operands(q, v, v_pos, idx)
+        drop = self.attn_drop if self.training and self.attn_drop.p > 0 else None
+        pool = None if L.POOL_TRACE is None else (lambda y: L.max_over(y, 2, 'region_attention.max'))
+        out = torch_cpu.region_attention(qp, idx, PK, PV, self.proj_k.bias, self.proj_v.bias, idx3, w3, self.num_heads, self.scale, drop, pool)
+        return self.proj_drop(self.proj(out))
+
+    def forward(self, x, pos, idx=None):
+        if pos.dim() != 3 or pos.size(-1) != 3:
+            raise ValueError("pos must be (B, N, 3), got %s" % (tuple(pos.shape),))
+        if x.size(-1) != self.dim:
+            raise ValueError("x must have %d channels, got %d" % (self.dim, x.size(-1)))
+        if idx is None:
+            idx = knn_point(self.k, pos, pos)
+        if idx.shape != (x.shape[0], x.shape[1], self.k):
+            raise ValueError("idx must be (B, N, k) = %s, got %s" % ((x.shape[0], x.shape[1], self.k), tuple(idx.shape)))
+        idx = idx.long()
+        if self.fusable(x, x):
+            return self._fused(x, x, pos, idx)
+        if x.is_cuda and L.POOL_TRACE is None:
+            HF.note_declined("DeformableLocalAttention (%d,%d), %d heads, k = %d" % (x.shape[1], self.dim, self.num_heads, self.k),
+                             "head_dim != 64 / more than 16 heads / k > 32 / dtype / attention dropout")
+        return self._torch(x, x, pos, idx)
 
 
 class improvedDeformableLocalGraphAttention(nn.Module):
@@ -393,6 +459,28 @@ class improvedDeformableLocalGraphAttention(nn.Module):
             HF.note_declined("improvedDeformableLocalGraphAttention (%d,%d) x (%d,%d), k = %d" % (q.shape[1], self.dim, v.shape[1], self.dim, self.k),
                              "dim not a multiple of 64 / beyond 1024 / k > 32 / dtype")
         return self._torch(q, v, v_pos, idx)
+
+
+class RegionWiseBlock(nn.Module):
+    """reference models/Transformer_utils.py:894-915: x + region-wise deformable attention, x + MLP.  forward(x (B,N,dim), pos (B,N,3)).
+    The forward is the reference's AS WRITTEN THERE: the MLP branch is normalised by norm1, not norm2.  norm2 exists (two state-dict
+    keys, so the reference's checkpoints load with strict=True), is never applied, and its parameters end with grad None."""
+
+    def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, drop=0., attn_drop=0., init_values=None, drop_path=0.,
+                 act_layer=nn.GELU, norm_layer=nn.LayerNorm):
+        super().__init__()
+        self.norm1 = norm_layer(dim)
+        self.deformable_attn = DeformableLocalAttention(dim, num_heads=num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop)
+        self.ls1 = LayerScale(dim, init_values=init_values) if init_values else nn.Identity()
+        self.drop_path1 = DropPath(drop_path) if drop_path > 0. else nn.Identity()
+        self.norm2 = norm_layer(dim)
+        self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
+        self.ls2 = LayerScale(dim, init_values=init_values) if init_values else nn.Identity()
+        self.drop_path2 = DropPath(drop_path) if drop_path > 0. else nn.Identity()
+
+    def forward(self, x, pos):
+        x = x + self.drop_path1(self.ls1(self.deformable_attn(HF.layer_norm(x, self.norm1), pos)))
+        return x + self.drop_path2(self.ls2(self.mlp(HF.layer_norm(x, self.norm1))))
 
 
 class DeformableAttnBlock(nn.Module):

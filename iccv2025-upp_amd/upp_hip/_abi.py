@@ -74,6 +74,9 @@ SIGNATURES = {
     "upp_interp_max_fwd": (_c_i, [_c_f] * 6 + [ctypes.c_float] + [_c_i] * 5 + [_c_f]),
     "upp_interp_max_bwd": (_c_i, [_c_f] * 7 + [ctypes.c_float] + [_c_i] * 5 + [_c_f]),
     "upp_interp_max_bwd_det": (_c_i, [_c_f] * 7 + [ctypes.c_float] + [_c_i] * 5 + [_c_f]),
+    "upp_region_attn_fwd": (_c_i, [_c_f] * 10 + [ctypes.c_float] + [_c_i] * 6 + [_c_f]),
+    "upp_region_attn_bwd": (_c_i, [_c_f] * 15 + [ctypes.c_float] + [_c_i] * 6 + [_c_f]),
+    "upp_region_attn_bwd_det": (_c_i, [_c_f] * 16 + [ctypes.c_float] + [_c_i] * 6 + [_c_f]),
     "upp_emd_matchcost_det_work_bytes": (ctypes.c_longlong, [_c_i, _c_i, _c_i]),
     "upp_emd_matchcost_det": (_c_i, [_c_f] * 5 + [_c_i] * 3 + [_c_f]),
     "upp_patch_embed_work_floats": (ctypes.c_longlong, [_c_i, _c_i]),

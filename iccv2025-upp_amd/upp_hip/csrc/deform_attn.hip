@@ -12,6 +12,7 @@
 // A wave's item is wave-uniform (readfirstlane), so idx3 / w3 travel through the scalar cache.  No LDS, no scratch: every per-lane array
 // is indexed by a fully unrolled, guarded loop.
 #include "det_scan.h"
+#include "deform_row.h"
 
 namespace {
 
@@ -96,22 +97,6 @@ __global__ __launch_bounds__(256) void da_offset_kernel(const float *__restrict_
             shift[row * 3 + lane] = valid ? __fadd_rn(pos[(b * NK + j) * 3 + lane], off) : __builtin_nanf("");
         }
     }
-}
-
-// bias[ch], then fma(w3, P[idx3], .) for ascending g, then ascending j: the key (or value) row of slot s of query (b, n), channel ch.
-// An index outside [0, NK) contributes nothing.
-__device__ __forceinline__ float da_row(const float *__restrict__ P, float bias, const int32_t *__restrict__ idx3, const float *__restrict__ w3,
-                                        long long b, int n, int s, int G, int N, int NK, int k, int C, int ch) {
-    float r = bias;
-    for (int g = 0; g < G; ++g) {
-        const long long bg = b * G + g, e = ((bg * N + n) * k + s) * 3;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int i = idx3[e + j];
-            if ((unsigned)i < (unsigned)NK) r = __builtin_fmaf(w3[e + j], P[(bg * NK + i) * C + ch], r);
-        }
-    }
-    return r;
 }
 
 // blockIdx.x * 4 + wave = item (b, n, h), grid-stride.  score_s sits on lane s; p (B,N,H,k) is saved for the backward.

@@ -7,6 +7,7 @@
 //   upp_knn_scatter_add_det, upp_edge_conv_bwd's g_A     KnnScatterJob       knn_points.hip
 //   upp_deform_attn_bwd_det                              DeformJob           deform_attn.hip (values formed on the fly while staging)
 //   upp_interp_max_bwd_det                               InterpMaxJob        interp_max.hip (a channel whose arg is another slot stages +0.0f)
+//   upp_region_attn_bwd_det's d_PK / d_PV                RegionJob           region_attn.hip (sources read from the caller's rows workspace)
 // (upp_emd_matchcost_det is an ordered sum of tile costs, not a scatter: emd.hip.)
 //
 // A scatter-add by f32 atomics sums each target's contributions in whatever order the hardware retires them.  Here every TARGET is

@@ -677,6 +677,71 @@ def interp_edge_max(PW, Bq, idx3, w3, slope=0.2, deterministic=None):
                                 None if deterministic is None else bool(deterministic))
 
 
+# ------------------------------------------------------------------ region-wise deformable attention (README section of that name)
+class _RegionAttention(Function):
+    """max over the rows of a k x k attention per token and head as one node (include/upp_hip.h "region-wise deformable attention"): saves
+    its inputs and the arg bytes (B,N,C) -- nothing of B N k C or B N H k k elements; the query, key and value rows and the
+    probabilities are recomputed, the probabilities by the forward's own statement.  The
+    three scatter-adds follow the deterministic mode: `det` None reads DETERMINISTIC when the backward runs, True / False fixes it for
+    this call; the deterministic form allocates its (3,B,N,k,C) workspace for the length of the call.  idx, idx3 and w3 get no gradient."""
+
+    @staticmethod
+    def forward(ctx, q, idx, PK, PV, bk, bv, idx3, w3, num_heads, scale, det):
+        out, arg = ops.region_attn_fwd(q, idx, PK, PV, bk, bv, idx3, w3, num_heads, scale)
+        ctx.save_for_backward(q, idx, PK, PV, bk, bv, idx3, w3, arg)
+        ctx.cfg = (num_heads, scale, det)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        q, idx, PK, PV, bk, bv, idx3, w3, arg = ctx.saved_tensors
+        num_heads, scale, det = ctx.cfg
+        need = ctx.needs_input_grad
+        want_bk, want_bv = bk is not None and need[4], bv is not None and need[5]
+        d_q, d_PK, d_PV, d_krow, d_vrow, _rows = ops.region_attn_bwd(q, idx, PK, PV, bk, bv, idx3, w3, arg, g.contiguous(), num_heads, scale,
+                                                                     deterministic=DETERMINISTIC if det is None else det,
+                                                                     want_krow=want_bk, want_vrow=want_bv)
+        C = g.shape[-1]
+        return (d_q if need[0] else None, None, d_PK if need[2] else None, d_PV if need[3] else None,
+                ops.sum_rows(d_krow.view(-1, C)) if want_bk else None, ops.sum_rows(d_vrow.view(-1, C)) if want_bv else None,
+                None, None, None, None, None)
+
+
+def region_attention_usable(q, idx, PK, PV, idx3, w3, num_heads):
+    """Do the fused kernels serve these operands (HIP f32 / int tensors, head_dim 64, the served sizes of include/upp_hip.h)?"""
+    if not (_deform_f32(q, PK, PV, w3) and isinstance(idx3, torch.Tensor) and idx3.is_cuda and idx3.dtype == torch.int32
+            and isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype in (torch.int64, torch.int32)):
+        return False
+    if q.dim() != 3 or idx.dim() != 3 or PK.dim() != 4 or PV.shape != PK.shape or idx3.dim() != 4 or idx3.shape != w3.shape:
+        return False
+    B, N, C = q.shape
+    G, NK, k = PK.shape[1], PK.shape[2], idx.shape[2]
+    H = int(num_heads)
+    if H < 1 or C != 64 * H or tuple(idx.shape) != (B, N, k) or tuple(PK.shape) != (B, G, NK, C) or tuple(idx3.shape) != (B, G, N * k, 3):
+        return False
+    return ops.region_attn_usable(B, N, NK, k, H, G)
+
+
+def region_attention(q, idx, PK, PV, bk, bv, idx3, w3, num_heads, scale, deterministic=None):
+    """q (B,N,C) the projected queries, idx (B,N,k) int64 rows of q (the neighbour list), PK / PV (B,G,NK,C) the per-group key / value
+    products of the memory tokens, bk / bv (C) or None, idx3 int32 and w3 f32 (B,G,N k,3) (three_nn of the shifted positions and the
+    reference's weights) -> (B,N,C): per token and head a k x k softmax attention of the k gathered query rows over the k interpolated
+    key / value rows, then the per-channel maximum over the k context rows (include/upp_hip.h "region-wise deformable attention").
+    q, PK, PV, bk, bv get gradients, idx, idx3 and w3 none.  deterministic: None follows functional.DETERMINISTIC (read when the backward
+    node runs), True / False per call.  HIP tensors outside the served range (head_dim 64, H <= 16, G | H, k <= 32) take the torch
+    formulation (note_declined records it); CPU tensors take it when upp_hip.torch_cpu is enabled."""
+    from . import torch_cpu
+    if _torch_cpu(q, PK, PV, idx3, w3):
+        return torch_cpu.region_attention(q, idx, PK, PV, bk, bv, idx3, w3, num_heads, scale)
+    if q.is_cuda and not region_attention_usable(q, idx, PK, PV, idx3, w3, num_heads):
+        note_declined("region_attention q %s, %d heads, PK %s, k = %d" % (tuple(q.shape), num_heads, tuple(PK.shape), idx.shape[-1]),
+                      "outside the served range")
+        return torch_cpu.region_attention(q, idx, PK, PV, bk, bv, idx3, w3, num_heads, scale)
+    return _RegionAttention.apply(q.contiguous(), idx.long().contiguous(), PK.contiguous(), PV.contiguous(),
+                                  None if bk is None else bk.contiguous(), None if bv is None else bv.contiguous(), idx3.contiguous(),
+                                  w3.detach().contiguous(), int(num_heads), float(scale), None if deterministic is None else bool(deterministic))
+
+
 def _expand_norm(norm):
     if norm is None:
         return None

@@ -925,6 +925,95 @@ def interp_max_bwd(g_out, out, arg, idx3, w3, NK, slope=0.2, deterministic=False
     return d_Bq, d_PW
 
 
+# ------------------------------------------------------------------ region-wise deformable attention (include/upp_hip.h)
+def region_attn_usable(B, N, NK, k, H, G):
+    """The served range of upp_region_attn_fwd / _bwd / _bwd_det (sizes only; head_dim 64 is the caller's C == 64 H)."""
+    if min(B, N, NK, k, H, G) < 1 or H > DEFORM_MAX_H or k > DEFORM_MAX_K or H % G or B > 65535:
+        return False
+    C = 64 * H
+    return max(B * G * NK * C, 3 * B * N * k * C, B * G * N * k * 3) < 2 ** 31
+
+
+def _region_attn_args(who, q, idx, PK, PV, bk, bv, idx3, w3, H, scale):
+    _need(q, "q", torch.float32, 3)
+    B, N, C = q.shape
+    _need(idx, "idx", torch.int64, 3)
+    k = idx.shape[2]
+    if tuple(idx.shape) != (B, N, k):
+        raise RuntimeError("%s: idx must be (B, N, k) = (%d, %d, k), got %s" % (who, B, N, tuple(idx.shape)))
+    _need(PK, "PK", torch.float32, 4)
+    G, NK = PK.shape[1], PK.shape[2]
+    _need_f32(PK, "PK", (B, G, NK, C))
+    _need_f32(PV, "PV", (B, G, NK, C))
+    _need_f32(bk, "bk", (C,), optional=True)
+    _need_f32(bv, "bv", (C,), optional=True)
+    _need(idx3, "idx3", torch.int32, 4, 3)
+    _need(w3, "w3", torch.float32, 4, 3)
+    if idx3.shape != w3.shape or tuple(idx3.shape) != (B, G, N * k, 3):
+        raise RuntimeError("%s: idx3 and w3 must both be (B, G, N k, 3) = (%d, %d, %d, 3), got %s and %s"
+                           % (who, B, G, N * k, tuple(idx3.shape), tuple(w3.shape)))
+    _same_device(q, idx, PK, PV, idx3, w3, *[t for t in (bk, bv) if t is not None])
+    H = int(H)
+    scale = _positive(who, "scale", scale)
+    if H < 1 or C != 64 * H:
+        raise RuntimeError("%s: C = %d with %d heads is outside the served range (head_dim 64: UPP_E_RANGE)" % (who, C, H))
+    if min(B, N, NK, k, H, G) < 1:
+        raise RuntimeError("%s: every size must be positive, got B = %d, N = %d, NK = %d, k = %d, H = %d, G = %d" % (who, B, N, NK, k, H, G))
+    if not region_attn_usable(B, N, NK, k, H, G):
+        raise RuntimeError("%s: B = %d, N = %d, NK = %d, k = %d, H = %d, G = %d is outside the served range head_dim 64, 1 <= H <= %d, "
+                           "G | H, 1 <= k <= %d, B <= 65535, every array below 2^31 elements (UPP_E_RANGE)"
+                           % (who, B, N, NK, k, H, G, DEFORM_MAX_H, DEFORM_MAX_K))
+    _aligned16(who, q=q, idx=idx, PK=PK, PV=PV, bk=bk, bv=bv, idx3=idx3, w3=w3)
+    return B, N, NK, k, H, G, C, scale
+
+
+def region_attn_fwd(q, idx, PK, PV, bk, bv, idx3, w3, H, scale):
+    """q (B,N,C), idx (B,N,k) int64 rows of q, PK / PV (B,G,NK,C), bk / bv (C) | None, idx3 int32 and w3 (B,G,N k,3) -> out (B,N,C),
+    arg (B,N,C) uint8: upp_region_attn_fwd, 1 launch, no (B,N,k,C) tensor and no (B,N,H,k,k) probabilities."""
+    B, N, NK, k, H, G, C, scale = _region_attn_args("region_attention", q, idx, PK, PV, bk, bv, idx3, w3, H, scale)
+    out = torch.empty((B, N, C), dtype=torch.float32, device=q.device)
+    arg = torch.empty((B, N, C), dtype=torch.uint8, device=q.device)
+    _call(q.device, "upp_region_attn_fwd", _abi.ptr(q), _abi.ptr(idx), _abi.ptr(PK), _abi.ptr(PV), _abi.ptr(bk), _abi.ptr(bv), _abi.ptr(idx3),
+          _abi.ptr(w3), _abi.ptr(out), _abi.ptr(arg), scale, B, N, NK, k, H, G)
+    return out, arg
+
+
+def region_attn_bwd(q, idx, PK, PV, bk, bv, idx3, w3, arg, d_out, H, scale, deterministic=False, want_krow=False, want_vrow=False,
+                    rows=None):
+    """-> d_q (B,N,C), d_PK, d_PV (B,G,NK,C), d_krow, d_vrow (B,N,C) | None (the rows whose column sums are d_bk / d_bv), rows | None.
+    The three scatter-adds by f32 atomics into arrays the entry point zeroes with a kernel (upp_region_attn_bwd) or, deterministic,
+    through the workspace rows (3,B,N,k,C) -- allocated here when None -- in ascending n k + t and (n k + s) 3 + j
+    (upp_region_attn_bwd_det, include/upp_hip.h)."""
+    B, N, NK, k, H, G, C, scale = _region_attn_args("region_attention_bwd", q, idx, PK, PV, bk, bv, idx3, w3, H, scale)
+    _need_f32(d_out, "d_out", (B, N, C))
+    _need(arg, "arg", torch.uint8, 3)
+    if tuple(arg.shape) != (B, N, C):
+        raise RuntimeError("region_attention_bwd: arg must be (B, N, C) = %s, got %s" % ((B, N, C), tuple(arg.shape)))
+    _same_device(q, arg, d_out)
+    _aligned16("region_attention_bwd", arg=arg, d_out=d_out)
+    dev = q.device
+    d_q = torch.empty((B, N, C), dtype=torch.float32, device=dev)
+    d_PK = torch.empty((B, G, NK, C), dtype=torch.float32, device=dev)
+    d_PV = torch.empty((B, G, NK, C), dtype=torch.float32, device=dev)
+    d_krow = torch.empty((B, N, C), dtype=torch.float32, device=dev) if want_krow else None
+    d_vrow = torch.empty((B, N, C), dtype=torch.float32, device=dev) if want_vrow else None
+    if deterministic:
+        if rows is None:
+            rows = torch.empty((3, B, N, k, C), dtype=torch.float32, device=dev)
+        _need_f32(rows, "rows", (3, B, N, k, C))
+        _same_device(q, rows)
+        _aligned16("region_attention_bwd", rows=rows)
+        _call(dev, "upp_region_attn_bwd_det", _abi.ptr(q), _abi.ptr(idx), _abi.ptr(PK), _abi.ptr(PV), _abi.ptr(bk), _abi.ptr(bv),
+              _abi.ptr(idx3), _abi.ptr(w3), _abi.ptr(arg), _abi.ptr(d_out), _abi.ptr(d_q), _abi.ptr(d_PK), _abi.ptr(d_PV),
+              _abi.ptr(d_krow), _abi.ptr(d_vrow), _abi.ptr(rows), scale, B, N, NK, k, H, G)
+    else:
+        rows = None
+        _call(dev, "upp_region_attn_bwd", _abi.ptr(q), _abi.ptr(idx), _abi.ptr(PK), _abi.ptr(PV), _abi.ptr(bk), _abi.ptr(bv), _abi.ptr(idx3),
+              _abi.ptr(w3), _abi.ptr(arg), _abi.ptr(d_out), _abi.ptr(d_q), _abi.ptr(d_PK), _abi.ptr(d_PV), _abi.ptr(d_krow),
+              _abi.ptr(d_vrow), scale, B, N, NK, k, H, G)
+    return d_q, d_PK, d_PV, d_krow, d_vrow, rows
+
+
 # ------------------------------------------------------------------ Chamfer
 def chamfer_fwd(xyz1, xyz2):
     _need(xyz1, "xyz1", torch.float32, 3, 3)

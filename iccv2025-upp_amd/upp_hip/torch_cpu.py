@@ -321,6 +321,45 @@ def deform_attention(q, PK, PV, bk, bv, idx3, w3, num_heads, scale, drop=None):
     return (p.unsqueeze(-1) * val).sum(2).reshape(B, N, C)
 
 
+def region_attention(q, idx, PK, PV, bk, bv, idx3, w3, num_heads, scale, drop=None, pool=None):
+    """The core of include/upp_hip.h "region-wise deformable attention" as torch operators (any device, dtype and head_dim;
+    differentiable in q, PK, PV, bk, bv): q (B,N,C), idx (B,N,k) rows of q, PK / PV (B,G,NK,C), bk / bv (C) | None, idx3 and w3
+    (B,G,N k,3) -> (B,N,C).  Q_t = q[idx[.,t]] (zero for an index outside [0, N)); key_s = bk + sum_g sum_j w3 PK_g[idx3] (g, then j
+    ascending; an idx3 outside [0, NK) contributes nothing), val_s likewise; per head p = softmax_s(scale Q_t . key_s), ctx_t = sum_s
+    p[t,s] val_s, out = max_t ctx_t.  drop: the module's attention dropout or None.  pool: None, or a callable ctx (B,N,k,C) -> (B,N,C)
+    that takes the place of ctx.max(2)[0] (the modules' arg-max instrument).  It keeps the (B,N,k,C) tensors and the (B,N,H,k,k) scores
+    the kernels avoid."""
+    B, N, C = q.shape
+    G, NK = PK.shape[1], PK.shape[2]
+    H = int(num_heads)
+    k = idx.shape[2]
+    i3 = idx3.long()
+    inside = ((i3 >= 0) & (i3 < NK)).unsqueeze(-1)
+    flat = i3.clamp(0, NK - 1).reshape(B, G, N * k * 3, 1).expand(-1, -1, -1, C)
+    w = w3.detach().unsqueeze(-1)
+
+    def rows(P, bias):
+        t = torch.gather(P, 2, flat).view(B, G, N * k, 3, C) * w
+        t = torch.where(inside, t, torch.zeros((), dtype=P.dtype, device=P.device))
+        r = None
+        for g in range(G):
+            for j in range(3):
+                r = t[:, g, :, j] if r is None else r + t[:, g, :, j]
+        if bias is not None:
+            r = r + bias
+        return r.view(B, N, k, H, C // H)
+
+    key, val = rows(PK, bk), rows(PV, bv)
+    i = idx.long()
+    Q = torch.gather(q, 1, i.clamp(0, N - 1).reshape(B, N * k, 1).expand(-1, -1, C)).view(B, N, k, C)
+    Q = torch.where(((i >= 0) & (i < N)).unsqueeze(-1), Q, torch.zeros((), dtype=q.dtype, device=q.device)).view(B, N, k, H, C // H)
+    p = (torch.einsum('bnthc,bnshc->bnhts', Q, key) * scale).softmax(dim=-1)
+    if drop is not None:
+        p = drop(p)
+    ctx = torch.einsum('bnhts,bnshc->bnthc', p, val).reshape(B, N, k, C)
+    return ctx.max(dim=2)[0] if pool is None else pool(ctx)
+
+
 def chamfer(xyz1, xyz2):
     """-> (dist1 (B,N), dist2 (B,M)) squared nearest-neighbour distances, differentiable (reference extensions/chamfer_dist)."""
     d = ((xyz1.unsqueeze(2) - xyz2.unsqueeze(1)) ** 2).sum(-1)

@@ -452,6 +452,61 @@ int upp_interp_max_bwd(const float *g_out, const float *out, const uint8_t *arg,
 int upp_interp_max_bwd_det(const float *g_out, const float *out, const uint8_t *arg, const int32_t *idx3, const float *w3, float *d_Bq,
                            float *d_PW, float slope, int B, int N, int NK, int k, int O, void *stream);
 
+/* ---- region-wise deformable attention: a k x k attention per token, max over its rows (additions to ABI 5) -----------------------
+ * What is left of DeformableLocalAttention (reference models/Transformer_utils.py:159-266, block token `rw_deform`) once its tall
+ * products are taken through the gather (README "Region-wise deformable attention"): per (sample, token, head) work with no GEMM in it.
+ * C = 64 H channels, H heads of 64, G channel groups (G divides H), k neighbour slots, N tokens, NK memory points.
+ *
+ * upp_region_attn_fwd
+ *   q (B,N,C) the projected queries; idx (B,N,k) int64 rows of q (the neighbour list); PK, PV (B,G,NK,C), bk, bv (C) or NULL (= 0),
+ *   idx3 int32 and w3 f32 (B,G,N k,3), scale: what they are for upp_deform_attn_fwd
+ *   -> per (b, n, head h with channels [64 h, 64 h + 64)):
+ *        Q_t = q[b, idx[b,n,t]] for t < k (a zero row for an index outside [0, N));
+ *        key_s[ch], val_s[ch] for s < k: the rows of upp_deform_attn_fwd, by the same statement (csrc/deform_row.h): bias, then
+ *          fma(w3, P[idx3], .) for ascending g, then ascending j; an idx3 outside [0, NK) contributes nothing;
+ *        S[t,s] = scale * (fma(Q_t[ch], key_s[ch], .) from +0 in ascending ch), the product by scale rounded once;
+ *        p[t,s] = expf(S[t,s] - max_s S[t,s]) / (the sum of the k exponentials from +0 in ascending s), one division per element;
+ *        ctx_t[ch] = fma(p[t,s], val_s[ch], .) from +0 in ascending s;
+ *        out[b,n,ch] = max_t ctx_t[ch], arg[b,n,ch] = the lowest t that attains it (a NaN never wins; no ctx above -inf leaves
+ *          out = -inf and arg 0, as upp_interp_max_fwd).
+ *      out (B,N,C) f32 and arg (B,N,C) uint8, which the backward reads.  Q_t, key_s, S and p live in the LDS, val_s and ctx_t in
+ *      registers only: p is not stored (a (B,N,H,k,k) array is k / 64 of a (B,N,k,C) tensor); the backward forms it again.  One wave per (b,n,h): no atomics, nothing zeroed, deterministic.  Nothing is read or written
+ *      through an index outside its range.  1 launch.
+ *
+ * upp_region_attn_bwd / upp_region_attn_bwd_det
+ *   + arg, d_out (B,N,C) -> d_q (B,N,C), d_PK, d_PV (B,G,NK,C), d_krow, d_vrow (B,N,C) or NULL.  The rows and p are recomputed, p by
+ *   the forward's own statement on the same rows (the forward's bits).  With g = d_out and a[ch] = min(arg[ch], k - 1):
+ *        dp[t,s] = fma(g[ch], val_s[ch], .) from +0 over the channels of the head with a[ch] == t, in ascending ch;
+ *        r_t = fma(p[t,s], dp[t,s], .) from +0 in ascending s;  ds[t,s] = p[t,s] * (dp[t,s] - r_t);
+ *        d_Q_t[ch] = scale * (fma(ds[t,s], key_s[ch], .) from +0 in ascending s);
+ *        d_key_s[ch] = scale * (fma(ds[t,s], Q_t[ch], .) from +0 in ascending t);  d_val_s[ch] = p[a[ch], s] * g[ch];
+ *        d_krow[b,n] = sum_s d_key_s, d_vrow[b,n] = sum_s d_val_s from +0 in ascending s (their column sums are the gradients of
+ *          bk and bv);
+ *        d_q[b, idx[b,n,t]] += d_Q_t;  d_PK[b,g,idx3[..,j]] += w3[..,j] * d_key_s, d_PV likewise with d_val_s (each product rounded
+ *          once).  An index outside its range receives nothing.  idx, w3 and idx3 get no gradient.
+ *      upp_region_attn_bwd: d_q, d_PK and d_PV are zeroed here by a kernel (no memset) and summed by f32 atomics, 256 contiguous
+ *      bytes per wave instruction, in the order the hardware retires them; no (B,N,k,C) array exists.  4 launches.
+ *      upp_region_attn_bwd_det: the caller passes rows (3,B,N,k,C) f32, which receives d_Q, d_key and d_val (every element written);
+ *      d_q is upp_knn_scatter_add_det of plane 0 over idx, in ascending n k + t; d_PK[b,g,r,ch] = +0.0f, then + the rounded product
+ *      w3 * d_key_s of every source (n, s, j) with idx3 == r in ascending (n k + s) 3 + j, one rounded addition each, d_PV likewise:
+ *      a job of the one `_det` kernel body (csrc/det_scan.h).  Every output element is overwritten: nothing to zero, nothing
+ *      allocated.  3 launches.  d_krow and d_vrow have a fixed order in both forms.
+ *
+ * Limits: 1 <= H <= 16, G divides H, 1 <= k <= 32, N, NK >= 1, B <= 65535 and every array (d_PK, rows, idx3) below 2^31
+ *   elements -- UPP_E_RANGE beyond.  A null pointer (bk, bv, d_krow, d_vrow excepted; rows only in the _det form), a non-positive
+ *   size, a scale that is not finite and positive: UPP_E_BADARG.  Both before any launch. */
+int upp_region_attn_fwd(const float *q, const int64_t *idx, const float *PK, const float *PV, const float *bk, const float *bv,
+                        const int32_t *idx3, const float *w3, float *out, uint8_t *arg, float scale, int B, int N, int NK, int k, int H,
+                        int G, void *stream);
+int upp_region_attn_bwd(const float *q, const int64_t *idx, const float *PK, const float *PV, const float *bk, const float *bv,
+                        const int32_t *idx3, const float *w3, const uint8_t *arg, const float *d_out, float *d_q,
+                        float *d_PK, float *d_PV, float *d_krow, float *d_vrow, float scale, int B, int N, int NK, int k, int H, int G,
+                        void *stream);
+int upp_region_attn_bwd_det(const float *q, const int64_t *idx, const float *PK, const float *PV, const float *bk, const float *bv,
+                            const int32_t *idx3, const float *w3, const uint8_t *arg, const float *d_out, float *d_q,
+                            float *d_PK, float *d_PV, float *d_krow, float *d_vrow, float *rows, float scale, int B, int N, int NK,
+                            int k, int H, int G, void *stream);
+
 /* ---- Chamfer distance ----------------------------------------------------------
  * Replaces chamfer.forward / chamfer.backward (reference
  * extensions/chamfer_dist/chamfer_cuda.cpp:36-39, kernels chamfer.cu:15-145 and
@@ -526,7 +581,9 @@ int upp_emd_matchcost_bwd(const float *grad_cost, const float *xyz1, const float
  *   upp_knn_scatter_add_det stated and declared with its sibling under "the pytorch3d.ops surface" above: ascending l * K + k.
  *   upp_deform_attn_bwd_det stated and declared with its sibling under "deformable local cross-attention" above: ascending
  *                           (n k + s) 3 + j.
- *   upp_interp_max_bwd_det  stated and declared with its sibling under "deformable graph attention" above: ascending 3 n + j. */
+ *   upp_interp_max_bwd_det  stated and declared with its sibling under "deformable graph attention" above: ascending 3 n + j.
+ *   upp_region_attn_bwd_det stated and declared with its sibling under "region-wise deformable attention" above: ascending n k + t
+ *                           (d_q) and (n k + s) 3 + j (d_PK, d_PV). */
 int upp_chamfer_bwd_det(const float *xyz1, const float *xyz2, const int32_t *idx1, const int32_t *idx2,
                         const float *grad_dist1, const float *grad_dist2, float *g1, float *g2,
                         int B, int n, int m, void *stream);
