@@ -433,6 +433,18 @@ __global__ __launch_bounds__(64 * kFW) void ln_adapter_fwd_kernel(LnAdapterArgs 
                 mu[e] = a.bn_mean[lane + 64 * e]; rs[e] = a.bn_rstd[lane + 64 * e];
                 ga[e] = a.bn_gamma[lane + 64 * e]; be[e] = a.bn_beta[lane + 64 * e];
             }
+            // The index rounds (idx8 / w8 -> i2 -> u) of ALL rows of the wave go out before the first row's gathers, one
+            // load each: three dependent rounds per wave and not per row.  A row that is no centre row reads centre 0's lists and drops them.
+            // Lane 8 q + k holds neighbour k of row q; the row loop reads them back with v_readlane.
+            static_assert(RW * kNb <= 64, "shape");
+            int bl = bi[0], cl = ci[0];
+#pragma unroll
+            for (int q = 1; q < RW; ++q) if ((lane >> 3) == q) { bl = bi[q]; cl = ci[q]; }
+            const size_t tokl = ((size_t)bl * a.T + max(cl, 0)) * kNb + (lane & 7);
+            const int jl = a.idx8[tokl];
+            const float wl = a.w8[tokl];
+            const int crl = a.i2[bl * a.G2 + jl];
+            const float scl = a.u ? floorf(a.keep + a.u[crl / a.Lin]) / a.keep : 1.0f;   // the sample of the gathered row
 #pragma unroll
             for (int q = 0; q < RW; ++q) {
                 float acc[E];
@@ -441,13 +453,13 @@ __global__ __launch_bounds__(64 * kFW) void ln_adapter_fwd_kernel(LnAdapterArgs 
                 if (ci[q] >= 0) {               // wave-uniform
                     int j[kNb], cr[kNb];
                     float w[kNb], scr[kNb];
-                    const size_t tok = ((size_t)bi[q] * a.T + ci[q]) * kNb;
 #pragma unroll
-                    for (int k = 0; k < kNb; ++k) { j[k] = a.idx8[tok + k]; w[k] = a.w8[tok + k]; }
-#pragma unroll
-                    for (int k = 0; k < kNb; ++k) cr[k] = a.i2[bi[q] * a.G2 + j[k]];
-#pragma unroll
-                    for (int k = 0; k < kNb; ++k) scr[k] = a.u ? floorf(a.keep + a.u[cr[k] / a.Lin]) / a.keep : 1.0f;   // the sample of the gathered row
+                    for (int k = 0; k < kNb; ++k) {
+                        j[k] = __builtin_amdgcn_readlane(jl, kNb * q + k);
+                        cr[k] = __builtin_amdgcn_readlane(crl, kNb * q + k);
+                        w[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wl), kNb * q + k));
+                        scr[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(scl), kNb * q + k));
+                    }
 #pragma unroll
                     for (int h = 0; h < E; h += EC) {
                         float lv[EC][kNb], cx[EC][kNb], cy[EC][kNb];

@@ -15,6 +15,18 @@
 // converts the reference's flat / per-sample index conventions, including its stride-64-into-stride-74
 // behaviour, into that form); pool and interpolate are one kernel each, one wavefront per row, and the
 // backward scatter-adds are done as deterministic "scan the index list for my row" gathers, no atomics.
+//
+// The row walk of the fused step's backward kernels (prop_c2_csr, prop_x_csr, prop_x_csr_res), as built: a kernel's time is the longest
+// chain of address-dependent loads among its waves (~0.5 us per round), so a CSR row costs four rounds whatever its length --
+//   1. start[r], start[r + 1] together with the row's own loads (g_out row, column constants);
+//   2. the row's entries, one load: lane t reads perm[start + t], 64 entries per sweep (lanes past the end repeat the last entry --
+//      these are the zero-weight slots of the last batch); a longer row sweeps again, and a sweep is a chunk of the long-row path;
+//   3. what depends only on the entry, one load: w8[q] (c2), u[g] (g_X);
+//   4. the data rows, in the batches the arithmetic always had (8 entries in c2, 4 in g_X), each entry's row index and scalar read
+//      from its lane with v_readlane at a uniform index.  c2 (one workgroup per CU, 200 registers) requests batch i + 1 before it
+//      adds batch i; g_X does not: a second register set is 298 registers, one wave per SIMD for 600 workgroups, and was 6 us slower.
+// These kernels keep E column slots per lane, a template parameter: 6 for D <= 384, 8 up to 512.  No floating-point operation, and no
+// order of operations, differs from the batched loops these kernels replaced (tests/test_gpu_prop_chains.py restates them).
 #include "common.h"
 
 int upp_bn_finalize_launch(const float *part, int slabs, int per, int rows, int C, int training, float momentum, float eps,
@@ -23,6 +35,14 @@ int upp_bn_finalize_launch(const float *part, int slabs, int per, int rows, int 
 namespace {
 
 constexpr int kMaxE = 8;   // D <= 512
+// The CSR kernels of the fused step's backward take their column slot count E as a template parameter: 6 slots serve D <= 384 (every
+// model here), 8 serve D <= 512 -- two load instructions less per gathered row and a quarter of the row registers.  (The pool kernels
+// keep 8: with 6 they were 0.2-0.4 us shorter in the step, less than the 0.5 us that would have justified a second instantiation.)
+#define PROP_LAUNCH_E(D, kernel, ...)                                          \
+    do {                                                                       \
+        if ((D) <= 64 * 6) hipLaunchKernelGGL(kernel<6>, __VA_ARGS__);         \
+        else hipLaunchKernelGGL(kernel<kMaxE>, __VA_ARGS__);                   \
+    } while (0)
 constexpr int kNb = 8;     // neighbours per level-2 group and per interpolation (reference: group_size=8, de_neighbors=8)
 
 // pooled[g][c] = max_k v_k + (sum_k v_k) / 8,  v_k = X[i1[g][k]][c] * (1 + s_g);  amax[g][c] = arg max
@@ -480,54 +500,68 @@ __global__ __launch_bounds__(256) void prop_interp_bn_fwd_kernel(const float *__
     }
 }
 
+// The backward row kernels walk a CSR row as  start -> entries -> per-entry scalars -> data rows, whatever the row's length: the lanes of
+// the wave fetch up to 64 entries of the row in one load (lane t holds entry t of the sweep), the scalars that depend only on the entry
+// (w8[q], u[g]) in the next, and hand them to the arithmetic through v_readlane at a uniform index.  The arithmetic keeps its batches
+// (8 entries in c2, 4 in g_X; the empty slots of the last batch repeat the row's last entry with weight 0) and their order; in c2 the
+// data rows of batch i + 1 are requested before batch i is added (two register sets, peeled tail).
+__device__ __forceinline__ int lane_get(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
+__device__ __forceinline__ float lane_get(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+constexpr int kSweep = 64;   // entries of a CSR row held by the wave at a time
+
 // g_c2[gj] = 0.3 * sum over the CSR entries q of row gj of w8[q] * g_out[token row of q]; plus the BatchNorm-backward
 // column partials of the workgroup's 4 rows: part[(wg*2+0)*D+c] = sum g_c2, part[(wg*2+1)*D+c] = sum g_c2 * xhat.
+template <int E>
 __global__ __launch_bounds__(256) void prop_c2_csr_kernel(const float *__restrict__ g_out, const int32_t *__restrict__ start8,
                                                           const int32_t *__restrict__ perm8, const float *__restrict__ w8,
                                                           const float *__restrict__ pooled, const float *__restrict__ mean,
                                                           const float *__restrict__ rstd, float *__restrict__ g_c2,
                                                           float *__restrict__ part, int B, int Lp, int T, int G2, int D) {
     const int wgx = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);   // XCD x owns a contiguous eighth of the rows / groups (common.h)
-    __shared__ float sh[2][4][64 * kMaxE];
+    __shared__ float sh[2][4][64 * E];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int gj = wgx * 4 + wave;
     const int groups = B * G2;
     if (gj < groups) {
-        int cc[kMaxE];
-        float acc[kMaxE], pv[kMaxE], mu[kMaxE], rs[kMaxE];
+        const int s = start8[gj], eend = start8[gj + 1];
+        int cc[E];
+        float acc[E], pv[E], mu[E], rs[E];
 #pragma unroll
-        for (int e = 0; e < kMaxE; ++e) {
+        for (int e = 0; e < E; ++e) {
             cc[e] = min(lane + 64 * e, D - 1); acc[e] = 0.0f;
             pv[e] = pooled[(size_t)gj * D + cc[e]]; mu[e] = mean[cc[e]]; rs[e] = rstd[cc[e]];
         }
-        const int s = start8[gj], eend = start8[gj + 1];
-        for (int h0 = s; h0 < eend; h0 += 8) {                // 8 token rows x kMaxE column slots in flight
-            int q[8];
+        for (int c0 = s; c0 < eend; c0 += kSweep) {
+            const int q = perm8[min(c0 + lane, eend - 1)];    // lanes past the row's end repeat its last entry
+            const float wq = w8[q];
+            const int tok = q / kNb;                          // b * T + i
+            const int bb = tok / T, ii = tok - bb * T;
+            const int rq = bb * Lp + (Lp - T) + ii;           // the entry's token row
+            const int nb = (min(kSweep, eend - c0) + 7) / 8;  // batches of 8 token rows x E column slots
+            auto load = [&](float (&gv)[E][8], int b) {
 #pragma unroll
-            for (int t = 0; t < 8; ++t) q[t] = perm8[min(h0 + t, eend - 1)];
-            float w[8];
-            const float *grow[8];
+                for (int t = 0; t < 8; ++t) {
+                    const float *grow = g_out + (size_t)lane_get(rq, 8 * b + t) * D;
 #pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const int tok = q[t] / kNb;                   // b * T + i
-                const int bb = tok / T, ii = tok - bb * T;
-                w[t] = w8[q[t]];
-                grow[t] = g_out + ((size_t)bb * Lp + (Lp - T) + ii) * D;
-            }
-            float gv[kMaxE][8];
+                    for (int e = 0; e < E; ++e) gv[e][t] = grow[cc[e]];
+                }
+            };
+            auto add = [&](const float (&gv)[E][8], int b) {
 #pragma unroll
-            for (int e = 0; e < kMaxE; ++e)
+                for (int t = 0; t < 8; ++t) {
+                    const float wt = c0 + 8 * b + t < eend ? lane_get(wq, 8 * b + t) : 0.0f;
 #pragma unroll
-                for (int t = 0; t < 8; ++t) gv[e][t] = grow[t][cc[e]];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const float wt = h0 + t < eend ? w[t] : 0.0f;
-#pragma unroll
-                for (int e = 0; e < kMaxE; ++e) acc[e] += gv[e][t] * wt;
-            }
+                    for (int e = 0; e < E; ++e) acc[e] += gv[e][t] * wt;
+                }
+            };
+            float ga[E][8], gb[E][8];
+            load(ga, 0);
+            int b = 0;
+            for (; b + 2 < nb; b += 2) { load(gb, b + 1); add(ga, b); load(ga, b + 2); add(gb, b + 1); }
+            if (b + 1 < nb) { load(gb, b + 1); add(ga, b); add(gb, b + 1); } else add(ga, b);
         }
 #pragma unroll
-        for (int e = 0; e < kMaxE; ++e) {
+        for (int e = 0; e < E; ++e) {
             const int c = lane + 64 * e;
             if (c < D) {
                 const float gl = 0.3f * acc[e];
@@ -547,7 +581,9 @@ __global__ __launch_bounds__(256) void prop_c2_csr_kernel(const float *__restric
     }
 }
 
-// g_beta[c] = sum of the "sum g_lc" partials, g_gamma[c] = sum of the "sum g_lc * xhat" partials (fixed order)
+// g_beta[c] = sum of the "sum g_lc" partials, g_gamma[c] = sum of the "sum g_lc * xhat" partials (fixed order: wave w adds the
+// partial rows w, w + 4, w + 8, ... in turn, then (s0 + s1) + (s2 + s3)).  All loads of a wave -- up to 64 partial rows of both
+// arrays -- are requested before its first addition; more rows than that go round the loop again.
 __global__ __launch_bounds__(256) void prop_bn_grad_kernel(const float *__restrict__ part, int wgs, int D, float *__restrict__ g_gamma,
                                                            float *__restrict__ g_beta) {
     __shared__ float sb[4][64], sg[4][64];
@@ -555,15 +591,19 @@ __global__ __launch_bounds__(256) void prop_bn_grad_kernel(const float *__restri
     const int c = blockIdx.x * 64 + lane;
     const int cc = min(c, D - 1);
     float ab = 0.0f, ag = 0.0f;
-    for (int w0 = wave; w0 < wgs; w0 += 4 * 8) {
-        float pb[8], pg[8];
+    for (int w0 = wave; w0 < wgs; w0 += 4 * 64) {
+        float pb[2][32], pg[2][32];
 #pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const int w = min(w0 + 4 * t, wgs - 1);
-            pb[t] = part[((size_t)w * 2 + 0) * D + cc]; pg[t] = part[((size_t)w * 2 + 1) * D + cc];
-        }
+        for (int h = 0; h < 2; ++h)
 #pragma unroll
-        for (int t = 0; t < 8; ++t) if (w0 + 4 * t < wgs) { ab += pb[t]; ag += pg[t]; }
+            for (int t = 0; t < 32; ++t) {
+                const int w = min(w0 + 4 * (32 * h + t), wgs - 1);
+                pb[h][t] = part[((size_t)w * 2 + 0) * D + cc]; pg[h][t] = part[((size_t)w * 2 + 1) * D + cc];
+            }
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int t = 0; t < 32; ++t) if (w0 + 4 * (32 * h + t) < wgs) { ab += pb[h][t]; ag += pg[h][t]; }
     }
     sb[wave][lane] = ab; sg[wave][lane] = ag;
     __syncthreads();
@@ -573,10 +613,131 @@ __global__ __launch_bounds__(256) void prop_bn_grad_kernel(const float *__restri
     }
 }
 
+__device__ __forceinline__ float res_scale(const float *u_dp, float keep_dp, int b) {
+    return u_dp ? floorf(keep_dp + u_dp[b]) / keep_dp : 1.0f;
+}
+
 // The whole g_X of the step, one wavefront per row r of X:
 //   g_X[r] = g_out[r] + 0.3 * sum_{m: i2[m] == r} g_c2[m]
 //          + sum_{(g,k): i1[g][k] == r} (1 + s_g) * g_pooled[g] * (1/8 + [amax[g] == k])
 //   g_pooled[g] = gamma * rstd * (g_c2[g] - g_beta/n - xhat[g] * g_gamma/n)      (training; eval: gamma * rstd * g_c2[g])
+// RES: the row leaves as the two gradients of the residual x3 = x2 + dp_scale * (m + mbias):  g_x2[r] = g_X[r], g_m[r] = g_X[r] * dp_scale
+// (rowln_bwd_kernel without a LayerNorm: a copy and a scale of the row this kernel holds in registers).
+template <int E> struct XBatch { float gl[E][4], pv[E][4]; int am[E][4]; };
+
+template <int E, bool RES>
+__device__ __forceinline__ void prop_x_csr_row(const float *__restrict__ g_out, const float *__restrict__ g_c2,
+                                               const float *__restrict__ pooled, const uint8_t *__restrict__ amax,
+                                               const float *__restrict__ mean, const float *__restrict__ rstd,
+                                               const float *__restrict__ gamma, const float *__restrict__ g_gamma,
+                                               const float *__restrict__ g_beta, const float *__restrict__ u, float keep,
+                                               const int32_t *__restrict__ start1, const int32_t *__restrict__ perm1,
+                                               const int32_t *__restrict__ start2, const int32_t *__restrict__ perm2,
+                                               const float *__restrict__ u_dp, float keep_dp, int Lp, float *__restrict__ g_X,
+                                               float *__restrict__ g_m, int rows, int groups, int D, int training) {
+    const int wgx = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);   // XCD x owns a contiguous eighth of the rows / groups (common.h)
+    const int lane = threadIdx.x & 63;
+    const int r = wgx * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (r >= rows) return;
+    const int s1 = start1[r], e1 = start1[r + 1], s2 = start2[r], e2 = start2[r + 1];
+    constexpr int kRowChunk = kSweep;                          // a long row's chunk of partial sums is one sweep
+    // round 2 of the walk: the first sweep of both lists (lanes past a row's end repeat its last entry)
+    int q = 0, m2 = 0;
+    if (e1 > s1) q = perm1[min(s1 + lane, min(e1, s1 + kRowChunk) - 1)];
+    if (e2 > s2) m2 = perm2[min(s2 + lane, e2 - 1)];
+    const float sc = RES ? res_scale(u_dp, keep_dp, r / Lp) : 1.0f;
+    int cc[E];
+    float acc[E], mu[E], rs[E], ga[E], c1[E], c2[E];
+    const float inv_n = 1.0f / (float)groups;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        cc[e] = min(lane + 64 * e, D - 1);
+        acc[e] = g_out[(size_t)r * D + cc[e]];
+        mu[e] = mean[cc[e]]; rs[e] = rstd[cc[e]]; ga[e] = gamma[cc[e]];
+        c1[e] = 0.0f; c2[e] = 0.0f;
+    }
+    if (training) {                                            // one uniform branch around the whole batch of loads
+#pragma unroll
+        for (int e = 0; e < E; ++e) { c1[e] = g_beta[cc[e]]; c2[e] = g_gamma[cc[e]]; }
+    }
+#pragma unroll
+    for (int e = 0; e < E; ++e) { c1[e] *= inv_n; c2[e] *= inv_n; }
+    // the groups that list this row as a neighbour, entries [b0, b1) of its CSR row (at most one sweep, held as qs), four at a time
+    auto add_entries = [&](int b0, int b1, int qs) {
+        const int g = qs / kNb, k = qs - g * kNb;
+        const float f = 1.0f + (u ? floorf(keep + u[g]) / keep : 1.0f);   // round 3: the group's stochastic-depth factor
+        const int nb = (b1 - b0 + 3) / 4;
+        auto load = [&](XBatch<E> &x, int b) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const size_t o = (size_t)lane_get(g, 4 * b + t) * D;
+#pragma unroll
+                for (int e = 0; e < E; ++e) { x.gl[e][t] = g_c2[o + cc[e]]; x.pv[e][t] = pooled[o + cc[e]]; x.am[e][t] = amax[o + cc[e]]; }
+            }
+        };
+        auto add = [&](const XBatch<E> &x, int b) {
+            float ft[4];
+            int kt[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) { ft[t] = b0 + 4 * b + t < b1 ? lane_get(f, 4 * b + t) : 0.0f; kt[t] = lane_get(k, 4 * b + t); }
+#pragma unroll
+            for (int e = 0; e < E; ++e)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const float xh = (x.pv[e][t] - mu[e]) * rs[e];
+                    // eval: g_pooled = gamma * rstd * g_c2 and nothing else -- a non-finite xhat (a NaN token) must not reach g_X through 0 * xhat
+                    const float gp = (ga[e] * rs[e]) * (training ? x.gl[e][t] - c1[e] - xh * c2[e] : x.gl[e][t]);
+                    acc[e] += gp * ft[t] * (0.125f + (x.am[e][t] == kt[t] ? 1.0f : 0.0f));
+                }
+        };
+        // one batch in flight: a second register set (loads one batch ahead, as in the c2 kernel) costs 298 registers at E = 6 -- one
+        // wave per SIMD for 600 workgroups -- and measured 6 us slower; this form holds 154 (three waves per SIMD, one round)
+        for (int b = 0; b < nb; ++b) { XBatch<E> x; load(x, b); add(x, b); }
+    };
+    // level-2 centres whose own token is this row (usually <= 1), two at a time
+    for (int c0 = s2; c0 < e2; c0 += kSweep) {
+        if (c0 > s2) m2 = perm2[min(c0 + lane, e2 - 1)];
+        const int n = min(kSweep, e2 - c0);
+        for (int h = 0; h < n; h += 2) {
+            const size_t o0 = (size_t)lane_get(m2, h) * D, o1 = (size_t)lane_get(m2, h + 1) * D;
+            float a0[E], a1[E];
+#pragma unroll
+            for (int e = 0; e < E; ++e) { a0[e] = g_c2[o0 + cc[e]]; a1[e] = g_c2[o1 + cc[e]]; }
+            const float f1 = h + 1 < n ? 0.3f : 0.0f;
+#pragma unroll
+            for (int e = 0; e < E; ++e) { acc[e] += 0.3f * a0[e]; acc[e] += f1 * a1[e]; }
+        }
+    }
+    // A row listed by hundreds of groups is summed in chunks of kRowChunk entries: every chunk after the first starts a fresh partial
+    // sum, so its terms meet a small accumulator and only one addition per chunk meets the large one -- the rounding of those
+    // additions is what a long row's error consists of.  Every row of the models is one chunk: a few dozen entries at most.
+    float head[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) head[e] = 0.0f;
+    for (int c0 = s1; c0 < e1; c0 += kRowChunk) {
+        const int b1 = min(e1, c0 + kRowChunk);
+        if (c0 > s1) {
+            q = perm1[min(c0 + lane, b1 - 1)];
+#pragma unroll
+            for (int e = 0; e < E; ++e) { head[e] += acc[e]; acc[e] = 0.0f; }
+        }
+        add_entries(c0, b1, q);
+    }
+    if (e1 - s1 > kRowChunk) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) acc[e] += head[e];
+    }
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int c = lane + 64 * e;
+        if (c < D) {
+            g_X[(size_t)r * D + c] = acc[e];
+            if (RES) g_m[(size_t)r * D + c] = acc[e] * sc;
+        }
+    }
+}
+
+template <int E>
 __global__ __launch_bounds__(256) void prop_x_csr_kernel(const float *__restrict__ g_out, const float *__restrict__ g_c2,
                                                          const float *__restrict__ pooled, const uint8_t *__restrict__ amax,
                                                          const float *__restrict__ mean, const float *__restrict__ rstd,
@@ -585,87 +746,8 @@ __global__ __launch_bounds__(256) void prop_x_csr_kernel(const float *__restrict
                                                          const int32_t *__restrict__ start1, const int32_t *__restrict__ perm1,
                                                          const int32_t *__restrict__ start2, const int32_t *__restrict__ perm2,
                                                          float *__restrict__ g_X, int rows, int groups, int D, int training) {
-    const int wgx = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);   // XCD x owns a contiguous eighth of the rows / groups (common.h)
-    const int lane = threadIdx.x & 63;
-    const int r = wgx * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (r >= rows) return;
-    const int s1 = start1[r], e1 = start1[r + 1], s2 = start2[r], e2 = start2[r + 1];
-    int cc[kMaxE];
-    float acc[kMaxE], mu[kMaxE], rs[kMaxE], ga[kMaxE], c1[kMaxE], c2[kMaxE];
-    const float inv_n = 1.0f / (float)groups;
-#pragma unroll
-    for (int e = 0; e < kMaxE; ++e) {
-        cc[e] = min(lane + 64 * e, D - 1);
-        acc[e] = g_out[(size_t)r * D + cc[e]];
-        mu[e] = mean[cc[e]]; rs[e] = rstd[cc[e]]; ga[e] = gamma[cc[e]];
-        c1[e] = 0.0f; c2[e] = 0.0f;
-    }
-    if (training) {                                            // one uniform branch around the whole batch of loads
-#pragma unroll
-        for (int e = 0; e < kMaxE; ++e) { c1[e] = g_beta[cc[e]]; c2[e] = g_gamma[cc[e]]; }
-    }
-#pragma unroll
-    for (int e = 0; e < kMaxE; ++e) { c1[e] *= inv_n; c2[e] *= inv_n; }
-    for (int h0 = s2; h0 < e2; h0 += 2) {                     // level-2 centres whose own token is this row (usually <= 1)
-        const int m0 = perm2[h0], m1 = perm2[min(h0 + 1, e2 - 1)];
-        float a0[kMaxE], a1[kMaxE];
-#pragma unroll
-        for (int e = 0; e < kMaxE; ++e) { a0[e] = g_c2[(size_t)m0 * D + cc[e]]; a1[e] = g_c2[(size_t)m1 * D + cc[e]]; }
-        const float f1 = h0 + 1 < e2 ? 0.3f : 0.0f;
-#pragma unroll
-        for (int e = 0; e < kMaxE; ++e) { acc[e] += 0.3f * a0[e]; acc[e] += f1 * a1[e]; }
-    }
-    // the groups that list this row as a neighbour, entries [b0, b1) of its CSR row, four at a time
-    auto add_entries = [&](int b0, int b1) {
-        for (int h0 = b0; h0 < b1; h0 += 4) {
-            int g[4], k[4];
-            float f[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) { const int q = perm1[min(h0 + t, b1 - 1)]; g[t] = q / kNb; k[t] = q - g[t] * kNb; }
-#pragma unroll
-            for (int t = 0; t < 4; ++t) f[t] = h0 + t < b1 ? 1.0f + (u ? floorf(keep + u[g[t]]) / keep : 1.0f) : 0.0f;
-            float gl[kMaxE][4], pv[kMaxE][4];
-            int am[kMaxE][4];
-#pragma unroll
-            for (int e = 0; e < kMaxE; ++e)
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const size_t o = (size_t)g[t] * D + cc[e];
-                    gl[e][t] = g_c2[o]; pv[e][t] = pooled[o]; am[e][t] = amax[o];
-                }
-#pragma unroll
-            for (int e = 0; e < kMaxE; ++e)
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const float xh = (pv[e][t] - mu[e]) * rs[e];
-                    // eval: g_pooled = gamma * rstd * g_c2 and nothing else -- a non-finite xhat (a NaN token) must not reach g_X through 0 * xhat
-                    const float gp = (ga[e] * rs[e]) * (training ? gl[e][t] - c1[e] - xh * c2[e] : gl[e][t]);
-                    acc[e] += gp * f[t] * (0.125f + (am[e][t] == k[t] ? 1.0f : 0.0f));
-                }
-        }
-    };
-    constexpr int kRowChunk = 64;
-    if (e1 - s1 <= kRowChunk) {                               // every row of the models: a few dozen entries at most
-        add_entries(s1, e1);
-    } else {
-        // A row listed by hundreds of groups is summed in chunks of kRowChunk entries: every chunk after the first starts a fresh partial
-        // sum, so its terms meet a small accumulator and only one addition per chunk meets the large one -- the rounding of those
-        // additions is what a long row's error consists of.
-        float head[kMaxE];
-#pragma unroll
-        for (int e = 0; e < kMaxE; ++e) head[e] = 0.0f;
-        for (int c0 = s1; c0 < e1; c0 += kRowChunk) {
-            if (c0 > s1) {
-#pragma unroll
-                for (int e = 0; e < kMaxE; ++e) { head[e] += acc[e]; acc[e] = 0.0f; }
-            }
-            add_entries(c0, min(e1, c0 + kRowChunk));
-        }
-#pragma unroll
-        for (int e = 0; e < kMaxE; ++e) acc[e] += head[e];
-    }
-#pragma unroll
-    for (int e = 0; e < kMaxE; ++e) { const int c = lane + 64 * e; if (c < D) g_X[(size_t)r * D + c] = acc[e]; }
+    prop_x_csr_row<E, false>(g_out, g_c2, pooled, amax, mean, rstd, gamma, g_gamma, g_beta, u, keep, start1, perm1, start2, perm2, nullptr, 1.0f, 1,
+                             g_X, nullptr, rows, groups, D, training);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -673,12 +755,8 @@ __global__ __launch_bounds__(256) void prop_x_csr_kernel(const float *__restrict
 //     x3[r] = x2[r] + dp_scale(u_dp, r / Lp) * (m[r] + mbias)          (rowln_fwd_kernel without a LayerNorm, block.hip)
 // and was written by a launch of its own only to be gathered here.  The two kernels below are prop_pool_stats_kernel and
 // prop_x_csr_kernel with that row formed (forward) / its two gradients written (backward) in place: the same operations in the
-// same order, so every output is bit-identical to the composition with the row kernels.  They are kernels of their own so that
-// the plain ones keep their code.
-__device__ __forceinline__ float res_scale(const float *u_dp, float keep_dp, int b) {
-    return u_dp ? floorf(keep_dp + u_dp[b]) / keep_dp : 1.0f;
-}
-
+// same order, so every output is bit-identical to the composition with the row kernels.  The forward one is a kernel of its own so that
+// the plain one keeps its code; the backward pair shares prop_x_csr_row above.
 __global__ __launch_bounds__(256) void prop_pool_res_stats_kernel(const float *__restrict__ x2, const float *__restrict__ m,
                                                                   const float *__restrict__ mbias, const float *__restrict__ u_dp,
                                                                   float keep_dp, int Lp, const int32_t *__restrict__ i1,
@@ -734,8 +812,8 @@ __global__ __launch_bounds__(256) void prop_pool_res_stats_kernel(const float *_
     }
 }
 
-// prop_x_csr_kernel writing the gradient of x3 as the two gradients of the residual: g_x2[r] = g_X[r], g_m[r] = g_X[r] * dp_scale
-// (rowln_bwd_kernel without a LayerNorm: a copy and a scale of the row this kernel holds in registers).
+// prop_x_csr_kernel writing the gradient of x3 as the two gradients of the residual (prop_x_csr_row<E, true>)
+template <int E>
 __global__ __launch_bounds__(256) void prop_x_csr_res_kernel(const float *__restrict__ g_out, const float *__restrict__ g_c2,
                                                              const float *__restrict__ pooled, const uint8_t *__restrict__ amax,
                                                              const float *__restrict__ mean, const float *__restrict__ rstd,
@@ -746,86 +824,8 @@ __global__ __launch_bounds__(256) void prop_x_csr_res_kernel(const float *__rest
                                                              const float *__restrict__ u_dp, float keep_dp, int Lp,
                                                              float *__restrict__ g_x2, float *__restrict__ g_m, int rows, int groups, int D,
                                                              int training) {
-    const int wgx = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);
-    const int lane = threadIdx.x & 63;
-    const int r = wgx * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (r >= rows) return;
-    const int s1 = start1[r], e1 = start1[r + 1], s2 = start2[r], e2 = start2[r + 1];
-    const float sc = res_scale(u_dp, keep_dp, r / Lp);
-    int cc[kMaxE];
-    float acc[kMaxE], mu[kMaxE], rs[kMaxE], ga[kMaxE], c1[kMaxE], c2[kMaxE];
-    const float inv_n = 1.0f / (float)groups;
-#pragma unroll
-    for (int e = 0; e < kMaxE; ++e) {
-        cc[e] = min(lane + 64 * e, D - 1);
-        acc[e] = g_out[(size_t)r * D + cc[e]];
-        mu[e] = mean[cc[e]]; rs[e] = rstd[cc[e]]; ga[e] = gamma[cc[e]];
-        c1[e] = 0.0f; c2[e] = 0.0f;
-    }
-    if (training) {
-#pragma unroll
-        for (int e = 0; e < kMaxE; ++e) { c1[e] = g_beta[cc[e]]; c2[e] = g_gamma[cc[e]]; }
-    }
-#pragma unroll
-    for (int e = 0; e < kMaxE; ++e) { c1[e] *= inv_n; c2[e] *= inv_n; }
-    for (int h0 = s2; h0 < e2; h0 += 2) {
-        const int m0 = perm2[h0], m1 = perm2[min(h0 + 1, e2 - 1)];
-        float a0[kMaxE], a1[kMaxE];
-#pragma unroll
-        for (int e = 0; e < kMaxE; ++e) { a0[e] = g_c2[(size_t)m0 * D + cc[e]]; a1[e] = g_c2[(size_t)m1 * D + cc[e]]; }
-        const float f1 = h0 + 1 < e2 ? 0.3f : 0.0f;
-#pragma unroll
-        for (int e = 0; e < kMaxE; ++e) { acc[e] += 0.3f * a0[e]; acc[e] += f1 * a1[e]; }
-    }
-    auto add_entries = [&](int b0, int b1) {
-        for (int h0 = b0; h0 < b1; h0 += 4) {
-            int g[4], k[4];
-            float f[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) { const int q = perm1[min(h0 + t, b1 - 1)]; g[t] = q / kNb; k[t] = q - g[t] * kNb; }
-#pragma unroll
-            for (int t = 0; t < 4; ++t) f[t] = h0 + t < b1 ? 1.0f + (u ? floorf(keep + u[g[t]]) / keep : 1.0f) : 0.0f;
-            float gl[kMaxE][4], pv[kMaxE][4];
-            int am[kMaxE][4];
-#pragma unroll
-            for (int e = 0; e < kMaxE; ++e)
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const size_t o = (size_t)g[t] * D + cc[e];
-                    gl[e][t] = g_c2[o]; pv[e][t] = pooled[o]; am[e][t] = amax[o];
-                }
-#pragma unroll
-            for (int e = 0; e < kMaxE; ++e)
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const float xh = (pv[e][t] - mu[e]) * rs[e];
-                    const float gp = (ga[e] * rs[e]) * (training ? gl[e][t] - c1[e] - xh * c2[e] : gl[e][t]);
-                    acc[e] += gp * f[t] * (0.125f + (am[e][t] == k[t] ? 1.0f : 0.0f));
-                }
-        }
-    };
-    constexpr int kRowChunk = 64;                             // long rows: chunked partial sums, as prop_x_csr_kernel
-    if (e1 - s1 <= kRowChunk) {
-        add_entries(s1, e1);
-    } else {
-        float head[kMaxE];
-#pragma unroll
-        for (int e = 0; e < kMaxE; ++e) head[e] = 0.0f;
-        for (int c0 = s1; c0 < e1; c0 += kRowChunk) {
-            if (c0 > s1) {
-#pragma unroll
-                for (int e = 0; e < kMaxE; ++e) { head[e] += acc[e]; acc[e] = 0.0f; }
-            }
-            add_entries(c0, min(e1, c0 + kRowChunk));
-        }
-#pragma unroll
-        for (int e = 0; e < kMaxE; ++e) acc[e] += head[e];
-    }
-#pragma unroll
-    for (int e = 0; e < kMaxE; ++e) {
-        const int c = lane + 64 * e;
-        if (c < D) { g_x2[(size_t)r * D + c] = acc[e]; g_m[(size_t)r * D + c] = acc[e] * sc; }
-    }
+    prop_x_csr_row<E, true>(g_out, g_c2, pooled, amax, mean, rstd, gamma, g_gamma, g_beta, u, keep, start1, perm1, start2, perm2, u_dp, keep_dp, Lp,
+                            g_x2, g_m, rows, groups, D, training);
 }
 
 // Index lists of the propagation step for one forward, in ONE launch (the reference spends ~30 small torch kernels on
@@ -1119,10 +1119,10 @@ extern "C" int upp_prop_bwd(const float *g_out, const float *pooled, const uint8
     if (D > 64 * kMaxE) return UPP_E_RANGE;
     hipStream_t st = (hipStream_t)stream;
     const int groups = B * G2, wgs = (groups + 3) / 4;
-    hipLaunchKernelGGL(prop_c2_csr_kernel, dim3(wgs), dim3(256), 0, st, g_out, start8, perm8, w8, pooled, mean, rstd, g_c2, part, B, Lp, T,
+    PROP_LAUNCH_E(D, prop_c2_csr_kernel, dim3(wgs), dim3(256), 0, st, g_out, start8, perm8, w8, pooled, mean, rstd, g_c2, part, B, Lp, T,
                        G2, D);
     hipLaunchKernelGGL(prop_bn_grad_kernel, dim3((D + 63) / 64), dim3(256), 0, st, part, wgs, D, g_gamma, g_beta);
-    hipLaunchKernelGGL(prop_x_csr_kernel, rows_grid((long long)B * Lp), dim3(256), 0, st, g_out, g_c2, pooled, amax, mean, rstd, gamma,
+    PROP_LAUNCH_E(D, prop_x_csr_kernel, rows_grid((long long)B * Lp), dim3(256), 0, st, g_out, g_c2, pooled, amax, mean, rstd, gamma,
                        g_gamma, g_beta, u, keep, start1, perm1, start2, perm2, g_X, B * Lp, groups, D, training);
     return upp_launch_status();
 }
@@ -1155,10 +1155,10 @@ extern "C" int upp_prop_res_bwd(const float *g_out, const float *pooled, const u
     if (D > 64 * kMaxE) return UPP_E_RANGE;
     hipStream_t st = (hipStream_t)stream;
     const int groups = B * G2, wgs = (groups + 3) / 4;
-    hipLaunchKernelGGL(prop_c2_csr_kernel, dim3(wgs), dim3(256), 0, st, g_out, start8, perm8, w8, pooled, mean, rstd, g_c2, part, B, Lp, T,
+    PROP_LAUNCH_E(D, prop_c2_csr_kernel, dim3(wgs), dim3(256), 0, st, g_out, start8, perm8, w8, pooled, mean, rstd, g_c2, part, B, Lp, T,
                        G2, D);
     hipLaunchKernelGGL(prop_bn_grad_kernel, dim3((D + 63) / 64), dim3(256), 0, st, part, wgs, D, g_gamma, g_beta);
-    hipLaunchKernelGGL(prop_x_csr_res_kernel, rows_grid((long long)B * Lp), dim3(256), 0, st, g_out, g_c2, pooled, amax, mean, rstd, gamma,
+    PROP_LAUNCH_E(D, prop_x_csr_res_kernel, rows_grid((long long)B * Lp), dim3(256), 0, st, g_out, g_c2, pooled, amax, mean, rstd, gamma,
                        g_gamma, g_beta, u, keep, start1, perm1, start2, perm2, u_dp, keep_dp, Lp, g_x2, g_m, B * Lp, groups, D, training);
     return upp_launch_status();
 }
