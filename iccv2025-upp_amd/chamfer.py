@@ -7,4 +7,4 @@ def forward(xyz1, xyz2):
 
 
 def backward(xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2):
-    return list(ops.chamfer_bwd(xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2))
+    return list(ops.chamfer_bwd(xyz1, xyz2, idx1, idx2, grad_dist1.contiguous(), grad_dist2.contiguous()))

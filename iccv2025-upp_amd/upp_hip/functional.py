@@ -111,7 +111,7 @@ class ChamferFunction(Function):
     @staticmethod
     def backward(ctx, grad_dist1, grad_dist2):
         xyz1, xyz2, idx1, idx2 = ctx.saved_tensors
-        return ops.chamfer_bwd(xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2, deterministic=DETERMINISTIC)
+        return ops.chamfer_bwd(xyz1, xyz2, idx1, idx2, grad_dist1.contiguous(), grad_dist2.contiguous(), deterministic=DETERMINISTIC)
 
 
 class _ChamferLoss(Function):

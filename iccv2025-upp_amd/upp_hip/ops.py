@@ -1035,19 +1035,33 @@ def chamfer_fwd(xyz1, xyz2):
     return dist1, dist2, idx1, idx2
 
 
-def chamfer_bwd(xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2, deterministic=False):
-    """deterministic: every gradient row = own term, then the other cloud's terms in ascending index (upp_chamfer_bwd_det,
-    include/upp_hip.h) instead of f32 atomics."""
+def _need_i32(t, name, shape):
+    """_need for an int32 index operand of exactly `shape`.  Metadata only; the VALUES cannot be checked without a synchronisation."""
+    _need(t, name, torch.int32)
+    if tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def _cloud_pair(xyz1, xyz2):
+    """-> (B, n, m) of two f32 clouds (B,n,3), (B,m,3) on one device."""
     _need(xyz1, "xyz1", torch.float32, 3, 3)
     _need(xyz2, "xyz2", torch.float32, 3, 3)
-    _need(idx1, "idx1", torch.int32, 2)
-    _need(idx2, "idx2", torch.int32, 2)
-    grad_dist1 = grad_dist1.contiguous()
-    grad_dist2 = grad_dist2.contiguous()
-    _need(grad_dist1, "grad_dist1", torch.float32, 2)
-    _need(grad_dist2, "grad_dist2", torch.float32, 2)
-    B, n, _ = xyz1.shape
-    m = xyz2.shape[1]
+    _same_device(xyz1, xyz2)
+    if xyz2.shape[0] != xyz1.shape[0]:
+        raise RuntimeError("xyz1 and xyz2 batch sizes differ")
+    return xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
+
+
+def chamfer_bwd(xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2, deterministic=False):
+    """deterministic: every gradient row = own term, then the other cloud's terms in ascending index (upp_chamfer_bwd_det,
+    include/upp_hip.h) instead of f32 atomics.  Every tensor is checked from its metadata (device, dtype, contiguity, exact shape); the
+    index VALUES are the caller's: they must lie inside the other cloud (include/upp_hip.h)."""
+    B, n, m = _cloud_pair(xyz1, xyz2)
+    _need_i32(idx1, "idx1", (B, n))
+    _need_i32(idx2, "idx2", (B, m))
+    _need_f32(grad_dist1, "grad_dist1", (B, n))
+    _need_f32(grad_dist2, "grad_dist2", (B, m))
+    _same_device(xyz1, idx1, idx2, grad_dist1, grad_dist2)
     g1 = torch.empty_like(xyz1)          # (overwritten by the kernel: include/upp_hip.h)
     g2 = torch.empty_like(xyz2)
     if B == 0:
@@ -1061,8 +1075,13 @@ def chamfer_loss(dist1, dist2, l1):
     """-> (loss (1,), fac1 (B,n), fac2 (B,m)): the reduction of ChamferDistanceL1 (l1) / L2 and d loss / d dist (upp_chamfer_loss)."""
     _need(dist1, "dist1", torch.float32, 2)
     _need(dist2, "dist2", torch.float32, 2)
+    _same_device(dist1, dist2)
     B, n = dist1.shape
     m = dist2.shape[1]
+    if dist2.shape[0] != B:
+        raise RuntimeError("dist1 and dist2 batch sizes differ")
+    if B < 1 or n < 1 or m < 1:
+        raise RuntimeError("chamfer_loss: a mean over nothing")
     dev = dist1.device
     loss = torch.empty((1,), dtype=torch.float32, device=dev)
     fac1, fac2 = torch.empty_like(dist1), torch.empty_like(dist2)
@@ -1091,13 +1110,9 @@ def emd_approxmatch(xyz1, xyz2):
 
 def emd_matchcost(xyz1, xyz2, match, deterministic=False):
     """deterministic: the 64-point tiles' partial costs summed in ascending tile order (upp_emd_matchcost_det) instead of atomics."""
-    _need(xyz1, "xyz1", torch.float32, 3, 3)
-    _need(xyz2, "xyz2", torch.float32, 3, 3)
-    _need(match, "match", torch.float32, 3)
-    B, n, _ = xyz1.shape
-    m = xyz2.shape[1]
-    if tuple(match.shape) != (B, m, n):
-        raise RuntimeError("match must be (B, n2, n1)")
+    B, n, m = _cloud_pair(xyz1, xyz2)
+    _need_f32(match, "match", (B, m, n))
+    _same_device(xyz1, match)
     cost = torch.empty((B,), dtype=torch.float32, device=xyz1.device)
     if B == 0:
         return cost
@@ -1111,12 +1126,10 @@ def emd_matchcost(xyz1, xyz2, match, deterministic=False):
 
 
 def emd_matchcost_bwd(grad_cost, xyz1, xyz2, match):
-    _need(grad_cost, "grad_cost", torch.float32, 1)
-    _need(xyz1, "xyz1", torch.float32, 3, 3)
-    _need(xyz2, "xyz2", torch.float32, 3, 3)
-    _need(match, "match", torch.float32, 3)
-    B, n, _ = xyz1.shape
-    m = xyz2.shape[1]
+    B, n, m = _cloud_pair(xyz1, xyz2)
+    _need_f32(grad_cost, "grad_cost", (B,))
+    _need_f32(match, "match", (B, m, n))
+    _same_device(xyz1, grad_cost, match)
     g1 = torch.empty_like(xyz1)
     g2 = torch.empty_like(xyz2)
     if B == 0:

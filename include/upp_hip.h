@@ -518,7 +518,15 @@ int upp_region_attn_bwd_det(const float *q, const int64_t *idx, const float *PK,
  * Backward: g1 (B,n,3) and g2 (B,m,3) are OVERWRITTEN (no pre-zeroing: the reference's wrapper allocates zeros and its kernel adds,
  * chamfer.cu:194-199,215-222); sums by f32 atomics in an unspecified order as there -- in the LDS, one workgroup per cloud pair, when
  * both gradient arrays fit (n + m <= 5,461), in global memory otherwise.  The same sums in a defined order: upp_chamfer_bwd_det
- * ("deterministic scatter-adds" below). */
+ * ("deterministic scatter-adds" below).
+ * idx1 / idx2 are TRUSTED by upp_chamfer_bwd: every idx1[b][j] must lie in [0, m) and every idx2[b][i] in [0, n), as upp_chamfer_fwd
+ * writes them.  Neither the library nor its torch wrapper (which checks device, dtype, contiguity and the exact shape of every tensor
+ * from metadata) can check the values without a synchronisation; an index outside the other cloud is a read and an atomic add outside
+ * the caller's arrays.
+ * NaN coordinates (a deviation from the reference): the comparison is `d < best`, which is false for NaN.  A query point with a NaN
+ * coordinate gets dist = +inf and idx = 0 (chamfer.cu's `k == 0 ||` takes the first candidate unconditionally and returns NaN); a
+ * NaN point of the other cloud is skipped by every other query.  The NaN is not lost: the point's own distance in its own direction
+ * is non-finite, so both module losses (upp_chamfer_loss, L1 and L2) are non-finite; the other samples of the batch are untouched. */
 int upp_chamfer_fwd(const float *xyz1, const float *xyz2,
                     float *dist1, float *dist2, int32_t *idx1, int32_t *idx2,
                     int B, int n, int m, void *stream);
@@ -542,7 +550,19 @@ int upp_chamfer_loss(const float *dist1, const float *dist2, int B, int n, int m
  *   work  f32 scratch of upp_emd_work_floats(B,n,m) elements
  *   cost  (B) f32 out: sum_{k,l} |xyz1[k]-xyz2[l]|^2 * match[l,k]
  *   grad1 (B,n,3), grad2 (B,m,3) out (overwritten); match is a constant.
- * Limits: n, m >= 1. */
+ * Limits: n, m >= 1 (a cloud larger than the 1,024-point LDS tile is staged tile by tile).
+ * After upp_emd_approxmatch, work holds the auction's state, in this order (csrc/emd.hip carve(); upp_emd_work_floats = 11 B (n + m)):
+ *   remainL [B][n]      the mass each point of xyz1 still has after level 8 (the last level's own decrement is never applied:
+ *                       nothing reads it)
+ *   remainR [B][m]      the mass each point of xyz2 still has after all 10 levels
+ *   ratioL  [10][B][n]  per level it (-4^7 ... -4^-1, then 0): remainL / (1e-9 + sum_l exp(level d) remainR[l]) at the start of the level
+ *   ratioR  [10][B][m]  per level: min(remainR / (sumr + 1e-9), 1) remainR with sumr = remainR sum_k exp(level d) ratioL[it][k]
+ * and match[b][l][k] = sum_it exp(level_it d[l][k]) ratioL[it][k] ratioR[it][l], accumulated in level order and stored once.  Every
+ * element is written on every call (nothing to zero-fill).  tests/test_gpu_losses.py checks each level against float64 from these
+ * factors.
+ * NaN coordinates: as in the reference, fmaxf(0, NaN) = 0 and fminf(NaN, 1) = 1 in the remain / ratio updates, so a NaN does not
+ * spread through the remains; it reaches match through the exponentials of the poisoned point's row or column, and the cost of that
+ * sample is NaN.  The other samples of the batch are untouched. */
 long long upp_emd_work_floats(int B, int n, int m);
 int upp_emd_approxmatch(const float *xyz1, const float *xyz2, float *match, float *work,
                         int B, int n, int m, void *stream);

@@ -664,7 +664,8 @@ def bad_versions(t):
 
 # the tensor that DEFINES a size nothing else pins: a larger one is another valid call
 DEFINES = {("cls_pool_fwd", "x", "first"), ("ce_acc", "logits", "last"), ("bn_rows_fwd", "x", "first"),
-           ("interp_fwd", "out", "last")}
+           ("interp_fwd", "out", "last"),
+           ("chamfer_loss", "dist1", "last"), ("chamfer_loss", "dist2", "last")}          # (tests/test_gpu_losses.py: n and m of the two distance arrays)
 
 
 def refuse_wrong_tensors(name, fn, tensors):
