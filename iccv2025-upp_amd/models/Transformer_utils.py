@@ -23,6 +23,8 @@ reference's, so its checkpoints load with strict=True.
                                             and head and the max over its rows, no (B, N, k, C) tensor and no (B H N, k, k) scores (README
                                             "Region-wise deformable attention")
     DeformableAttnBlock, DeformableAttnDecoderBlock, RegionWiseBlock   the reference's fixed layouts around them
+    _neighbour_list, _sample                what the modules above share: the head of every forward (defaults, checks, the neighbour
+                                            list) and the deformable modules' sampling positions (offset head, three_nn, weights)
 The fused attention path is taken for HIP f32 tensors with head_dim 64, N <= HF.ATTN_MAX_L and no active attention dropout; otherwise
 the same module runs the torch formulation, and a HIP tensor that was declined is recorded by HF.note_declined.
 
@@ -108,6 +110,28 @@ class Attention(L.Attention):
         return self._masked_torch(x, torch_cpu.prefix_mask(N, N, N - D, N - D, x.device))
 
 
+def _neighbour_list(m, q, q_pos, v, v_pos, idx, denoise_length, branch=False):
+    """The head of every forward below, for module m (its dim and k) -> (v, v_pos, idx): v / v_pos default to q / q_pos (the self form),
+    the shapes are checked, and idx (B,N,k) is searched when None -- with denoise_length by denoise_knn, which is for the self form and
+    the list computed here only.  branch: DynamicGraphAttention, whose callers can supply that list and know the form as a branch."""
+    if denoise_length is not None:
+        if idx is not None and not branch:
+            raise ValueError("denoise_length needs the list computed here, but idx is given")
+        if v is not None or v_pos is not None:
+            raise ValueError("denoise_length applies to the self %s only, but v / v_pos is given" % ("branch" if branch else "form"))
+    v = q if v is None else v
+    v_pos = q_pos if v_pos is None else v_pos
+    if q_pos.dim() != 3 or q_pos.size(-1) != 3 or v_pos.dim() != 3 or v_pos.size(-1) != 3:
+        raise ValueError("q_pos and v_pos must be (B, N, 3), got %s and %s" % (tuple(q_pos.shape), tuple(v_pos.shape)))
+    if q.size(-1) != m.dim or v.size(-1) != m.dim:
+        raise ValueError("q and v must have %d channels, got %d and %d" % (m.dim, q.size(-1), v.size(-1)))
+    if idx is None:
+        idx = knn_point(m.k, v_pos, q_pos) if denoise_length is None else denoise_knn(m.k, q_pos, denoise_length)
+    if idx.shape != (q.shape[0], q.shape[1], m.k):
+        raise ValueError("idx must be (B, N, k) = %s, got %s" % ((q.shape[0], q.shape[1], m.k), tuple(idx.shape)))
+    return v, v_pos, idx
+
+
 class DynamicGraphAttention(nn.Module):
     """reference models/Transformer_utils.py:777-858: the graph feature of every query token over k neighbour tokens.
     forward(q (B,N,dim), q_pos (B,N,3), v=None, v_pos=None, idx=None, denoise_length=None) -> (B,N,dim); v / v_pos default to q / q_pos
@@ -122,18 +146,7 @@ class DynamicGraphAttention(nn.Module):
         self.knn_map = nn.Sequential(nn.Linear(dim * 2, dim), nn.LeakyReLU(negative_slope=0.2))
 
     def forward(self, q, q_pos, v=None, v_pos=None, idx=None, denoise_length=None):
-        if denoise_length is not None and (v is not None or v_pos is not None):
-            raise ValueError("denoise_length applies to the self branch only, but v / v_pos is given")
-        v = q if v is None else v
-        v_pos = q_pos if v_pos is None else v_pos
-        if q_pos.dim() != 3 or q_pos.size(-1) != 3 or v_pos.dim() != 3 or v_pos.size(-1) != 3:
-            raise ValueError("q_pos and v_pos must be (B, N, 3), got %s and %s" % (tuple(q_pos.shape), tuple(v_pos.shape)))
-        if q.size(-1) != self.dim or v.size(-1) != self.dim:
-            raise ValueError("q and v must have %d channels, got %d and %d" % (self.dim, q.size(-1), v.size(-1)))
-        if idx is None:
-            idx = knn_point(self.k, v_pos, q_pos) if denoise_length is None else denoise_knn(self.k, q_pos, denoise_length)
-        if idx.shape != (q.shape[0], q.shape[1], self.k):
-            raise ValueError("idx must be (B, N, k) = %s, got %s" % ((q.shape[0], q.shape[1], self.k), tuple(idx.shape)))
+        v, _, idx = _neighbour_list(self, q, q_pos, v, v_pos, idx, denoise_length, branch=True)
         return DecoderBlock.local_branch(self.knn_map, v, q, idx)
 
 
@@ -146,6 +159,50 @@ def shifted_three_nn(shift, known):
         return torch_cpu.three_nn(shift, known)
 
 
+def _sample(m, q_off, v, v_pos, idx, fused):
+    """The sampling positions of the deformable modules, for module m (proj_v_off, linear_offset, k, n_group, ball, trace_site): q_off
+    (B,N,dim) the query side of the offset head, v (B,NK,dim), v_pos (B,NK,3), idx (B,N,k) -> idx3 int32, w3 (B,G,N k,3).  Per group g of
+    c = dim / G channels, with linear_offset.0.weight = [Wa | Wb]: Linear([v_off_g[idx] ; q_g]) = A_g[idx] + Bq_g with A_g = v_off_g Wa^T
+    over the NK points and Bq_g = q_g Wb^T + b over the N queries; deform_offset does gather, LayerNorm, GELU, the 3-row Linear, tanh and
+    the shift; three_nn of the shifted positions among v_pos; weights by the reference's own r = 1 / (dist + 1e-8), r / r.sum(-1) in torch,
+    so that they carry its rounding.  fused: the library's kernels (G = 1 takes A / Bq as views and v_pos as it is: no copy); otherwise
+    torch operators on any device and dtype, which under upp_layers.POOL_TRACE record or replay idx3.  No gradient."""
+    B, N, _ = q_off.shape
+    NK, G, c, lin0, ln = v.shape[1], m.n_group, m.dim // m.n_group, m.linear_offset[0], m.linear_offset[1]
+    with torch.no_grad():
+        pos = v_pos.detach().contiguous()
+        if not fused:
+            A = torch.matmul(m.proj_v_off(v).view(B, NK, G, c).permute(0, 2, 1, 3), lin0.weight[:, :c].t())
+            Bq = torch.matmul(q_off.reshape(B, N, G, c).permute(0, 2, 1, 3), lin0.weight[:, c:].t()) + lin0.bias
+        else:
+            v_off = HF.linear(v.detach(), m.proj_v_off.weight, m.proj_v_off.bias)
+            Wa, Wb = lin0.weight[:, :c].contiguous(), lin0.weight[:, c:].contiguous()
+            if G == 1:
+                A, Bq = HF.linear(v_off, Wa).unsqueeze(1), HF.linear(q_off.detach(), Wb, lin0.bias).unsqueeze(1)
+            else:
+                vg, qg = _grouped(v_off, G), _grouped(q_off.detach(), G)
+                A = torch.stack([HF.linear(vg[g], Wa) for g in range(G)], dim=1)                    # (B,G,NK,C)
+                Bq = torch.stack([HF.linear(qg[g], Wb, lin0.bias) for g in range(G)], dim=1)        # (B,G,N,C)
+        shift = (HF if fused else torch_cpu).deform_offset(A, Bq, idx, pos, ln.weight, ln.bias, ln.eps, m.linear_offset[3].weight, ball=m.ball)
+        flat = shift.reshape(B * G, N * m.k, 3)
+        known = pos if G == 1 else pos.unsqueeze(1).expand(-1, G, -1, -1).reshape(B * G, NK, 3)
+        dist, idx3 = shifted_three_nn(flat, known)
+        if not fused and L.POOL_TRACE is not None:
+            # the recorded choice replaces this run's, and the distances follow it (slots beyond NK < 3 points stay at +inf)
+            idx3 = L.trace_idx(m.trace_site, idx3)
+            near = torch.gather(known, 1, idx3.long().reshape(B * G, -1, 1).expand(-1, -1, 3)).view(B * G, -1, 3, 3)
+            d = (flat.unsqueeze(2) - near).pow(2).sum(-1).sqrt()
+            dist = torch.where(torch.arange(3, device=d.device) < NK, d, torch.full_like(d, float('inf')))
+        r = 1.0 / (dist + 1e-8)
+        return idx3.view(B, G, N * m.k, 3), (r / torch.sum(r, dim=-1, keepdim=True)).view(B, G, N * m.k, 3)
+
+
+def _grouped(x, G):
+    """(B,M,dim) -> (G,B,M,dim / G) contiguous: the channel groups as whole matrices"""
+    B, M, C = x.shape
+    return x.view(B, M, G, C // G).permute(2, 0, 1, 3).contiguous()
+
+
 class DeformableLocalCrossAttention(nn.Module):
     """reference models/Transformer_utils.py:269-491: every query attends over k neighbour slots whose keys and values are
     interpolated at learned, shifted positions.  forward(q (B,N,dim), q_pos (B,N,3), v=None (B,NK,dim), v_pos=None (B,NK,3), idx=None
@@ -153,11 +210,8 @@ class DeformableLocalCrossAttention(nn.Module):
     form only; v, v_pos and idx must be None, as in the reference) the list is denoise_knn's.
     State-dict keys: proj_q, proj_k, proj_v, proj_v_off, proj, linear_offset.{0,1,3}.
 
-    Per group g of dim / n_group channels (c = dim / n_group, W0 = linear_offset.0.weight = [Wa | Wb]):
-        offset head     Linear([v_off_g[idx] ; q_g]) = A_g[idx] + Bq_g with A_g = v_off_g Wa^T over the NK points, Bq_g = q_g Wb^T + b over
-                        the N queries; HF.deform_offset does gather, LayerNorm, GELU, the 3-row Linear, tanh and the shift
-        three_nn        HF.three_nn of the shifted positions among v_pos; weights by the reference's own r = 1 / (dist + 1e-8),
-                        r / r.sum(-1) in torch, so that they carry its rounding
+    Per group g of c = dim / n_group channels:
+        idx3, w3        _sample with proj_q(q) on the query side: the offset head, three_nn of the shifted positions, the weights
         keys, values    proj_k(interp)[n,s] = b_k + sum_g sum_j w[g,n,s,j] PK_g[idx3[g,n,s,j]] with PK_g = v_g Wk[:, g-slice]^T over the
                         NK points, likewise proj_v; HF.deform_attention gathers, scores, normalises and sums
     three_nn is not differentiable (as upstream marks dist and idx), so the offset branch -- proj_v_off, linear_offset -- and the
@@ -196,94 +250,37 @@ class DeformableLocalCrossAttention(nn.Module):
                 and not (self.training and self.attn_drop.p > 0) and L.POOL_TRACE is None
                 and ops.deform_attn_usable(q.shape[0], q.shape[1], v.shape[1], self.k, self.num_heads, self.n_group))
 
-    def _grouped(self, x):
-        """(B,M,dim) -> (G,B,M,c) contiguous: the channel groups as whole matrices"""
-        B, M, _ = x.shape
-        return x.view(B, M, self.n_group, self.group_dims).permute(2, 0, 1, 3).contiguous()
-
-    def _weights(self, dist):
-        r = 1.0 / (dist + 1e-8)
-        return r / torch.sum(r, dim=-1, keepdim=True)
-
-    def _fused_operands(self, q, v, v_pos, idx):
-        """-> (proj_q(q), PK, PV, idx3, w3): everything in front of the attention core, on the library's kernels"""
-        B, N, C = q.shape
-        NK, G, c, lin0, ln = v.shape[1], self.n_group, self.group_dims, self.linear_offset[0], self.linear_offset[1]
-        qp = HF.linear(q, self.proj_q.weight, self.proj_q.bias)
-        with torch.no_grad():
-            v_off = HF.linear(v.detach(), self.proj_v_off.weight, self.proj_v_off.bias)
-            Wa, Wb = lin0.weight[:, :c].contiguous(), lin0.weight[:, c:].contiguous()
-            vg, qg = self._grouped(v_off), self._grouped(qp.detach())
-            A = torch.stack([HF.linear(vg[g], Wa) for g in range(G)], dim=1)                    # (B,G,NK,C)
-            Bq = torch.stack([HF.linear(qg[g], Wb, lin0.bias) for g in range(G)], dim=1)        # (B,G,N,C)
-            pos = v_pos.detach().contiguous()
-            shift = HF.deform_offset(A, Bq, idx, pos, ln.weight, ln.bias, ln.eps, self.linear_offset[3].weight, ball=self.ball)
-            known = pos.unsqueeze(1).expand(-1, G, -1, -1).reshape(B * G, NK, 3)
-            dist, idx3 = shifted_three_nn(shift.view(B * G, N * self.k, 3), known)
-            w3 = self._weights(dist).view(B, G, N * self.k, 3)
-            idx3 = idx3.view(B, G, N * self.k, 3)
-        vg = self._grouped(v)
+    def _operands(self, q, v, v_pos, idx, fused):
+        """-> (proj_q(q), PK, PV, idx3, w3): everything in front of the attention core, on the library's kernels (fused) or as torch
+        operators, any device and dtype"""
+        C, G, c = self.dim, self.n_group, self.group_dims
+        qp = HF.linear(q, self.proj_q.weight, self.proj_q.bias) if fused else self.proj_q(q)
+        idx3, w3 = _sample(self, qp.detach(), v, v_pos, idx, fused)
         Wk, Wv = self.proj_k.weight, self.proj_v.weight
-        PK = torch.stack([HF.linear(vg[g], Wk[:, g * c:(g + 1) * c].contiguous()) for g in range(G)], dim=1)
-        PV = torch.stack([HF.linear(vg[g], Wv[:, g * c:(g + 1) * c].contiguous()) for g in range(G)], dim=1)
+        if fused:
+            vg = _grouped(v, G)
+            PK = torch.stack([HF.linear(vg[g], Wk[:, g * c:(g + 1) * c].contiguous()) for g in range(G)], dim=1)
+            PV = torch.stack([HF.linear(vg[g], Wv[:, g * c:(g + 1) * c].contiguous()) for g in range(G)], dim=1)
+        else:
+            vg = v.view(v.shape[0], v.shape[1], G, c).permute(0, 2, 1, 3)
+            PK = torch.matmul(vg, Wk.view(C, G, c).permute(1, 2, 0))
+            PV = torch.matmul(vg, Wv.view(C, G, c).permute(1, 2, 0))
         return qp, PK, PV, idx3, w3
 
     def _fused(self, q, v, v_pos, idx):
-        qp, PK, PV, idx3, w3 = self._fused_operands(q, v, v_pos, idx)
+        qp, PK, PV, idx3, w3 = self._operands(q, v, v_pos, idx, True)
         ctx = HF.deform_attention(qp, PK, PV, self.proj_k.bias, self.proj_v.bias, idx3, w3, self.num_heads, self.scale)
         return self.proj_drop(HF.linear(ctx, self.proj.weight, self.proj.bias))
 
-    def _torch_operands(self, q, v, v_pos, idx):
-        """the same operands as torch operators, any device and dtype"""
-        B, N, C = q.shape
-        NK, G, c, lin0, ln = v.shape[1], self.n_group, self.group_dims, self.linear_offset[0], self.linear_offset[1]
-        qp = self.proj_q(q)
-        with torch.no_grad():
-            pos = v_pos.detach()
-            vg = self.proj_v_off(v).view(B, NK, G, c).permute(0, 2, 1, 3)
-            qg = qp.view(B, N, G, c).permute(0, 2, 1, 3)
-            A = torch.matmul(vg, lin0.weight[:, :c].t())
-            Bq = torch.matmul(qg, lin0.weight[:, c:].t()) + lin0.bias
-            shift = torch_cpu.deform_offset(A, Bq, idx, pos, ln.weight, ln.bias, ln.eps, self.linear_offset[3].weight, ball=self.ball)
-            known = pos.unsqueeze(1).expand(-1, G, -1, -1).reshape(B * G, NK, 3)
-            flat = shift.reshape(B * G, N * self.k, 3)
-            dist, idx3 = shifted_three_nn(flat, known)
-            if L.POOL_TRACE is not None:
-                # the recorded choice replaces this run's, and the distances follow it (slots beyond NK < 3 points stay at +inf)
-                idx3 = L.trace_idx(self.trace_site, idx3)
-                near = torch.gather(known, 1, idx3.long().reshape(B * G, -1, 1).expand(-1, -1, 3)).view(B * G, -1, 3, 3)
-                d = (flat.unsqueeze(2) - near).pow(2).sum(-1).sqrt()
-                dist = torch.where(torch.arange(3, device=d.device) < NK, d, torch.full_like(d, float('inf')))
-            w3 = self._weights(dist).view(B, G, N * self.k, 3)
-            idx3 = idx3.view(B, G, N * self.k, 3)
-        vg = v.view(B, NK, G, c).permute(0, 2, 1, 3)
-        PK = torch.matmul(vg, self.proj_k.weight.view(C, G, c).permute(1, 2, 0))
-        PV = torch.matmul(vg, self.proj_v.weight.view(C, G, c).permute(1, 2, 0))
-        return qp, PK, PV, idx3, w3
-
     def _torch(self, q, v, v_pos, idx):
         """the same restatement as torch operators, any device and dtype"""
-        qp, PK, PV, idx3, w3 = self._torch_operands(q, v, v_pos, idx)
+        qp, PK, PV, idx3, w3 = self._operands(q, v, v_pos, idx, False)
         drop = self.attn_drop if self.training and self.attn_drop.p > 0 else None
         ctx = torch_cpu.deform_attention(qp, PK, PV, self.proj_k.bias, self.proj_v.bias, idx3, w3, self.num_heads, self.scale, drop)
         return self.proj_drop(self.proj(ctx))
 
     def forward(self, q, q_pos, v=None, v_pos=None, idx=None, denoise_length=None):
-        if denoise_length is not None:
-            if idx is not None:
-                raise ValueError("denoise_length needs the list computed here, but idx is given")
-            if v is not None or v_pos is not None:
-                raise ValueError("denoise_length applies to the self form only, but v / v_pos is given")
-        v = q if v is None else v
-        v_pos = q_pos if v_pos is None else v_pos
-        if q_pos.dim() != 3 or q_pos.size(-1) != 3 or v_pos.dim() != 3 or v_pos.size(-1) != 3:
-            raise ValueError("q_pos and v_pos must be (B, N, 3), got %s and %s" % (tuple(q_pos.shape), tuple(v_pos.shape)))
-        if q.size(-1) != self.dim or v.size(-1) != self.dim:
-            raise ValueError("q and v must have %d channels, got %d and %d" % (self.dim, q.size(-1), v.size(-1)))
-        if idx is None:
-            idx = knn_point(self.k, v_pos, q_pos) if denoise_length is None else denoise_knn(self.k, q_pos, denoise_length)
-        if idx.shape != (q.shape[0], q.shape[1], self.k):
-            raise ValueError("idx must be (B, N, k) = %s, got %s" % ((q.shape[0], q.shape[1], self.k), tuple(idx.shape)))
+        v, v_pos, idx = _neighbour_list(self, q, q_pos, v, v_pos, idx, denoise_length)
         idx = idx.long()
         if self.fusable(q, v):
             return self._fused(q, v, v_pos, idx)
@@ -328,27 +325,19 @@ class DeformableLocalAttention(DeformableLocalCrossAttention):
         return (super().fusable(q, v) and ops.region_attn_usable(q.shape[0], q.shape[1], v.shape[1], self.k, self.num_heads, self.n_group))
 
     def _fused(self, q, v, v_pos, idx):
-        qp, PK, PV, idx3, w3 = self._fused_operands(q, v, v_pos, idx)
+        qp, PK, PV, idx3, w3 = self._operands(q, v, v_pos, idx, True)
         out = HF.region_attention(qp, idx, PK, PV, self.proj_k.bias, self.proj_v.bias, idx3, w3, self.num_heads, self.scale)
         return self.proj_drop(HF.linear(out, self.proj.weight, self.proj.bias))
 
     def _torch(self, q, v, v_pos, idx):
-        qp, PK, PV, idx3, w3 = self._torch_operands(q, v, v_pos, idx)
+        qp, PK, PV, idx3, w3 = self._operands(q, v, v_pos, idx, False)
         drop = self.attn_drop if self.training and self.attn_drop.p > 0 else None
         pool = None if L.POOL_TRACE is None else (lambda y: L.max_over(y, 2, 'region_attention.max'))
         out = torch_cpu.region_attention(qp, idx, PK, PV, self.proj_k.bias, self.proj_v.bias, idx3, w3, self.num_heads, self.scale, drop, pool)
         return self.proj_drop(self.proj(out))
 
     def forward(self, x, pos, idx=None):
-        if pos.dim() != 3 or pos.size(-1) != 3:
-            raise ValueError("pos must be (B, N, 3), got %s" % (tuple(pos.shape),))
-        if x.size(-1) != self.dim:
-            raise ValueError("x must have %d channels, got %d" % (self.dim, x.size(-1)))
-        if idx is None:
-            idx = knn_point(self.k, pos, pos)
-        if idx.shape != (x.shape[0], x.shape[1], self.k):
-            raise ValueError("idx must be (B, N, k) = %s, got %s" % ((x.shape[0], x.shape[1], self.k), tuple(idx.shape)))
-        idx = idx.long()
+        idx = _neighbour_list(self, x, pos, None, None, idx, None)[2].long()
         if self.fusable(x, x):
             return self._fused(x, x, pos, idx)
         if x.is_cuda and L.POOL_TRACE is None:
@@ -364,12 +353,9 @@ class improvedDeformableLocalGraphAttention(nn.Module):
     (the self form).  With denoise_length = D (self form only; v, v_pos and idx must be None, as the reference asserts) the list is
     denoise_knn's.  State-dict keys: proj_v_off, linear_offset.{0,1,3}, knn_map.0.
 
-    With linear_offset.0.weight = [Wa | Wb] and knn_map.0.weight = [W1 | W2] (no proj_q, no heads, no channel groups: G = 1):
-        offset head     Linear([v_off[idx] ; q]) = A[idx] + Bq with A = v_off Wa^T over the NK points and Bq = q Wb^T + b over the N
-                        queries (the RAW q); HF.deform_offset(ball=True) does gather, LayerNorm, GELU, the 3-row Linear, tanh, the scale
-                        0.5 (max_s pos[idx] - min_s pos[idx]) and the shift
-        three_nn        HF.three_nn of the shifted positions among v_pos; weights by the reference's own r = 1 / (dist + 1e-8),
-                        r / r.sum(-1) in torch, so that they carry its rounding
+    With knn_map.0.weight = [W1 | W2] (no proj_q, no heads, no channel groups: G = 1):
+        idx3, w3        _sample with the RAW q on the query side and ball = True -- the tanh scaled by 0.5 (max_s pos[idx] - min_s
+                        pos[idx]) -- and of its (B,1,N k,3) results the G = 1 slice
         graph feature   knn_map([f - q ; q]) = W1 f + (W2 - W1) q + b and f = sum_j w3 v[idx3], so y[n,s] = Bq'[n] + sum_j w3[n,s,j]
                         PW[idx3[n,s,j]] with PW = v W1^T over the NK points and Bq' = q (W2 - W1)^T + b over the N queries;
                         HF.interp_edge_max gathers, interpolates in registers, takes the max over the slots and applies the LeakyReLU
@@ -379,7 +365,7 @@ class improvedDeformableLocalGraphAttention(nn.Module):
     (B,N,k,C) tensors) runs, and a HIP tensor that was declined is recorded by HF.note_declined.  Under POOL_TRACE the torch formulation
     records and replays idx3 and the arg of the max.  The neighbour set is the library's ascending (distance, index)."""
 
-    _weights = DeformableLocalCrossAttention._weights
+    n_group, ball, trace_site = 1, True, 'deformable_graph.idx3'        # (what _sample reads beside proj_v_off, linear_offset and k)
 
     def __init__(self, dim, k=10):
         super().__init__()
@@ -396,62 +382,25 @@ class improvedDeformableLocalGraphAttention(nn.Module):
                 and ops.interp_max_usable(q.shape[0], q.shape[1], v.shape[1], self.k, self.dim))
 
     def _fused(self, q, v, v_pos, idx):
-        B, N, C = q.shape
-        lin0, ln, lin, act = self.linear_offset[0], self.linear_offset[1], self.knn_map[0], self.knn_map[1]
-        with torch.no_grad():
-            v_off = HF.linear(v.detach(), self.proj_v_off.weight, self.proj_v_off.bias)
-            A = HF.linear(v_off, lin0.weight[:, :C].contiguous()).unsqueeze(1)                   # (B,1,NK,C)
-            Bq = HF.linear(q.detach(), lin0.weight[:, C:].contiguous(), lin0.bias).unsqueeze(1)  # (B,1,N,C)
-            pos = v_pos.detach().contiguous()
-            shift = HF.deform_offset(A, Bq, idx, pos, ln.weight, ln.bias, ln.eps, self.linear_offset[3].weight, ball=True)
-            dist, idx3 = shifted_three_nn(shift.view(B, N * self.k, 3), pos)
-            w3 = self._weights(dist)
+        C, lin, act = self.dim, self.knn_map[0], self.knn_map[1]
+        idx3, w3 = _sample(self, q, v, v_pos, idx, True)
         W = lin.weight
         PW = HF.linear(v, W[:, :C].contiguous())
         Bm = HF.linear(q, W[:, C:] - W[:, :C], lin.bias)
-        return HF.interp_edge_max(PW, Bm, idx3, w3, act.negative_slope)
+        return HF.interp_edge_max(PW, Bm, idx3[:, 0], w3[:, 0], act.negative_slope)
 
     def _torch(self, q, v, v_pos, idx):
         """the same restatement as torch operators, any device and dtype"""
-        B, N, C = q.shape
-        NK = v.shape[1]
-        lin0, ln, lin, act = self.linear_offset[0], self.linear_offset[1], self.knn_map[0], self.knn_map[1]
-        with torch.no_grad():
-            pos = v_pos.detach()
-            A = torch.matmul(self.proj_v_off(v), lin0.weight[:, :C].t()).unsqueeze(1)
-            Bq = (torch.matmul(q, lin0.weight[:, C:].t()) + lin0.bias).unsqueeze(1)
-            shift = torch_cpu.deform_offset(A, Bq, idx, pos, ln.weight, ln.bias, ln.eps, self.linear_offset[3].weight, ball=True)
-            flat = shift.reshape(B, N * self.k, 3)
-            dist, idx3 = shifted_three_nn(flat, pos)
-            if L.POOL_TRACE is not None:
-                # the recorded choice replaces this run's, and the distances follow it (slots beyond NK < 3 points stay at +inf)
-                idx3 = L.trace_idx('deformable_graph.idx3', idx3)
-                near = torch.gather(pos, 1, idx3.long().reshape(B, -1, 1).expand(-1, -1, 3)).view(B, -1, 3, 3)
-                d = (flat.unsqueeze(2) - near).pow(2).sum(-1).sqrt()
-                dist = torch.where(torch.arange(3, device=d.device) < NK, d, torch.full_like(d, float('inf')))
-            w3 = self._weights(dist)
+        C, lin, act = self.dim, self.knn_map[0], self.knn_map[1]
+        idx3, w3 = _sample(self, q, v, v_pos, idx, False)
         W = lin.weight
         PW = torch.matmul(v, W[:, :C].t())
         Bm = torch.matmul(q, (W[:, C:] - W[:, :C]).t()) + lin.bias
         pool = None if L.POOL_TRACE is None else (lambda y: L.max_over(y, 2, 'deformable_graph.max'))
-        return torch_cpu.interp_edge_max(PW, Bm, idx3, w3, act.negative_slope, pool)
+        return torch_cpu.interp_edge_max(PW, Bm, idx3[:, 0], w3[:, 0], act.negative_slope, pool)
 
     def forward(self, q, q_pos, v=None, v_pos=None, idx=None, denoise_length=None):
-        if denoise_length is not None:
-            if idx is not None:
-                raise ValueError("denoise_length needs the list computed here, but idx is given")
-            if v is not None or v_pos is not None:
-                raise ValueError("denoise_length applies to the self form only, but v / v_pos is given")
-        v = q if v is None else v
-        v_pos = q_pos if v_pos is None else v_pos
-        if q_pos.dim() != 3 or q_pos.size(-1) != 3 or v_pos.dim() != 3 or v_pos.size(-1) != 3:
-            raise ValueError("q_pos and v_pos must be (B, N, 3), got %s and %s" % (tuple(q_pos.shape), tuple(v_pos.shape)))
-        if q.size(-1) != self.dim or v.size(-1) != self.dim:
-            raise ValueError("q and v must have %d channels, got %d and %d" % (self.dim, q.size(-1), v.size(-1)))
-        if idx is None:
-            idx = knn_point(self.k, v_pos, q_pos) if denoise_length is None else denoise_knn(self.k, q_pos, denoise_length)
-        if idx.shape != (q.shape[0], q.shape[1], self.k):
-            raise ValueError("idx must be (B, N, k) = %s, got %s" % ((q.shape[0], q.shape[1], self.k), tuple(idx.shape)))
+        v, v_pos, idx = _neighbour_list(self, q, q_pos, v, v_pos, idx, denoise_length)
         idx = idx.long()
         if self.fusable(q, v):
             return self._fused(q, v, v_pos, idx)

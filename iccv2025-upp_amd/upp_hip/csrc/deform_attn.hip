@@ -8,16 +8,14 @@
 //                      weighted 256-byte row reads each and live in registers only; scores by a wave sum, softmax over the <= 32 slots
 //                      on the lanes, ctx by an fma chain over the slots
 //   da_bwd_kernel      the same walk twice (value rows for dp, key rows for d_q); d_PK / d_PV by f32 atomics (256 contiguous bytes per
-//                      wave instruction) or, <false>, left to DeformJob -- a job of det_scan.h's det_scatter_kernel
+//                      wave instruction: deform_row.h's da_scatter) or, <false>, left to DeformJob -- a job of det_scan.h's
+//                      det_scatter_kernel
 // A wave's item is wave-uniform (readfirstlane), so idx3 / w3 travel through the scalar cache.  No LDS, no scratch: every per-lane array
 // is indexed by a fully unrolled, guarded loop.
-#include "det_scan.h"
 #include "deform_row.h"
 
 namespace {
 
-constexpr int kDaMaxH = 16;           // heads (C = 64 H <= 1024)
-constexpr int kDaMaxK = 32;           // neighbour slots: one lane each in the softmax
 constexpr int kDaWaves = 4;           // waves (items) per workgroup
 constexpr long long kDaGridCap = 65536;
 
@@ -106,9 +104,7 @@ __global__ __launch_bounds__(256) void da_fwd_kernel(const float *__restrict__ q
                                                      int N, int NK, int k, int H, int G, long long items) {
     const int lane = threadIdx.x & 63, C = H * 64;
     for (long long it = (long long)blockIdx.x * kDaWaves + da_wave(); it < items; it += (long long)gridDim.x * kDaWaves) {
-        const int h = (int)(it % H), ch = h * 64 + lane;
-        const long long bn = it / H, b = bn / N;
-        const int n = (int)(bn % N);
+        const auto [bn, b, n, ch] = da_item(it, N, H, lane);
         const float qv = q[bn * C + ch], kb = bk ? bk[ch] : 0.0f, vb = bv ? bv[ch] : 0.0f;
         float sc = 0.0f;
         for (int s = 0; s < k; ++s) {
@@ -141,9 +137,7 @@ __global__ __launch_bounds__(256) void da_bwd_kernel(const float *__restrict__ q
                                                      int H, int G, long long items) {
     const int lane = threadIdx.x & 63, C = H * 64;
     for (long long it = (long long)blockIdx.x * kDaWaves + da_wave(); it < items; it += (long long)gridDim.x * kDaWaves) {
-        const int h = (int)(it % H), ch = h * 64 + lane;
-        const long long bn = it / H, b = bn / N;
-        const int n = (int)(bn % N);
+        const auto [bn, b, n, ch] = da_item(it, N, H, lane);
         const float qv = q[bn * C + ch], dc = d_ctx[bn * C + ch], kb = bk ? bk[ch] : 0.0f, vb = bv ? bv[ch] : 0.0f;
         const float pr = lane < k ? p[it * k + lane] : 0.0f;
         float dp = 0.0f;
@@ -161,21 +155,7 @@ __global__ __launch_bounds__(256) void da_bwd_kernel(const float *__restrict__ q
             dq = __builtin_fmaf(dss, key, dq);
             const float dk = __fmul_rn(__fmul_rn(scale, dss), qv);
             dkb = __fadd_rn(dkb, dk);
-            if (kAtomic) {
-                const float dv = __fmul_rn(da_lane(pr, s), dc);
-                for (int g = 0; g < G; ++g) {
-                    const long long bg = b * G + g, e = ((bg * N + n) * k + s) * 3;
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        const int i = idx3[e + j];
-                        if ((unsigned)i < (unsigned)NK) {
-                            const float w = w3[e + j];
-                            atomicAdd(d_PK + (bg * NK + i) * C + ch, __fmul_rn(w, dk));
-                            atomicAdd(d_PV + (bg * NK + i) * C + ch, __fmul_rn(w, dv));
-                        }
-                    }
-                }
-            }
+            if (kAtomic) da_scatter(d_PK, d_PV, dk, __fmul_rn(da_lane(pr, s), dc), idx3, w3, b, n, s, G, N, NK, k, C, ch);
         }
         d_q[bn * C + ch] = scale * dq;
         if (d_krow) d_krow[bn * C + ch] = dkb;
@@ -220,25 +200,16 @@ struct DeformJob {
     }
 };
 
-static bool da_fits(long long v) { return v < 0x80000000LL; }
-
-static int da_sizes(int B, int N, int NK, int k, int H, int G) {
-    if (B < 1 || N < 1 || NK < 1 || k < 1 || H < 1 || G < 1) return UPP_E_BADARG;
-    if (H > kDaMaxH || k > kDaMaxK || H % G || B > 65535) return UPP_E_RANGE;
-    const long long C = 64LL * H;
-    if (!da_fits((long long)B * N * k * H) || !da_fits((long long)B * G * NK * C) || !da_fits((long long)B * G * N * C) ||
-        !da_fits((long long)B * G * N * k * 3))
-        return UPP_E_RANGE;
-    return 0;
+// (the arrays: p / ds, PK / PV, q-sized rows per group, idx3 / w3)
+static int da_check(int B, int N, int NK, int k, int H, int G) {
+    return da_sizes(B, N, NK, k, H, G, {{B, N, k, H}, {B, G, NK, 64, H}, {B, G, N, 64, H}, {B, G, N, k, 3}});
 }
-
-static bool da_positive(float v) { return v > 0.0f && __builtin_isfinite(v); }
 
 static int da_bwd(bool det, const float *q, const float *PK, const float *PV, const float *bk, const float *bv, const int32_t *idx3,
                   const float *w3, const float *p, const float *d_ctx, float *d_q, float *d_PK, float *d_PV, float *d_krow, float *ds,
                   float scale, int B, int N, int NK, int k, int H, int G, void *stream) {
     if (!q || !PK || !PV || !idx3 || !w3 || !p || !d_ctx || !d_q || !d_PK || !d_PV || !ds || !da_positive(scale)) return UPP_E_BADARG;
-    const int rc = da_sizes(B, N, NK, k, H, G);
+    const int rc = da_check(B, N, NK, k, H, G);
     if (rc) return rc;
     const long long items = (long long)B * N * H;
     const dim3 grid(grid_for(items, kDaWaves, kDaGridCap));
@@ -260,7 +231,7 @@ static int da_offset(bool ball, const float *A, const float *Bq, const int64_t *
                      const float *W3, float *shift, float eps, int B, int G, int N, int NK, int k, int C, void *stream) {
     if (!A || !Bq || !idx || !pos || !gamma || !beta || !W3 || !shift || !da_positive(eps) || C < 1) return UPP_E_BADARG;
     if (C % 64) return UPP_E_RANGE;
-    const int rc = da_sizes(B, N, NK, k, C / 64, G);
+    const int rc = da_check(B, N, NK, k, C / 64, G);
     if (rc) return rc;
     const long long rows = (long long)B * G * N * k;
     const dim3 grid(grid_for(rows, kDaWaves, kDaGridCap));
@@ -292,7 +263,7 @@ extern "C" int upp_deform_attn_fwd(const float *q, const float *PK, const float 
                                    const float *w3, float *ctx, float *p, float scale, int B, int N, int NK, int k, int H, int G,
                                    void *stream) {
     if (!q || !PK || !PV || !idx3 || !w3 || !ctx || !p || !da_positive(scale)) return UPP_E_BADARG;
-    const int rc = da_sizes(B, N, NK, k, H, G);
+    const int rc = da_check(B, N, NK, k, H, G);
     if (rc) return rc;
     const long long items = (long long)B * N * H;
     hipLaunchKernelGGL(da_fwd_kernel, dim3(grid_for(items, kDaWaves, kDaGridCap)), dim3(256), 0, (hipStream_t)stream, q, PK, PV, bk, bv, idx3,

@@ -10,11 +10,11 @@
 //                   det_scan.h's det_scatter_kernel
 // A wave's item is wave-uniform (readfirstlane), so idx3 / w3 travel through the scalar cache in the forward.  No LDS, no scratch, no
 // per-lane array.  The NaN rule, lrelu and lrelu' are those of the norm-free ec_apply_kernel / ec_bwd_apply_kernel (edge_conv.hip).
-#include "det_scan.h"
+#include "deform_row.h"
 
 namespace {
 
-constexpr int kImMaxK = 32, kImMaxO = 1024;
+constexpr int kImMaxK = kDaMaxK, kImMaxO = 1024;      // (the slots are the deformable family's: deform_row.h)
 constexpr int kImWaves = 4;           // waves (items) per workgroup
 constexpr long long kImGridCap = 65536;
 
@@ -114,12 +114,10 @@ struct InterpMaxJob {
     }
 };
 
-static bool im_fits(long long v) { return v < 0x80000000LL; }
-
 static int im_args(bool ptrs, float slope, int B, int N, int NK, int k, int O) {
     if (!ptrs || B < 1 || N < 1 || NK < 1 || k < 1 || O < 1 || !(slope >= 0.0f && slope <= 1.0f)) return UPP_E_BADARG;
     if (k > kImMaxK || O > kImMaxO || B > 65535) return UPP_E_RANGE;
-    if (!im_fits((long long)B * NK * O) || !im_fits((long long)B * N * O) || !im_fits((long long)B * N * k * 3)) return UPP_E_RANGE;
+    if (!da_fits((long long)B * NK * O) || !da_fits((long long)B * N * O) || !da_fits((long long)B * N * k * 3)) return UPP_E_RANGE;
     return 0;
 }
 

@@ -17,13 +17,10 @@
 // kernel; neither uses private (scratch) memory.  Dynamic LDS: forward (2 k 68 + k (k + 1)) floats = 21,632 bytes at k = 32, 4,640 at
 // k = 8; backward (3 k 68 + 2 k (k + 1) + 128) floats = 35,072 bytes at k = 32, 7,616 at k = 8.  Per-lane arrays (ctx_t, d_Q_t) are
 // indexed by fully unrolled, guarded loops only.
-#include "det_scan.h"
 #include "deform_row.h"
 
 namespace {
 
-constexpr int kRaMaxH = 16;           // heads (C = 64 H <= 1024)
-constexpr int kRaMaxK = 32;           // neighbour slots
 constexpr int kRaRow = 68;            // LDS row stride of a 64-channel row, floats
 constexpr long long kRaGridCap = 262144;
 
@@ -93,27 +90,25 @@ __global__ __launch_bounds__(64) void ra_fwd_kernel(const float *__restrict__ q,
     float *Q = ra_lds, *K = Q + k * kRaRow, *P = K + k * kRaRow;
     const int lane = threadIdx.x, C = H * 64, ps = k + 1;
     for (long long it = blockIdx.x; it < items; it += gridDim.x) {
-        const int h = (int)(it % H), ch = h * 64 + lane;
-        const long long bn = it / H, b = bn / N;
-        const int n = (int)(bn % N);
+        const auto [bn, b, n, ch] = da_item(it, N, H, lane);
         const float kb = bk ? bk[ch] : 0.0f, vb = bv ? bv[ch] : 0.0f;
         __syncthreads();                                                         // the previous item's LDS reads are done
         ra_stage(Q, K, nullptr, q, idx, PK, PV, kb, vb, idx3, w3, b, n, G, N, NK, k, C, ch, lane);
         __syncthreads();
         ra_probs(Q, K, P, scale, k, lane);
-        float ctx[kRaMaxK];
+        float ctx[kDaMaxK];
 #pragma unroll
-        for (int t = 0; t < kRaMaxK; ++t) ctx[t] = 0.0f;
+        for (int t = 0; t < kDaMaxK; ++t) ctx[t] = 0.0f;
         for (int s = 0; s < k; ++s) {
             const float val = da_row(PV, vb, idx3, w3, b, n, s, G, N, NK, k, C, ch);
 #pragma unroll
-            for (int t = 0; t < kRaMaxK; ++t)
+            for (int t = 0; t < kDaMaxK; ++t)
                 if (t < k) ctx[t] = __builtin_fmaf(P[t * ps + s], val, ctx[t]);
         }
         float mx = -__builtin_inff();
         int a = 0;
 #pragma unroll
-        for (int t = 0; t < kRaMaxK; ++t)
+        for (int t = 0; t < kDaMaxK; ++t)
             if (t < k && ctx[t] > mx) { mx = ctx[t]; a = t; }                   // the first maximum wins: lowest t; a NaN never wins
         out[bn * C + ch] = mx;
         arg[bn * C + ch] = (uint8_t)a;
@@ -122,7 +117,7 @@ __global__ __launch_bounds__(64) void ra_fwd_kernel(const float *__restrict__ q,
 
 // The backward of one item.  kAtomic: d_q, d_PK, d_PV (zeroed by the entry point) take f32 atomics; otherwise the three planes of `rows`
 // (3,B,N,k,C) take d_Q_t, d_key_s, d_val_s.  d_krow / d_vrow (B,N,C) or NULL = sum_s d_key_s / d_val_s in ascending s.
-// 116 VGPRs (<true>) / 98 (<false>), 106 SGPRs, 0 bytes of scratch.
+// 98 VGPRs (both forms), 106 SGPRs, 0 bytes of scratch.
 template <bool kAtomic>
 __global__ __launch_bounds__(64) void ra_bwd_kernel(const float *__restrict__ q, const long long *__restrict__ idx, const float *__restrict__ PK,
                                                     const float *__restrict__ PV, const float *__restrict__ bk, const float *__restrict__ bv,
@@ -138,9 +133,7 @@ __global__ __launch_bounds__(64) void ra_bwd_kernel(const float *__restrict__ q,
     float *P = gL + 128, *D = P + k * ps;
     const long long plane = (long long)B * N * k * C;
     for (long long it = blockIdx.x; it < items; it += gridDim.x) {
-        const int h = (int)(it % H), ch = h * 64 + lane;
-        const long long bn = it / H, b = bn / N;
-        const int n = (int)(bn % N);
+        const auto [bn, b, n, ch] = da_item(it, N, H, lane);
         const float kb = bk ? bk[ch] : 0.0f, vb = bv ? bv[ch] : 0.0f;
         const float gv = d_out[bn * C + ch];
         const int a = min((int)arg[bn * C + ch], k - 1);
@@ -174,13 +167,13 @@ __global__ __launch_bounds__(64) void ra_bwd_kernel(const float *__restrict__ q,
             for (int s = 0; s < k; ++s) dr[s] = pr[s] * (dr[s] - r);
         }
         __syncthreads();
-        float dq[kRaMaxK], dkb = 0.0f, dvb = 0.0f;
+        float dq[kDaMaxK], dkb = 0.0f, dvb = 0.0f;
 #pragma unroll
-        for (int t = 0; t < kRaMaxK; ++t) dq[t] = 0.0f;
+        for (int t = 0; t < kDaMaxK; ++t) dq[t] = 0.0f;
         for (int s = 0; s < k; ++s) {
             const float key = K[s * kRaRow + lane];
 #pragma unroll
-            for (int t = 0; t < kRaMaxK; ++t)
+            for (int t = 0; t < kDaMaxK; ++t)
                 if (t < k) dq[t] = __builtin_fmaf(D[t * ps + s], key, dq[t]);
             float acc = 0.0f;
             for (int t = 0; t < k; ++t) acc = __builtin_fmaf(D[t * ps + s], Q[t * kRaRow + lane], acc);
@@ -188,25 +181,14 @@ __global__ __launch_bounds__(64) void ra_bwd_kernel(const float *__restrict__ q,
             dkb = __fadd_rn(dkb, dk);
             dvb = __fadd_rn(dvb, dv);
             if (kAtomic) {
-                for (int g = 0; g < G; ++g) {
-                    const long long bg = b * G + g, e = ((bg * N + n) * k + s) * 3;
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        const int i = idx3[e + j];
-                        if ((unsigned)i < (unsigned)NK) {
-                            const float w = w3[e + j];
-                            atomicAdd(d_PK + (bg * NK + i) * C + ch, __fmul_rn(w, dk));
-                            atomicAdd(d_PV + (bg * NK + i) * C + ch, __fmul_rn(w, dv));
-                        }
-                    }
-                }
+                da_scatter(d_PK, d_PV, dk, dv, idx3, w3, b, n, s, G, N, NK, k, C, ch);
             } else {
                 rows[plane + (bn * k + s) * C + ch] = dk;
                 rows[2 * plane + (bn * k + s) * C + ch] = dv;
             }
         }
 #pragma unroll
-        for (int t = 0; t < kRaMaxK; ++t)
+        for (int t = 0; t < kDaMaxK; ++t)
             if (t < k) {
                 const float v = __fmul_rn(scale, dq[t]);
                 if (kAtomic) {
@@ -253,27 +235,18 @@ struct RegionJob {
     }
 };
 
-static bool ra_fits(long long v) { return v < 0x80000000LL; }
-
-static int ra_sizes(int B, int N, int NK, int k, int H, int G) {
-    if (B < 1 || N < 1 || NK < 1 || k < 1 || H < 1 || G < 1) return UPP_E_BADARG;
-    if (H > kRaMaxH || k > kRaMaxK || H % G || B > 65535) return UPP_E_RANGE;
-    const long long C = 64LL * H;
-    if (!ra_fits((long long)B * G * NK * C) || !ra_fits(3LL * B * N * k * C) ||
-        !ra_fits((long long)B * G * N * k * 3))
-        return UPP_E_RANGE;
-    return 0;
+// (the arrays: PK / PV, the rows workspace, idx3 / w3)
+static int ra_check(int B, int N, int NK, int k, int H, int G) {
+    return da_sizes(B, N, NK, k, H, G, {{B, G, NK, 64, H}, {3, B, N, k, 64, H}, {B, G, N, k, 3}});
 }
-
-static bool ra_positive(float v) { return v > 0.0f && __builtin_isfinite(v); }
 
 static int ra_bwd(bool det, const float *q, const int64_t *idx, const float *PK, const float *PV, const float *bk, const float *bv,
                   const int32_t *idx3, const float *w3, const uint8_t *arg, const float *d_out, float *d_q, float *d_PK,
                   float *d_PV, float *d_krow, float *d_vrow, float *rows, float scale, int B, int N, int NK, int k, int H, int G,
                   void *stream) {
-    if (!q || !idx || !PK || !PV || !idx3 || !w3 || !arg || !d_out || !d_q || !d_PK || !d_PV || (det && !rows) || !ra_positive(scale))
+    if (!q || !idx || !PK || !PV || !idx3 || !w3 || !arg || !d_out || !d_q || !d_PK || !d_PV || (det && !rows) || !da_positive(scale))
         return UPP_E_BADARG;
-    const int rc = ra_sizes(B, N, NK, k, H, G);
+    const int rc = ra_check(B, N, NK, k, H, G);
     if (rc) return rc;
     const long long items = (long long)B * N * H;
     const dim3 grid(grid_for(items, 1, kRaGridCap));
@@ -302,8 +275,8 @@ static int ra_bwd(bool det, const float *q, const int64_t *idx, const float *PK,
 extern "C" int upp_region_attn_fwd(const float *q, const int64_t *idx, const float *PK, const float *PV, const float *bk, const float *bv,
                                    const int32_t *idx3, const float *w3, float *out, uint8_t *arg, float scale, int B, int N, int NK,
                                    int k, int H, int G, void *stream) {
-    if (!q || !idx || !PK || !PV || !idx3 || !w3 || !out || !arg || !ra_positive(scale)) return UPP_E_BADARG;
-    const int rc = ra_sizes(B, N, NK, k, H, G);
+    if (!q || !idx || !PK || !PV || !idx3 || !w3 || !out || !arg || !da_positive(scale)) return UPP_E_BADARG;
+    const int rc = ra_check(B, N, NK, k, H, G);
     if (rc) return rc;
     const long long items = (long long)B * N * H;
     hipLaunchKernelGGL(ra_fwd_kernel, dim3(grid_for(items, 1, kRaGridCap)), dim3(64), sizeof(float) * ra_fwd_lds(k), (hipStream_t)stream, q,

@@ -409,8 +409,7 @@ class _EdgeConvMax(Function):
     def backward(ctx, g_out):
         A, Bq, idx, arg, gamma, beta, mean, rstd = ctx.saved_tensors
         groups, slope, det = ctx.cfg
-        g_A, g_Bq, g_gamma, g_beta = ops.edge_conv_bwd(g_out.contiguous(), A, Bq, idx, arg, gamma, beta, mean, rstd, groups, slope,
-                                                       deterministic=DETERMINISTIC if det is None else det)
+        g_A, g_Bq, g_gamma, g_beta = ops.edge_conv_bwd(g_out.contiguous(), A, Bq, idx, arg, gamma, beta, mean, rstd, groups, slope, deterministic=_det(det))
         need = ctx.needs_input_grad
         return (g_A if need[0] else None, g_Bq if need[1] else None, None, g_gamma if groups and need[3] else None,
                 g_beta if groups and need[4] else None, None, None, None, None)
@@ -542,8 +541,7 @@ def query_select(score, cand, Q, extra=None):
 class _DeformAttention(Function):
     """softmax over the k interpolated neighbour rows of every query as one node (include/upp_hip.h "deformable local cross-attention"):
     saves its inputs, ctx's companion p (B,N,H,k) and nothing of B N k C elements -- the key / value rows are recomputed.  The d_PK / d_PV
-    scatter-add follows the deterministic mode: `det` None reads DETERMINISTIC when the backward runs, True / False fixes it for this call.
-    idx3 and w3 get no gradient."""
+    scatter-add follows the deterministic mode (`det`: _det).  idx3 and w3 get no gradient."""
 
     @staticmethod
     def forward(ctx, q, PK, PV, bk, bv, idx3, w3, num_heads, scale, det):
@@ -560,7 +558,7 @@ class _DeformAttention(Function):
         g = g.contiguous()
         want_bk = bk is not None and need[3]
         d_q, d_PK, d_PV, _ds, d_krow = ops.deform_attn_bwd(q, PK, PV, bk, bv, idx3, w3, p, g, num_heads, scale,
-                                                           deterministic=DETERMINISTIC if det is None else det, want_krow=want_bk)
+                                                           deterministic=_det(det), want_krow=want_bk)
         C = g.shape[-1]
         return (d_q if need[0] else None, d_PK if need[1] else None, d_PV if need[2] else None,
                 ops.sum_rows(d_krow.view(-1, C)) if want_bk else None,
@@ -571,11 +569,13 @@ def _deform_f32(*ts):
     return all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 for t in ts)
 
 
+def _deform_operands(idx3, *f32):                      # HIP f32 tensors plus an int32 HIP idx3: what the deformable kernels take
+    return _deform_f32(*f32) and isinstance(idx3, torch.Tensor) and idx3.is_cuda and idx3.dtype == torch.int32
+
+
 def deform_attention_usable(q, PK, PV, idx3, w3, num_heads):
     """Do the fused kernels serve these operands (HIP f32 / int32 tensors, head_dim 64, the served sizes of include/upp_hip.h)?"""
-    if not (_deform_f32(q, PK, PV, w3) and isinstance(idx3, torch.Tensor) and idx3.is_cuda and idx3.dtype == torch.int32):
-        return False
-    if q.dim() != 3 or PK.dim() != 4 or PV.shape != PK.shape or idx3.dim() != 4 or idx3.shape != w3.shape:
+    if not _deform_operands(idx3, q, PK, PV, w3) or q.dim() != 3 or PK.dim() != 4 or PV.shape != PK.shape or idx3.dim() != 4 or idx3.shape != w3.shape:
         return False
     B, N, C = q.shape
     G, NK = PK.shape[1], PK.shape[2]
@@ -626,8 +626,8 @@ def deform_attention(q, PK, PV, bk, bv, idx3, w3, num_heads, scale, deterministi
 # ------------------------------------------------------------------ deformable graph attention (README section of that name)
 class _InterpEdgeMax(Function):
     """lrelu(max_s (Bq + sum_j w3 PW[idx3])) as one node (include/upp_hip.h "deformable graph attention"): saves out, the arg bytes, idx3
-    and w3 -- never a (B,N,k,O) tensor, and no row is read again in the backward.  The d_PW scatter-add follows the deterministic mode:
-    `det` None reads DETERMINISTIC when the backward runs, True / False fixes it for this call.  idx3 and w3 get no gradient."""
+    and w3 -- never a (B,N,k,O) tensor, and no row is read again in the backward.  The d_PW scatter-add follows the deterministic mode
+    (`det`: _det).  idx3 and w3 get no gradient."""
 
     @staticmethod
     def forward(ctx, PW, Bq, idx3, w3, slope, det):
@@ -640,17 +640,14 @@ class _InterpEdgeMax(Function):
     def backward(ctx, g):
         out, arg, idx3, w3 = ctx.saved_tensors
         NK, slope, det = ctx.cfg
-        d_Bq, d_PW = ops.interp_max_bwd(g.contiguous(), out, arg, idx3, w3, NK, slope,
-                                        deterministic=DETERMINISTIC if det is None else det)
+        d_Bq, d_PW = ops.interp_max_bwd(g.contiguous(), out, arg, idx3, w3, NK, slope, deterministic=_det(det))
         need = ctx.needs_input_grad
         return d_PW if need[0] else None, d_Bq if need[1] else None, None, None, None, None
 
 
 def interp_edge_max_usable(PW, Bq, idx3, w3):
     """Do the fused kernels serve these operands (HIP f32 / int32 tensors of the served sizes of include/upp_hip.h)?"""
-    if not (_deform_f32(PW, Bq, w3) and isinstance(idx3, torch.Tensor) and idx3.is_cuda and idx3.dtype == torch.int32):
-        return False
-    if PW.dim() != 3 or Bq.dim() != 3 or idx3.dim() != 3 or idx3.shape != w3.shape or idx3.shape[2] != 3:
+    if not _deform_operands(idx3, PW, Bq, w3) or PW.dim() != 3 or Bq.dim() != 3 or idx3.dim() != 3 or idx3.shape != w3.shape or idx3.shape[2] != 3:
         return False
     B, N, O = Bq.shape
     if N < 1 or idx3.shape[0] != B or idx3.shape[1] % N or PW.shape[0] != B or PW.shape[2] != O:
@@ -681,9 +678,8 @@ def interp_edge_max(PW, Bq, idx3, w3, slope=0.2, deterministic=None):
 class _RegionAttention(Function):
     """max over the rows of a k x k attention per token and head as one node (include/upp_hip.h "region-wise deformable attention"): saves
     its inputs and the arg bytes (B,N,C) -- nothing of B N k C or B N H k k elements; the query, key and value rows and the
-    probabilities are recomputed, the probabilities by the forward's own statement.  The
-    three scatter-adds follow the deterministic mode: `det` None reads DETERMINISTIC when the backward runs, True / False fixes it for
-    this call; the deterministic form allocates its (3,B,N,k,C) workspace for the length of the call.  idx, idx3 and w3 get no gradient."""
+    probabilities are recomputed, the probabilities by the forward's own statement.  The three scatter-adds follow the deterministic
+    mode (`det`: _det); the deterministic form allocates its (3,B,N,k,C) workspace for the call.  idx, idx3 and w3 get no gradient."""
 
     @staticmethod
     def forward(ctx, q, idx, PK, PV, bk, bv, idx3, w3, num_heads, scale, det):
@@ -699,8 +695,7 @@ class _RegionAttention(Function):
         need = ctx.needs_input_grad
         want_bk, want_bv = bk is not None and need[4], bv is not None and need[5]
         d_q, d_PK, d_PV, d_krow, d_vrow, _rows = ops.region_attn_bwd(q, idx, PK, PV, bk, bv, idx3, w3, arg, g.contiguous(), num_heads, scale,
-                                                                     deterministic=DETERMINISTIC if det is None else det,
-                                                                     want_krow=want_bk, want_vrow=want_bv)
+                                                                     deterministic=_det(det), want_krow=want_bk, want_vrow=want_bv)
         C = g.shape[-1]
         return (d_q if need[0] else None, None, d_PK if need[2] else None, d_PV if need[3] else None,
                 ops.sum_rows(d_krow.view(-1, C)) if want_bk else None, ops.sum_rows(d_vrow.view(-1, C)) if want_bv else None,
@@ -709,8 +704,7 @@ class _RegionAttention(Function):
 
 def region_attention_usable(q, idx, PK, PV, idx3, w3, num_heads):
     """Do the fused kernels serve these operands (HIP f32 / int tensors, head_dim 64, the served sizes of include/upp_hip.h)?"""
-    if not (_deform_f32(q, PK, PV, w3) and isinstance(idx3, torch.Tensor) and idx3.is_cuda and idx3.dtype == torch.int32
-            and isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype in (torch.int64, torch.int32)):
+    if not (_deform_operands(idx3, q, PK, PV, w3) and isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype in (torch.int64, torch.int32)):
         return False
     if q.dim() != 3 or idx.dim() != 3 or PK.dim() != 4 or PV.shape != PK.shape or idx3.dim() != 4 or idx3.shape != w3.shape:
         return False
@@ -2369,6 +2363,10 @@ ADAPTER_FACTORS = True        # ... which inside a deferred scope writes per-row
 # scatter-adds").  Read at CALL time, also by the backward thread; a captured step keeps the choice it was captured under, whatever the
 # attribute says at replay.  UPP_DETERMINISTIC=1 sets it once, at import.
 DETERMINISTIC = os.environ.get("UPP_DETERMINISTIC", "").strip() not in ("", "0")
+
+
+def _det(det):                 # a node's per-call choice (True / False), or -- None -- DETERMINISTIC as it reads when the backward runs
+    return DETERMINISTIC if det is None else det
 
 
 class deterministic:

@@ -746,21 +746,28 @@ DEFORM_MAX_H = 16
 DEFORM_MAX_K = 32
 
 
+def _deform_range(B, N, NK, k, H, G, arrays):
+    """da_sizes of csrc/deform_row.h: positive sizes, the family's limits, and every array (its element count) below 2^31"""
+    return min(B, N, NK, k, H, G) >= 1 and H <= DEFORM_MAX_H and k <= DEFORM_MAX_K and H % G == 0 and B <= 65535 and max(arrays) < 2 ** 31
+
+
 def deform_attn_usable(B, N, NK, k, H, G):
     """The served range of upp_deform_offset_fwd / upp_deform_attn_* (head_dim 64 is the caller's C == 64 H)."""
-    if min(B, N, NK, k, H, G) < 1 or H > DEFORM_MAX_H or k > DEFORM_MAX_K or H % G or B > 65535:
-        return False
     C = 64 * H
-    return max(B * N * k * H, B * G * NK * C, B * G * N * C, B * G * N * k * 3) < 2 ** 31
+    return _deform_range(B, N, NK, k, H, G, (B * N * k * H, B * G * NK * C, B * G * N * C, B * G * N * k * 3))
 
 
-def _deform_sizes(who, B, N, NK, k, H, G):
-    if min(B, N, NK, k, H, G) < 1:
-        raise RuntimeError("%s: every size must be positive, got B = %d, N = %d, NK = %d, k = %d, H = %d, G = %d" % (who, B, N, NK, k, H, G))
-    if not deform_attn_usable(B, N, NK, k, H, G):
-        raise RuntimeError("%s: B = %d, N = %d, NK = %d, k = %d, H = %d, G = %d is outside the served range head_dim 64, 1 <= H <= %d, "
-                           "G | H, 1 <= k <= %d, B <= 65535, every array below 2^31 elements (UPP_E_RANGE)"
-                           % (who, B, N, NK, k, H, G, DEFORM_MAX_H, DEFORM_MAX_K))
+def _served(who, usable, limits, **sizes):
+    """Raise unless the sizes -- named, in `usable`'s argument order -- are positive and `usable` (an *_usable of this file) serves
+    them; `limits` is the range, in words."""
+    got = ", ".join("%s = %d" % s for s in sizes.items())
+    if min(sizes.values()) < 1:
+        raise RuntimeError("%s: every size must be positive, got %s" % (who, got))
+    if not usable(*sizes.values()):
+        raise RuntimeError("%s: %s is outside the served range %s, B <= 65535, every array below 2^31 elements (UPP_E_RANGE)" % (who, got, limits))
+
+
+_DEFORM_LIMITS = "head_dim 64, 1 <= H <= %d, G | H, 1 <= k <= %d" % (DEFORM_MAX_H, DEFORM_MAX_K)
 
 
 def _aligned16(who, **tensors):
@@ -797,7 +804,7 @@ def deform_offset_fwd(A, Bq, idx, pos, gamma, beta, W3, eps, ball=False):
     eps = _positive("deform_offset", "eps", eps)
     if C % 64:
         raise RuntimeError("deform_offset: C = %d is outside the served range (a multiple of 64: UPP_E_RANGE)" % C)
-    _deform_sizes("deform_offset", B, N, NK, k, C // 64, G)
+    _served("deform_offset", deform_attn_usable, _DEFORM_LIMITS, B=B, N=N, NK=NK, k=k, H=C // 64, G=G)
     _aligned16("deform_offset", A=A, Bq=Bq, idx=idx, pos=pos, gamma=gamma, beta=beta, W3=W3)
     shift = torch.empty((B, G, N * k, 3), dtype=torch.float32, device=A.device)
     _call(A.device, "upp_deform_offset_ball_fwd" if ball else "upp_deform_offset_fwd", _abi.ptr(A), _abi.ptr(Bq), _abi.ptr(idx), _abi.ptr(pos),
@@ -805,9 +812,15 @@ def deform_offset_fwd(A, Bq, idx, pos, gamma, beta, W3, eps, ball=False):
     return shift
 
 
-def _deform_attn_args(who, q, PK, PV, bk, bv, idx3, w3, H, scale):
+def _deform_attn_args(who, q, PK, PV, bk, bv, idx3, w3, H, scale, idx=None):
+    """The operands of upp_deform_attn_* (idx None: k is idx3's) and upp_region_attn_* (idx (B,N,k) int64 gives k, and idx3 must be
+    exactly (B, G, N k, 3)) -> B, N, NK, k, H, G, C, scale"""
     _need(q, "q", torch.float32, 3)
     B, N, C = q.shape
+    if idx is not None:
+        _need(idx, "idx", torch.int64, 3)
+        if tuple(idx.shape) != (B, N, idx.shape[2]):
+            raise RuntimeError("%s: idx must be (B, N, k) = (%d, %d, k), got %s" % (who, B, N, tuple(idx.shape)))
     _need(PK, "PK", torch.float32, 4)
     G, NK = PK.shape[1], PK.shape[2]
     _need_f32(PK, "PK", (B, G, NK, C))
@@ -816,18 +829,28 @@ def _deform_attn_args(who, q, PK, PV, bk, bv, idx3, w3, H, scale):
     _need_f32(bv, "bv", (C,), optional=True)
     _need(idx3, "idx3", torch.int32, 4, 3)
     _need(w3, "w3", torch.float32, 4, 3)
-    if idx3.shape != w3.shape or idx3.shape[0] != B or idx3.shape[1] != G or idx3.shape[2] % N:
-        raise RuntimeError("%s: idx3 and w3 must both be (B, G, N k, 3) = (%d, %d, %d k, 3), got %s and %s"
-                           % (who, B, G, N, tuple(idx3.shape), tuple(w3.shape)))
-    k = idx3.shape[2] // N
-    _same_device(q, PK, PV, idx3, w3, *[t for t in (bk, bv) if t is not None])
+    rows = "%d k" % N if idx is None else N * idx.shape[2]
+    if idx3.shape != w3.shape or tuple(idx3.shape[:2]) != (B, G) or (idx3.shape[2] % N if idx is None else idx3.shape[2] != rows):
+        raise RuntimeError("%s: idx3 and w3 must both be (B, G, N k, 3) = (%d, %d, %s, 3), got %s and %s"
+                           % (who, B, G, rows, tuple(idx3.shape), tuple(w3.shape)))
+    k = idx3.shape[2] // N if idx is None else idx.shape[2]
+    _same_device(q, PK, PV, idx3, w3, *[t for t in (idx, bk, bv) if t is not None])
     H = int(H)
     scale = _positive(who, "scale", scale)
     if H < 1 or C != 64 * H:
         raise RuntimeError("%s: C = %d with %d heads is outside the served range (head_dim 64: UPP_E_RANGE)" % (who, C, H))
-    _deform_sizes(who, B, N, NK, k, H, G)
-    _aligned16(who, q=q, PK=PK, PV=PV, bk=bk, bv=bv, idx3=idx3, w3=w3)
+    _served(who, deform_attn_usable if idx is None else region_attn_usable, _DEFORM_LIMITS, B=B, N=N, NK=NK, k=k, H=H, G=G)
+    _aligned16(who, q=q, idx=idx, PK=PK, PV=PV, bk=bk, bv=bv, idx3=idx3, w3=w3)
     return B, N, NK, k, H, G, C, scale
+
+
+def _need_arg(who, arg, shape, like):
+    """the uint8 arg of the max (B, N, channels) that a backward reads, on `like`'s device"""
+    _need(arg, "arg", torch.uint8, 3)
+    if tuple(arg.shape) != tuple(shape):
+        raise RuntimeError("%s: arg must be %s, got %s" % (who, tuple(shape), tuple(arg.shape)))
+    _same_device(like, arg)
+    _aligned16(who, arg=arg)
 
 
 def deform_attn_fwd(q, PK, PV, bk, bv, idx3, w3, H, scale):
@@ -889,11 +912,7 @@ def _interp_max_args(who, a, a_name, b, b_name, idx3, w3, slope, NK=None):
     slope = float(slope)
     if not 0.0 <= slope <= 1.0:
         raise RuntimeError("%s: slope must be in [0, 1], got %r (UPP_E_BADARG)" % (who, slope))
-    if min(B, N, NK, k, O) < 1:
-        raise RuntimeError("%s: every size must be positive, got B = %d, N = %d, NK = %d, k = %d, O = %d" % (who, B, N, NK, k, O))
-    if not interp_max_usable(B, N, NK, k, O):
-        raise RuntimeError("%s: B = %d, N = %d, NK = %d, k = %d, O = %d is outside the served range 1 <= k <= %d, 1 <= O <= %d, B <= 65535, "
-                           "every array below 2^31 elements (UPP_E_RANGE)" % (who, B, N, NK, k, O, INTERP_MAX_K, INTERP_MAX_O))
+    _served(who, interp_max_usable, "1 <= k <= %d, 1 <= O <= %d" % (INTERP_MAX_K, INTERP_MAX_O), B=B, N=N, NK=NK, k=k, O=O)
     _aligned16(who, **{a_name: a, b_name: b, "idx3": idx3, "w3": w3})
     return B, N, NK, k, O, slope
 
@@ -913,11 +932,8 @@ def interp_max_bwd(g_out, out, arg, idx3, w3, NK, slope=0.2, deterministic=False
     """g_out, out (B,N,O), arg (B,N,O) uint8 -> d_Bq (B,N,O), d_PW (B,NK,O).  d_PW by f32 atomics into an array the entry point zeroes with
     a kernel (upp_interp_max_bwd) or, deterministic, in ascending 3 n + j (upp_interp_max_bwd_det, include/upp_hip.h)."""
     B, N, NK, k, O, slope = _interp_max_args("interp_edge_max_bwd", g_out, "g_out", out, "out", idx3, w3, slope, NK=NK)
-    _need(arg, "arg", torch.uint8, 3)
-    if tuple(g_out.shape) != (B, N, O) or tuple(arg.shape) != (B, N, O):
-        raise RuntimeError("interp_edge_max_bwd: g_out and arg must be (B, N, O) = %s" % ((B, N, O),))
-    _same_device(g_out, arg)
-    _aligned16("interp_edge_max_bwd", arg=arg)
+    _need_f32(g_out, "g_out", (B, N, O))
+    _need_arg("interp_edge_max_bwd", arg, (B, N, O), g_out)
     d_Bq = torch.empty((B, N, O), dtype=torch.float32, device=g_out.device)
     d_PW = torch.empty((B, NK, O), dtype=torch.float32, device=g_out.device)
     _call(g_out.device, "upp_interp_max_bwd_det" if deterministic else "upp_interp_max_bwd", _abi.ptr(g_out), _abi.ptr(out), _abi.ptr(arg),
@@ -928,49 +944,14 @@ def interp_max_bwd(g_out, out, arg, idx3, w3, NK, slope=0.2, deterministic=False
 # ------------------------------------------------------------------ region-wise deformable attention (include/upp_hip.h)
 def region_attn_usable(B, N, NK, k, H, G):
     """The served range of upp_region_attn_fwd / _bwd / _bwd_det (sizes only; head_dim 64 is the caller's C == 64 H)."""
-    if min(B, N, NK, k, H, G) < 1 or H > DEFORM_MAX_H or k > DEFORM_MAX_K or H % G or B > 65535:
-        return False
     C = 64 * H
-    return max(B * G * NK * C, 3 * B * N * k * C, B * G * N * k * 3) < 2 ** 31
-
-
-def _region_attn_args(who, q, idx, PK, PV, bk, bv, idx3, w3, H, scale):
-    _need(q, "q", torch.float32, 3)
-    B, N, C = q.shape
-    _need(idx, "idx", torch.int64, 3)
-    k = idx.shape[2]
-    if tuple(idx.shape) != (B, N, k):
-        raise RuntimeError("%s: idx must be (B, N, k) = (%d, %d, k), got %s" % (who, B, N, tuple(idx.shape)))
-    _need(PK, "PK", torch.float32, 4)
-    G, NK = PK.shape[1], PK.shape[2]
-    _need_f32(PK, "PK", (B, G, NK, C))
-    _need_f32(PV, "PV", (B, G, NK, C))
-    _need_f32(bk, "bk", (C,), optional=True)
-    _need_f32(bv, "bv", (C,), optional=True)
-    _need(idx3, "idx3", torch.int32, 4, 3)
-    _need(w3, "w3", torch.float32, 4, 3)
-    if idx3.shape != w3.shape or tuple(idx3.shape) != (B, G, N * k, 3):
-        raise RuntimeError("%s: idx3 and w3 must both be (B, G, N k, 3) = (%d, %d, %d, 3), got %s and %s"
-                           % (who, B, G, N * k, tuple(idx3.shape), tuple(w3.shape)))
-    _same_device(q, idx, PK, PV, idx3, w3, *[t for t in (bk, bv) if t is not None])
-    H = int(H)
-    scale = _positive(who, "scale", scale)
-    if H < 1 or C != 64 * H:
-        raise RuntimeError("%s: C = %d with %d heads is outside the served range (head_dim 64: UPP_E_RANGE)" % (who, C, H))
-    if min(B, N, NK, k, H, G) < 1:
-        raise RuntimeError("%s: every size must be positive, got B = %d, N = %d, NK = %d, k = %d, H = %d, G = %d" % (who, B, N, NK, k, H, G))
-    if not region_attn_usable(B, N, NK, k, H, G):
-        raise RuntimeError("%s: B = %d, N = %d, NK = %d, k = %d, H = %d, G = %d is outside the served range head_dim 64, 1 <= H <= %d, "
-                           "G | H, 1 <= k <= %d, B <= 65535, every array below 2^31 elements (UPP_E_RANGE)"
-                           % (who, B, N, NK, k, H, G, DEFORM_MAX_H, DEFORM_MAX_K))
-    _aligned16(who, q=q, idx=idx, PK=PK, PV=PV, bk=bk, bv=bv, idx3=idx3, w3=w3)
-    return B, N, NK, k, H, G, C, scale
+    return _deform_range(B, N, NK, k, H, G, (B * G * NK * C, 3 * B * N * k * C, B * G * N * k * 3))
 
 
 def region_attn_fwd(q, idx, PK, PV, bk, bv, idx3, w3, H, scale):
     """q (B,N,C), idx (B,N,k) int64 rows of q, PK / PV (B,G,NK,C), bk / bv (C) | None, idx3 int32 and w3 (B,G,N k,3) -> out (B,N,C),
     arg (B,N,C) uint8: upp_region_attn_fwd, 1 launch, no (B,N,k,C) tensor and no (B,N,H,k,k) probabilities."""
-    B, N, NK, k, H, G, C, scale = _region_attn_args("region_attention", q, idx, PK, PV, bk, bv, idx3, w3, H, scale)
+    B, N, NK, k, H, G, C, scale = _deform_attn_args("region_attention", q, PK, PV, bk, bv, idx3, w3, H, scale, idx)
     out = torch.empty((B, N, C), dtype=torch.float32, device=q.device)
     arg = torch.empty((B, N, C), dtype=torch.uint8, device=q.device)
     _call(q.device, "upp_region_attn_fwd", _abi.ptr(q), _abi.ptr(idx), _abi.ptr(PK), _abi.ptr(PV), _abi.ptr(bk), _abi.ptr(bv), _abi.ptr(idx3),
@@ -984,13 +965,11 @@ def region_attn_bwd(q, idx, PK, PV, bk, bv, idx3, w3, arg, d_out, H, scale, dete
     The three scatter-adds by f32 atomics into arrays the entry point zeroes with a kernel (upp_region_attn_bwd) or, deterministic,
     through the workspace rows (3,B,N,k,C) -- allocated here when None -- in ascending n k + t and (n k + s) 3 + j
     (upp_region_attn_bwd_det, include/upp_hip.h)."""
-    B, N, NK, k, H, G, C, scale = _region_attn_args("region_attention_bwd", q, idx, PK, PV, bk, bv, idx3, w3, H, scale)
+    B, N, NK, k, H, G, C, scale = _deform_attn_args("region_attention_bwd", q, PK, PV, bk, bv, idx3, w3, H, scale, idx)
     _need_f32(d_out, "d_out", (B, N, C))
-    _need(arg, "arg", torch.uint8, 3)
-    if tuple(arg.shape) != (B, N, C):
-        raise RuntimeError("region_attention_bwd: arg must be (B, N, C) = %s, got %s" % ((B, N, C), tuple(arg.shape)))
-    _same_device(q, arg, d_out)
-    _aligned16("region_attention_bwd", arg=arg, d_out=d_out)
+    _need_arg("region_attention_bwd", arg, (B, N, C), q)
+    _same_device(q, d_out)
+    _aligned16("region_attention_bwd", d_out=d_out)
     dev = q.device
     d_q = torch.empty((B, N, C), dtype=torch.float32, device=dev)
     d_PK = torch.empty((B, G, NK, C), dtype=torch.float32, device=dev)

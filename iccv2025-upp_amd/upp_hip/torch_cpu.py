@@ -291,29 +291,30 @@ def interp_edge_max(PW, Bq, idx3, w3, slope=0.2, pool=None):
     return F.leaky_relu(y.max(dim=2)[0] if pool is None else pool(y), float(slope))
 
 
+def _deform_rows(P, bias, idx3, w3):
+    """P (B,G,NK,C), bias (C) | None, idx3 and w3 (B,G,R,3) -> (B,R,C) = bias + sum_g sum_j w3 P_g[idx3] (g, then j ascending): the key /
+    value rows of deform_attention and region_attention.  An index outside [0, NK) contributes nothing."""
+    B, G, NK, C = P.shape
+    i3 = idx3.long()
+    inside = ((i3 >= 0) & (i3 < NK)).unsqueeze(-1)
+    t = torch.gather(P, 2, i3.clamp(0, NK - 1).reshape(B, G, -1, 1).expand(-1, -1, -1, C)).view(B, G, -1, 3, C) * w3.detach().unsqueeze(-1)
+    t = torch.where(inside, t, torch.zeros((), dtype=P.dtype, device=P.device))
+    r = None
+    for g in range(G):
+        for j in range(3):
+            r = t[:, g, :, j] if r is None else r + t[:, g, :, j]
+    return r if bias is None else r + bias
+
+
 def deform_attention(q, PK, PV, bk, bv, idx3, w3, num_heads, scale, drop=None):
     """The gather-attend core of include/upp_hip.h "deformable local cross-attention" as torch operators (any device, dtype and
     head_dim; differentiable in q, PK, PV, bk, bv): q (B,N,C), PK / PV (B,G,NK,C), bk / bv (C) | None, idx3 and w3 (B,G,N k,3) ->
-    ctx (B,N,C); drop: the module's attention dropout or None.  key_s = bk + sum_g sum_j w3 PK_g[idx3] (g, then j ascending), val_s likewise; softmax over the k slots per head.  It
-    keeps the (B,N,k,C) rows the kernels avoid."""
+    ctx (B,N,C); drop: the module's attention dropout or None.  key_s = bk + sum_g sum_j w3 PK_g[idx3] (g, then j ascending; an idx3
+    outside [0, NK) contributes nothing), val_s likewise; softmax over the k slots per head.  It keeps the (B,N,k,C) rows the kernels avoid."""
     B, N, C = q.shape
-    G, NK = PK.shape[1], PK.shape[2]
     H = int(num_heads)
     k = idx3.shape[2] // N
-    flat = idx3.long().reshape(B, G, N * k * 3, 1).expand(-1, -1, -1, C)
-    w = w3.detach().unsqueeze(-1)
-
-    def rows(P, bias):
-        t = torch.gather(P, 2, flat).view(B, G, N * k, 3, C) * w
-        r = None
-        for g in range(G):
-            for j in range(3):
-                r = t[:, g, :, j] if r is None else r + t[:, g, :, j]
-        if bias is not None:
-            r = r + bias
-        return r.view(B, N, k, H, C // H)
-
-    key, val = rows(PK, bk), rows(PV, bv)
+    key, val = (_deform_rows(P, b, idx3, w3).view(B, N, k, H, C // H) for P, b in ((PK, bk), (PV, bv)))
     score = (q.view(B, N, 1, H, C // H) * key).sum(-1) * scale                        # (B,N,k,H)
     p = score.softmax(dim=2)
     if drop is not None:
@@ -330,26 +331,9 @@ def region_attention(q, idx, PK, PV, bk, bv, idx3, w3, num_heads, scale, drop=No
     that takes the place of ctx.max(2)[0] (the modules' arg-max instrument).  It keeps the (B,N,k,C) tensors and the (B,N,H,k,k) scores
     the kernels avoid."""
     B, N, C = q.shape
-    G, NK = PK.shape[1], PK.shape[2]
     H = int(num_heads)
     k = idx.shape[2]
-    i3 = idx3.long()
-    inside = ((i3 >= 0) & (i3 < NK)).unsqueeze(-1)
-    flat = i3.clamp(0, NK - 1).reshape(B, G, N * k * 3, 1).expand(-1, -1, -1, C)
-    w = w3.detach().unsqueeze(-1)
-
-    def rows(P, bias):
-        t = torch.gather(P, 2, flat).view(B, G, N * k, 3, C) * w
-        t = torch.where(inside, t, torch.zeros((), dtype=P.dtype, device=P.device))
-        r = None
-        for g in range(G):
-            for j in range(3):
-                r = t[:, g, :, j] if r is None else r + t[:, g, :, j]
-        if bias is not None:
-            r = r + bias
-        return r.view(B, N, k, H, C // H)
-
-    key, val = rows(PK, bk), rows(PV, bv)
+    key, val = (_deform_rows(P, b, idx3, w3).view(B, N, k, H, C // H) for P, b in ((PK, bk), (PV, bv)))
     i = idx.long()
     Q = torch.gather(q, 1, i.clamp(0, N - 1).reshape(B, N * k, 1).expand(-1, -1, C)).view(B, N, k, C)
     Q = torch.where(((i >= 0) & (i < N)).unsqueeze(-1), Q, torch.zeros((), dtype=q.dtype, device=q.device)).view(B, N, k, H, C // H)

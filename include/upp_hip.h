@@ -462,7 +462,8 @@ int upp_interp_max_bwd_det(const float *g_out, const float *out, const uint8_t *
  *   idx3 int32 and w3 f32 (B,G,N k,3), scale: what they are for upp_deform_attn_fwd
  *   -> per (b, n, head h with channels [64 h, 64 h + 64)):
  *        Q_t = q[b, idx[b,n,t]] for t < k (a zero row for an index outside [0, N));
- *        key_s[ch], val_s[ch] for s < k: the rows of upp_deform_attn_fwd, by the same statement (csrc/deform_row.h): bias, then
+ *        key_s[ch], val_s[ch] for s < k: the rows of upp_deform_attn_fwd, by the same statement (da_row of csrc/deform_row.h, which
+ *          also holds the d_PK / d_PV atomic scatter and the size checks the two operators share): bias, then
  *          fma(w3, P[idx3], .) for ascending g, then ascending j; an idx3 outside [0, NK) contributes nothing;
  *        S[t,s] = scale * (fma(Q_t[ch], key_s[ch], .) from +0 in ascending ch), the product by scale rounded once;
  *        p[t,s] = expf(S[t,s] - max_s S[t,s]) / (the sum of the k exponentials from +0 in ascending s), one division per element;

@@ -87,6 +87,23 @@ def test_attention_formulation_equals_interpolate_then_project(B, N, NK, k, H, G
     assert got.shape == want.shape and (got - want).abs().max() <= 1e-12 * want.abs().max()
 
 
+def test_formulation_treats_indices_outside_their_range_as_absent():
+    """include/upp_hip.h and da_row: an idx3 outside [0, NK) contributes nothing (the twin of the rw_deform test of this name)."""
+    g = torch.Generator().manual_seed(11)
+    B, N, NK, k, G, H, C = 1, 2, 3, 2, 1, 2, 8
+    q, PK, PV, bk, bv = (torch.randn(*s, generator=g) for s in ((B, N, C), (B, G, NK, C), (B, G, NK, C), (C,), (C,)))
+    idx3 = torch.randint(0, NK, (B, G, N * k, 3), generator=g).int()
+    w3 = torch.rand(B, G, N * k, 3, generator=g) + 0.1
+    idx3[0, 0, 1, 0], idx3[0, 0, 2, 2] = -1, NK
+    got = torch_cpu.deform_attention(q, PK, PV, bk, bv, idx3, w3, H, 0.35)
+    w0, i0 = w3.clone(), idx3.clone()
+    w0[0, 0, 1, 0], w0[0, 0, 2, 2] = 0.0, 0.0
+    i0[0, 0, 1, 0], i0[0, 0, 2, 2] = 0, 0
+    want = torch_cpu.deform_attention(q, PK, PV, bk, bv, i0, w0, H, 0.35)
+    assert torch.isfinite(got).all() and torch.equal(got, want)
+    assert not torch.equal(got, torch_cpu.deform_attention(q, PK, PV, bk, bv, i0, w3, H, 0.35))      # (the two entries do carry weight)
+
+
 # ---- the modules: schema, fixture, wiring, gradients ----------------------------------------------------------------------------------
 def test_state_dict_schema_is_the_references_and_loads_strictly():
     from models import AdaPoinTr, Transformer_utils
