@@ -275,7 +275,7 @@ class Point_MAE_unify(PromptedBackbone):
                         L.bump_counter(layer.num_batches_tracked)
                     x = L._bn_rows(x, layer, self.training)
                 else:
-                    x = HF.linear(x, layer.weight, layer.bias, own_wgrad=True) if isinstance(layer, nn.Linear) and x.is_cuda else layer(x)
+                    x = HF.linear(x, layer.weight, layer.bias) if isinstance(layer, nn.Linear) and x.is_cuda else layer(x)
             return x
         if not (feat.is_cuda and feat.dtype == torch.float32 and feat.dim() == 2):
             return self.cls_head_finetune(feat)
@@ -292,7 +292,7 @@ class Point_MAE_unify(PromptedBackbone):
                 i += 3
             else:
                 # (the head is trainable: data and weight gradients on upp_linear_f32 / upp_linear_wgrad_f32, 32 rows)
-                x = HF.linear(x, layers[i].weight, layers[i].bias, own_wgrad=True) if isinstance(layers[i], nn.Linear) else layers[i](x)
+                x = HF.linear(x, layers[i].weight, layers[i].bias) if isinstance(layers[i], nn.Linear) else layers[i](x)
                 i += 1
         return x
 

@@ -49,7 +49,7 @@ class Point_MAE_unify_seg(PromptedBackbone):
         for conv, bn, act in ((c1, b1, a1), (c2, b2, a2)):
             if self.training and bn.track_running_stats:
                 L.bump_counter(bn.num_batches_tracked)
-            z = _bn_rows(HF.linear(x, conv.weight.squeeze(-1), conv.bias, own_wgrad=True), bn, self.training)
+            z = _bn_rows(HF.linear(x, conv.weight.squeeze(-1), conv.bias), bn, self.training)
             x = L.gate('label_conv', z, act.negative_slope) if (L.POOL_TRACE is not None and isinstance(act, nn.LeakyReLU)) else act(z)
         return x
 
@@ -58,7 +58,7 @@ class Point_MAE_unify_seg(PromptedBackbone):
         c1, bn1, _, drop, c2, bn2, _, c3 = self.seg_head
         B, N, C = point_feat.shape
         w1 = c1.weight.squeeze(-1)
-        per_sample = HF.linear(global_feat, w1[:, C:], c1.bias, own_wgrad=True)                       # (B,512), once per sample
+        per_sample = HF.linear(global_feat, w1[:, C:], c1.bias)                       # (B,512), once per sample
         h = HF.linear_group_bias(point_feat.reshape(B * N, C), w1[:, :C], per_sample, N).view(B, N, -1) if (N & (N - 1)) == 0 and N >= 32 \
             else HF.linear(point_feat.reshape(B * N, C), w1[:, :C]).view(B, N, -1) + per_sample.unsqueeze(1)    # (per-sample term: GEMM epilogue)
         if self.training and bn1.track_running_stats:

@@ -4,6 +4,7 @@ Layout:
   csrc/        hand-written HIP kernels + the C ABI of include/upp_hip.h
   build.py     hipcc driver (in-tree libupp_hip.so)
   _abi.py      ctypes binding (no fallback: missing library -> RuntimeError)
+  _derived.py  the cache of buffers derived from weights (W^T copies, bf16 plane images); pure torch
   ops.py       tensor validation + launches on torch's current stream
   functional.py  autograd Functions with the reference operators' semantics
 The packages next to this one (pointnet2_ops, knn_cuda, extensions, emd, chamfer,

@@ -1,13 +1,12 @@
 """Autograd Functions over upp_hip.ops with the reference operators' contracts."""
 import os
 import sys
-import weakref
 
 import torch
 import torch.nn.functional as F
 from torch.autograd import Function
 
-from . import ops
+from . import _derived, ops
 
 class FurthestPointSampling(Function):
     """pointnet2_utils.furthest_point_sample: (B,N,3) f32, npoint -> (B,npoint) int32, non-differentiable."""
@@ -1053,26 +1052,26 @@ class _DeferredSums:
         self.routed.add(ptr)
         return True, None
 
+    def _queue_wgrad(self, ptr, g2, x2, numel, window=None):
+        """The registered buffer of the parameter at `ptr` (numel elements) -- or its `window` -- receives the partials of g2^T . x2 at scope
+        exit.  -> True when queued (autograd is handed None), False when no such buffer is registered."""
+        dst = self.targets.get(ptr) if (self.targets is not None and g2.is_cuda) else None
+        if dst is None or dst.numel() != numel:
+            return False
+        self.wgrads.append((g2, x2, dst if window is None else window(dst)))
+        self.routed.add(ptr)
+        return True
+
     def wgrad(self, ptr, g2, x2):
         """Queue dW = g2^T . x2 for a parameter whose gradient buffer is registered: every weight gradient of the backward pass
         runs in ONE grouped launch at scope exit (upp_linear_wgrad_grouped_f32; a weight gradient is read by nothing inside the
         pass) and its partials are added to the buffer by the batched sum.  -> True when queued (autograd is handed None)."""
-        dst = self.targets.get(ptr) if (self.targets is not None and g2.is_cuda) else None
-        if dst is None or dst.numel() != g2.shape[1] * x2.shape[1]:
-            return False
-        self.wgrads.append((g2, x2, dst))
-        self.routed.add(ptr)
-        return True
+        return self._queue_wgrad(ptr, g2, x2, g2.shape[1] * x2.shape[1])
 
     def wgrad_rows(self, ptr, g2, x2, n_rows):
         """dW = (g2^T . x2)[:n_rows] for a parameter whose output was computed wider than it is (g2 has n_pad >= n_rows columns whose
         pad columns are zero): the partial tiles are (n_pad, K); only their first n_rows rows are summed into the buffer."""
-        dst = self.targets.get(ptr) if (self.targets is not None and g2.is_cuda) else None
-        if dst is None or dst.numel() != n_rows * x2.shape[1] or n_rows > g2.shape[1]:
-            return False
-        self.wgrads.append((g2, x2, dst))
-        self.routed.add(ptr)
-        return True
+        return n_rows <= g2.shape[1] and self._queue_wgrad(ptr, g2, x2, n_rows * x2.shape[1])
 
     def wgrad_window(self, w, g2, x2):
         """The same for a weight that is a COLUMN RANGE w = P[:, a:b] of a registered 2-D parameter P (the segmentation head's first layer
@@ -1080,19 +1079,14 @@ class _DeferredSums:
         partials are added into that range of P's gradient buffer (upp_batched_sum window destination) -- autograd is handed None, so the
         slice's backward (zero-fill of P's shape, strided copy, add) never runs.  -> True when queued."""
         root = w._base
-        if self.targets is None or root is None or not g2.is_cuda or w.dim() != 2 or w.stride(1) != 1:
+        if root is None or w.dim() != 2 or w.stride(1) != 1 or not root.is_contiguous() or root.numel() % w.shape[0]:
             return False
-        dst = self.targets.get(root.data_ptr())
         N, K = w.shape
-        if dst is None or dst.numel() != root.numel() or root.numel() % N or not root.is_contiguous():
-            return False
         Kt = root.numel() // N                        # P viewed as (N, Kt): trailing singleton dimensions of a Conv1d weight fold away
         off = w.storage_offset() - root.storage_offset()
         if w.stride(0) != Kt or off < 0 or off + K > Kt or (g2.shape[1], x2.shape[1]) != (N, K):
             return False
-        self.wgrads.append((g2, x2, dst.view(N, Kt)[:, off:off + K]))
-        self.routed.add(root.data_ptr())
-        return True
+        return self._queue_wgrad(root.data_ptr(), g2, x2, root.numel(), lambda dst: dst.view(N, Kt)[:, off:off + K])
 
     def adapter(self, ptrs, sizes, job):
         """Queue the weight gradients of one block's adapter (ptrs / sizes of W1, b1, W2, b2; job: see ops.adapter_wgrad_batched): formed
@@ -1168,100 +1162,59 @@ def note_declined(what, why):
         print("[upp_hip] %s: fused path declined (%s); running the torch / library formulation" % (what, why), file=sys.stderr)
 
 
-class _TransposedWeights:
-    """W^T copies of FROZEN weights for the data-gradient GEMMs (dX = dY . W is upp_linear_f32(dY, W^T)).  One copy per
-    weight, made on first use (during the eager warm-up of a captured step) and REFRESHED IN PLACE when the weight's
-    version counter moved (load_state_dict) -- in place, so that HIP graphs that captured the copy's address stay valid;
-    `refresh()` re-copies every entry (call it after loading weights into a model whose step is already captured)."""
+class _TransposedWeights(_derived.DerivedWeights):
+    """W^T copies for the data-gradient GEMMs (dX = dY . W is upp_linear_f32(dY, W^T)): the _derived.DerivedWeights (protocol and CONTRACT
+    there) of any owner's FROZEN weights, in buffers whose rows are zero-padded to a multiple of 4 (get_padded), and of a step driver's
+    trainable weights -- all refreshed by ONE batched launch per step (the pre-training recipe transposed 71 weights one by one: 0.36 ms).
+    A trainable entry's tag is the padded width of get_trainable_padded (False: the plain W^T)."""
 
     def __init__(self):
-        self.entries = {}
-        self.trainable = {}
+        super().__init__("W^T copy", self._make, lambda w, wt, tag: wt.copy_(w.detach().t()), _derived.any_owner, self._refill_batched)
+
+    trainable_anchor = staticmethod(lambda w: w)       # (a step driver's copy lives as long as the tensor it was made for, window or not)
 
     @staticmethod
-    def _view_of(owner, geom):
-        return torch.as_strided(owner.detach(), geom[0], geom[1], geom[2])
+    def _make(w, n_pad):
+        N, K = w.shape
+        if n_pad is not None:                          # a step driver's copy, on the transpose kernel
+            if not n_pad:
+                return ops.transpose(w)
+            full = torch.zeros((K, n_pad), dtype=w.dtype, device=w.device)
+            ops.transpose(w, out=full[:, :N])
+            return full
+        full = torch.zeros(((K + 3) // 4 * 4, N), dtype=w.dtype, device=w.device)        # rows padded to a multiple of 4: get_padded()
+        full._upp_persistent = True            # (ops.PLANES may keep the bf16 plane image of this copy: it lives as long as the entry)
+        full[:K].copy_(w.detach().t())
+        return full[:K]
 
-    def get(self, w):
-        owner = w._base if w._base is not None else w        # a column window of a parameter (w3[:, 256:]) shares its version counter
-        geom = (tuple(w.shape), tuple(w.stride()), w.storage_offset())
-        key = (w.data_ptr(),) + geom
-        e = self.entries.get(key)
-        if e is None or e[0]() is not owner:         # (another tensor on the same address is another weight)
-            if len(self.entries) > 1024:
-                self.entries = {k: v for k, v in self.entries.items() if v[0]() is not None}
-            K = w.shape[1]
-            full = torch.zeros(((K + 3) // 4 * 4, w.shape[0]), dtype=w.dtype, device=w.device)   # rows padded to a multiple of 4: get_padded()
-            full._upp_persistent = True            # (ops.PLANES may keep the bf16 plane image of this copy: it lives as long as the entry)
-            wt = full[:K]
-            wt.copy_(w.detach().t())
-            self.entries[key] = [weakref.ref(owner), owner._version, wt, geom, full]
-            return wt
-        if e[1] != owner._version:
-            if w.is_cuda and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("upp_hip: a frozen weight changed after its W^T copy was made and the stream is capturing; call "
-                                   "upp_hip.functional.refresh_caches(model) after changing weights and before capturing a step")
-            e[2].copy_(w.detach().t())
-            e[1] = owner._version
-        return e[2]
+    @staticmethod
+    def _refill_batched(jobs):
+        pairs = [(w, wt) for w, wt, n_pad in jobs if not n_pad and w.is_contiguous()]
+        ops.transpose_batched(pairs)
+        for w, wt, n_pad in jobs:              # column windows of a parameter (rows not contiguous as a whole), padded copies: one launch each
+            if n_pad or not w.is_contiguous():
+                ops.transpose(w, out=wt[:, :w.shape[0]])
 
     def get_padded(self, w):
         """W^T with zero rows up to a multiple of 4 (K, ceil4(K) x N): the B operand of a data-gradient GEMM whose output width K is
         not a multiple of 4 (K = 3: the first layer of a position MLP whose input carries a gradient); same storage as get(w)."""
-        self.get(w)
-        return self.entries[(w.data_ptr(), tuple(w.shape), tuple(w.stride()), w.storage_offset())][4]
-
-    def refresh(self):
-        for e in self.entries.values():
-            owner = e[0]()
-            if owner is not None:
-                e[2].copy_(self._view_of(owner, e[3]).t())
-                e[1] = owner._version
-
-    # -- trainable weights inside a step driver (TrainStep): their W^T copies are persistent too and are refreshed by ONE batched
-    #    launch at the start of every step (`refresh_trainable`, called by TrainStep._forward_backward while `managed` is set) -- the
-    #    pre-training recipe transposed 71 weights per step one by one (0.36 ms).  Outside a step driver a trainable weight is
-    #    transposed afresh at every use (it may have changed by any means).
-    managed = False
-
-    def get_trainable(self, w):
-        key = ("t", w.data_ptr(), tuple(w.shape), tuple(w.stride()))
-        e = self.trainable.get(key)
-        if e is None or e[0]() is None:
-            wt = ops.transpose(w.detach())
-            self.trainable[key] = [weakref.ref(w), wt, w.is_contiguous()]
-            return wt
-        return e[1]
+        return self.get(w)._base
 
     def get_trainable_padded(self, w, n_pad):
         """W^T of a trainable (N,K) weight as the first N columns of a persistent zero-initialised (K, n_pad) matrix (n_pad >= N): the B
         operand of the data gradient of a Linear layer whose OUTPUT was computed n_pad columns wide (the 50-class layer of the segmentation
         head in a 52-column matrix: _LinearPadN).  Refreshed with the other copies by refresh_trainable."""
-        key = ("tp", w.data_ptr(), tuple(w.shape), tuple(w.stride()), int(n_pad))
-        e = self.trainable.get(key)
-        if e is None or e[0]() is None:
-            full = torch.zeros((w.shape[1], int(n_pad)), dtype=w.dtype, device=w.device)
-            ops.transpose(w.detach(), out=full[:, :w.shape[0]])
-            self.trainable[key] = [weakref.ref(w), full[:, :w.shape[0]], False, full]
-            return full
-        return e[3]
-
-    def refresh_trainable(self):
-        pairs, strided = [], []
-        for key, e in list(self.trainable.items()):
-            w = e[0]()
-            if w is None:
-                del self.trainable[key]
-            elif e[2]:
-                pairs.append((w.detach(), e[1]))
-            else:
-                strided.append((w, e[1]))
-        ops.transpose_batched(pairs)
-        for w, wt in strided:               # column windows of a parameter (rows not contiguous as a whole): one launch each
-            ops.transpose(w.detach(), out=wt)
+        return self.get_trainable(w, tag=int(n_pad))
 
 
 TRANSPOSED = _TransposedWeights()
+
+
+def managed_weights(transposes=True, planes=True, owners=None):
+    """Scope of a step driver (train.TrainStep, the captured evaluation steps): inside it trainable weights are multiplied through
+    persistent W^T copies / bf16 plane images, refreshed here -- transposes, then planes, one launch each -- for the parameters in
+    `owners` (a set of id()s; None: all)."""
+    return _derived.managed(([TRANSPOSED] if transposes else []) + ([ops.PLANES] if planes else []), owners)
 
 
 def refresh_caches(model=None):
@@ -1290,9 +1243,46 @@ def _wt(w):
 
 def linear_usable(x, weight):
     """upp_linear_f32 serves f32 HIP operands with 16-byte aligned rows (contraction length a multiple of 4)."""
-    return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and weight.dim() == 2 and weight.stride(1) == 1
-            and weight.stride(0) % 4 == 0 and weight.data_ptr() % 16 == 0
+    return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and weight.dim() == 2 and _aligned(weight)
             and x.shape[-1] == weight.shape[1] and weight.shape[1] % 4 == 0 and x.numel() > 0)
+
+
+# -- what the backward passes of the Linear nodes share
+_aligned = ops.aligned_rows
+
+
+def _rows(g):
+    """g (..., N) as a contiguous (rows, N) matrix."""
+    g2 = g.reshape(-1, g.shape[-1])
+    return g2 if g2.is_contiguous() else g2.contiguous()
+
+
+def _smallk_dgrad(g2, w):
+    """dX = g2 . W of a small-K layer: the small kernel on a fresh transpose; over more than 64 outputs (_smallk_with_grad: N % 4 == 0 and
+    a frozen weight then) the contraction is too long for it -- the matrix cores, with W^T zero-padded to 4 output columns."""
+    if w.shape[0] > 64:
+        return ops.linear_f32(g2, TRANSPOSED.get_padded(w))[:, :w.shape[1]]
+    return ops.linear_smallk(g2, ops.transpose(w.detach()) if w.requires_grad else w.detach().t().contiguous(), None, 0)
+
+
+def _smallk_wgrad(ptr, g2, x, N, K):
+    """dW (N,K) = g2^T . x on upp_linear_smallk_wgrad_f32 partials, summed by the deferred sums (None: into the buffer registered for ptr)."""
+    x2 = x.reshape(-1, K)
+    if x2.stride(1) != 1:
+        x2 = x2.contiguous()
+    part = ops.linear_smallk_wgrad(g2, x2)
+    _, gw = _DEFERRED.reduce(ptr, part.view(part.shape[0], N * K), 0, N * K)
+    return None if gw is None else gw.view(N, K)
+
+
+def _colsum(ptr, g2):
+    """A bias gradient: the column sums of g2 through the deferred sums (None: into the buffer registered for ptr)."""
+    return _DEFERRED.reduce(ptr, g2, 0, g2.shape[1])[1]
+
+
+def _sum_splits(part):
+    """(splits, N, K) partial weight gradients summed NOW, in split order, on ops.sum_rows (never a torch reduction inside a step)."""
+    return ops.sum_rows(part.view(part.shape[0], -1)).view(part.shape[1:]) if part.shape[0] > 1 else part[0]
 
 
 def _lin(a, w, bias=None, epi=None, aux=None, dgrad=False):
@@ -1318,18 +1308,15 @@ class _LinearMFMA(Function):
     (not on the PEFT hot path: the Transformer weights are frozen there); a trainable bias takes the deferred column sum."""
 
     @staticmethod
-    def forward(ctx, x, w, b, own_wgrad=False):
+    def forward(ctx, x, w, b):
         ctx.save_for_backward(x if w.requires_grad else None, w)
         ctx.bias_ptr = b.data_ptr() if b is not None else 0
-        ctx.own_wgrad = own_wgrad
         return _lin(x, w, b, ops.LIN_BIAS if b is not None else ops.LIN_NONE)
 
     @staticmethod
     def backward(ctx, g):
         x, w = ctx.saved_tensors
-        g2 = g.reshape(-1, g.shape[-1])
-        if not g2.is_contiguous():
-            g2 = g2.contiguous()
+        g2 = _rows(g)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             if w.shape[0] % 4 == 0 and g2.stride(0) % 4 == 0:
@@ -1341,33 +1328,30 @@ class _LinearMFMA(Function):
                 note_declined("linear data gradient", "N = %d is not a multiple of 4" % w.shape[0])
                 gx = torch.mm(g2, w).view(g.shape[:-1] + (w.shape[1],))
         if ctx.needs_input_grad[1]:
-            gw = weight_grad(g2, x.reshape(-1, x.shape[-1]), w, ctx.own_wgrad)
+            gw = weight_grad(g2, x.reshape(-1, x.shape[-1]), w)
         if b_needed(ctx):
-            _, gb = _DEFERRED.reduce(ctx.bias_ptr, g2, 0, g2.shape[1])
-        return gx, gw, gb, None
+            gb = _colsum(ctx.bias_ptr, g2)
+        return gx, gw, gb
 
 
-def weight_grad(g2, x2, w, own=False):
+def weight_grad(g2, x2, w):
     """dW = g2^T . x2 for the trainable weight w (N,K) on upp_linear_wgrad_grouped_f32: inside a training step the pair is queued
     and every weight gradient of the backward pass runs in one launch at the end, its partials summed in split order straight
     into w's slot of the flat gradient buffer (then None is returned); otherwise a group of one, summed at once."""
     N, K = g2.shape[1], x2.shape[1]
     if N % 4 or K % 4 or not g2.is_cuda:
         if N * K <= 2048 and N + K <= 512 and x2.stride(1) == 1 and g2.stride(1) == 1 and g2.is_cuda:
-            part = ops.linear_smallk_wgrad(g2, x2)
-            _, gw = _DEFERRED.reduce(w.data_ptr(), part.view(part.shape[0], N * K), 0, N * K)
-            return None if gw is None else gw.view(N, K)
+            return _smallk_wgrad(w.data_ptr(), g2, x2, N, K)
         if g2.is_cuda:
             note_declined("linear weight gradient (%d,%d)" % (N, K), "N % 4 / K % 4")
         return torch.mm(g2.t(), x2)
-    if g2.stride(1) != 1 or g2.stride(0) % 4 or g2.data_ptr() % 16:          # (a misaligned view: one copy makes it servable)
+    if not _aligned(g2):                                                      # (a misaligned view: one copy makes it servable)
         g2 = g2.contiguous()
-    if x2.stride(1) != 1 or x2.stride(0) % 4 or x2.data_ptr() % 16:
+    if not _aligned(x2):
         x2 = x2.contiguous()
     if _DEFERRED.wgrad(w.data_ptr(), g2, x2) or _DEFERRED.wgrad_window(w, g2, x2):
         return None
-    part = ops.linear_wgrad(g2, x2)
-    return ops.sum_rows(part.view(part.shape[0], -1)).view(part.shape[1:]) if part.shape[0] > 1 else part[0]
+    return _sum_splits(ops.linear_wgrad(g2, x2))
 
 
 def b_needed(ctx):
@@ -1390,25 +1374,14 @@ class _LinearSmallK(Function):
     def backward(ctx, g):
         x, w = ctx.saved_tensors
         N, K = w.shape
-        g2 = g.reshape(-1, N)
-        if not g2.is_contiguous():
-            g2 = g2.contiguous()
+        g2 = _rows(g)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            if N > 64:      # (_smallk_with_grad: N % 4 == 0, frozen weight) contraction too long for the small kernel: the matrix cores,
-                gx = ops.linear_f32(g2, TRANSPOSED.get_padded(w))[:, :K]            # with W^T zero-padded to 4 output columns
-            else:
-                gx = ops.linear_smallk(g2, w.detach().t().contiguous() if not w.requires_grad else ops.transpose(w.detach()), None, 0)
-            gx = gx.reshape(g.shape[:-1] + (K,))
+            gx = _smallk_dgrad(g2, w).reshape(g.shape[:-1] + (K,))
         if ctx.needs_input_grad[1]:
-            x2 = x.reshape(-1, K)
-            if x2.stride(1) != 1:
-                x2 = x2.contiguous()
-            part = ops.linear_smallk_wgrad(g2, x2)
-            _, gw = _DEFERRED.reduce(ctx.ptrs[0], part.view(part.shape[0], N * K), 0, N * K)
-            gw = None if gw is None else gw.view(N, K)
+            gw = _smallk_wgrad(ctx.ptrs[0], g2, x, N, K)
         if ctx.needs_input_grad[2]:
-            _, gb = _DEFERRED.reduce(ctx.ptrs[1], g2, 0, N)
+            gb = _colsum(ctx.ptrs[1], g2)
         return gx, gw, gb
 
 
@@ -1420,19 +1393,19 @@ class _LinearGroupBias(Function):
     def forward(ctx, x, w, gb, rows):
         ctx.save_for_backward(x if w.requires_grad else None, w)
         ctx.rows = rows
-        if w.requires_grad and ops.PLANES.managed and ops.linear_sb_usable(x.shape[0], w.shape[0], w.shape[1]) and w.data_ptr() % 16 == 0 and w.stride(0) % 4 == 0:
+        if w.requires_grad and ops.PLANES.managed and ops.linear_sb_usable(x.shape[0], w.shape[0], w.shape[1]) and _aligned(w):
             return ops.linear_group_bias(x, w, gb, rows, planes=ops.PLANES.get_trainable(w))
         return ops.linear_group_bias(x, w, gb, rows, frozen=not w.requires_grad)
 
     @staticmethod
     def backward(ctx, g):
         x, w = ctx.saved_tensors
-        g2 = g if g.is_contiguous() else g.contiguous()
+        g2 = _rows(g)
         gx = gw = ggb = None
         if ctx.needs_input_grad[0]:
             gx = _lin(g2, w, dgrad=True)
         if ctx.needs_input_grad[1]:
-            gw = weight_grad(g2, x, w, True)
+            gw = weight_grad(g2, x, w)
         if ctx.needs_input_grad[2]:
             groups = g2.shape[0] // ctx.rows
             if g2.is_cuda and g2.dtype == torch.float32 and groups * ctx.rows == g2.shape[0] and 1 <= groups <= 65535:
@@ -1496,15 +1469,14 @@ def linear_group_bias(x, weight, group_bias, rows_per_group):
     M, K = x.shape
     N = weight.shape[0]
     r = int(rows_per_group)
-    if (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.stride(1) == 1 and x.stride(0) % 4 == 0
-            and x.data_ptr() % 16 == 0 and weight.stride(1) == 1 and weight.stride(0) % 4 == 0 and weight.data_ptr() % 16 == 0
+    if (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and _aligned(x) and _aligned(weight)
             and (K % 4 == 0 and weight.shape[1] == K) and ops.linear_group_bias_usable(M, N, K, r)
             and (not (torch.is_grad_enabled() and x.requires_grad) or K % 4 == 0)):
         gb = group_bias.contiguous()
         if not torch.is_grad_enabled() or not (x.requires_grad or weight.requires_grad or gb.requires_grad):
             return ops.linear_group_bias(x, weight, gb, r, frozen=not weight.requires_grad)
         return _LinearGroupBias.apply(x, weight, gb, r)
-    y = linear(x, weight, own_wgrad=True)
+    y = linear(x, weight)
     if y.is_cuda and y.dtype == torch.float32 and M % r == 0 and 1 <= M // r <= 65535 and torch.is_grad_enabled() and group_bias.requires_grad:
         return _GroupBiasAdd.apply(y, group_bias, r)
     return (y.view(M // r, r, N) + group_bias.unsqueeze(1)).view(M, N)
@@ -1527,14 +1499,14 @@ def _act_torch(y, act):
     return y if act is None else (F.relu(y) if act == 'relu' else F.gelu(y))
 
 
-def linear(x, weight, bias=None, own_wgrad=False, act=None):
+def linear(x, weight, bias=None, act=None):
     """act(F.linear(x, weight, bias)) on this library's kernels: upp_linear_f32 (FP32 matrix cores) for 16-byte aligned rows and
     K % 4 == 0, upp_linear_smallk_f32 (K <= 64, N <= 256, forward only) for the rest; otherwise the library GEMM (said once under
     UPP_VERBOSE).  act: None / 'relu' / 'gelu' (erf) -- fused into the epilogue when nothing needs a gradient, applied by torch
-    otherwise.  own_wgrad: kept for callers of round 2 (every weight gradient is ours now, whatever the row count)."""
+    otherwise."""
     needs_grad = torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad))
     if (x.is_cuda and weight.dim() == 2 and weight.dtype == torch.float32 and weight.shape[1] % 4 == 0 and weight.shape[1] > 64
-            and (weight.stride(1) != 1 or weight.stride(0) % 4 or weight.data_ptr() % 16)):
+            and not _aligned(weight)):
         # a column window of a wider weight whose rows start off a 16-byte boundary (w[:, 3:] of the (1536, 1155) first layer of the
         # segmentation head's feature propagation): inside a step driver a trainable window of a parameter is multiplied through its
         # persistent bf16 plane image and its gradient lands in the parameter's gradient window (_DeferredSums.wgrad_window) -- no copy;
@@ -1545,14 +1517,14 @@ def linear(x, weight, bias=None, own_wgrad=False, act=None):
                          and ops.linear_sb_usable(rows, weight.shape[0], weight.shape[1])
                          and (not x.requires_grad or ops.linear_sb_usable(rows, weight.shape[1], weight.shape[0])))
         if window_ok:
-            return _act_torch(_LinearMFMA.apply(x, weight, bias, bool(own_wgrad)), act)
+            return _act_torch(_LinearMFMA.apply(x, weight, bias), act)
         weight = weight.contiguous()
     if needs_grad and weight.dim() == 2 and weight.shape[0] % 4 and weight.shape[0] > 16 and linear_usable(x, weight):
         # the data gradient contracts over the N outputs and the weight gradient is (N, K): both want N % 4 == 0 (the 50 part classes of
         # the segmentation head's last layer).  Zero rows up to the next multiple of 4 -- their outputs are sliced off, their gradient
         # rows are dropped by the pad's backward -- keep forward and both gradients on our kernels.
         pad = -weight.shape[0] % 4
-        y = linear(x, F.pad(weight, (0, 0, 0, pad)), None if bias is None else F.pad(bias, (0, pad)), own_wgrad, act)
+        y = linear(x, F.pad(weight, (0, 0, 0, pad)), None if bias is None else F.pad(bias, (0, pad)), act)
         return y[..., :weight.shape[0]]
     if not linear_usable(x, weight):
         if (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and weight.dim() == 2 and x.shape[-1] == weight.shape[1]
@@ -1567,7 +1539,7 @@ def linear(x, weight, bias=None, own_wgrad=False, act=None):
         if act is not None and bias is None:
             bias = _zero_bias(weight)
         return ops.linear_f32(x, weight, bias, _ACT_EPI[act][0] if bias is not None else ops.LIN_NONE, frozen=not weight.requires_grad)
-    return _act_torch(_LinearMFMA.apply(x, weight, bias, bool(own_wgrad)), act)
+    return _act_torch(_LinearMFMA.apply(x, weight, bias), act)
 
 
 _ZERO_BIAS = {}
@@ -1600,9 +1572,7 @@ class _MlpGelu(Function):
     def backward(ctx, g):
         d, w1, w2, x, hid = ctx.saved_tensors
         need = ctx.needs_input_grad
-        g2 = g.reshape(-1, g.shape[-1])
-        if not g2.is_contiguous():
-            g2 = g2.contiguous()
+        g2 = _rows(g)
         g_z = _lin(g2, w2, None, ops.LIN_MUL, aux=d.view(-1, d.shape[-1]), dgrad=True)
         gx = None
         if need[0]:
@@ -1611,11 +1581,11 @@ class _MlpGelu(Function):
         if need[1]:
             gw1 = weight_grad(g_z, x.reshape(-1, x.shape[-1]), w1)
         if need[2]:
-            _, gb1 = _DEFERRED.reduce(ctx.bias_ptrs[0], g_z, 0, g_z.shape[1])
+            gb1 = _colsum(ctx.bias_ptrs[0], g_z)
         if need[3]:
             gw2 = weight_grad(g2, hid.reshape(-1, hid.shape[-1]), w2)
         if len(need) > 4 and need[4]:
-            _, gb2 = _DEFERRED.reduce(ctx.bias_ptrs[1], g2, 0, g2.shape[1])
+            gb2 = _colsum(ctx.bias_ptrs[1], g2)
         return gx, gw1, gb1, gw2, gb2
 
 
@@ -1642,30 +1612,19 @@ class _MlpSmallKGelu(Function):
         x, w1, w2, d, hid = ctx.saved_tensors
         need = ctx.needs_input_grad
         H, K = w1.shape
-        g2 = g.reshape(-1, g.shape[-1])
-        if not g2.is_contiguous():
-            g2 = g2.contiguous()
+        g2 = _rows(g)
         g_z = _lin(g2, w2, None, ops.LIN_MUL, aux=d.view(-1, H), dgrad=True)                 # (rows, H) = gradient at the pre-activation
         gx = gw1 = gb1 = gw2 = gb2 = None
         if need[0]:
-            if H > 64:
-                gx = ops.linear_f32(g_z, TRANSPOSED.get_padded(w1))[:, :K]                   # (_smallk_gelu_usable: w1 frozen then)
-            else:
-                gx = ops.linear_smallk(g_z, w1.detach().t().contiguous() if not w1.requires_grad else ops.transpose(w1.detach()), None, 0)
-            gx = gx.reshape(g.shape[:-1] + (K,))
+            gx = _smallk_dgrad(g_z, w1).reshape(g.shape[:-1] + (K,))
         if need[1]:
-            x2 = x.reshape(-1, K)
-            if x2.stride(1) != 1:
-                x2 = x2.contiguous()
-            part = ops.linear_smallk_wgrad(g_z, x2)
-            _, gw1 = _DEFERRED.reduce(ctx.ptrs[0], part.view(part.shape[0], H * K), 0, H * K)
-            gw1 = None if gw1 is None else gw1.view(H, K)
+            gw1 = _smallk_wgrad(ctx.ptrs[0], g_z, x, H, K)
         if need[2]:
-            _, gb1 = _DEFERRED.reduce(ctx.ptrs[1], g_z, 0, H)
+            gb1 = _colsum(ctx.ptrs[1], g_z)
         if need[3]:
             gw2 = weight_grad(g2, hid.reshape(-1, H), w2)
         if need[4]:
-            _, gb2 = _DEFERRED.reduce(ctx.ptrs[2], g2, 0, g2.shape[1])
+            gb2 = _colsum(ctx.ptrs[2], g2)
         return gx, gw1, gb1, gw2, gb2
 
 
@@ -1675,7 +1634,7 @@ def mlp_smallk_gelu_usable(x, w1, b1, w2, b2):
     kernels' and the hidden width allows a small-K weight gradient."""
     H = w1.shape[0]
     return (_smallk_with_grad(x, w1) and b1 is not None and H % 4 == 0 and H * w1.shape[1] <= 2048 and w2.dim() == 2 and w2.shape[1] == H
-            and w2.dtype == torch.float32 and w2.stride(1) == 1 and w2.stride(0) % 4 == 0 and w2.data_ptr() % 16 == 0 and w2.shape[0] % 4 == 0
+            and w2.dtype == torch.float32 and _aligned(w2) and w2.shape[0] % 4 == 0
             and (b2 is None or b2.data_ptr() % 16 == 0))
 
 
@@ -2121,7 +2080,7 @@ class _LinearPadN(Function):
     def backward(ctx, g):
         x, w = ctx.saved_tensors
         N, K = w.shape
-        g = g if g.is_contiguous() else g.contiguous()
+        g = _rows(g)
         gx = gw = None
         if ctx.needs_input_grad[0]:
             wt = (TRANSPOSED.get_trainable_padded(w, ctx.Np) if w.requires_grad and TRANSPOSED.managed
@@ -2129,15 +2088,14 @@ class _LinearPadN(Function):
             gx = ops.linear_f32(g, wt)
         if ctx.needs_input_grad[1]:
             if not _DEFERRED.wgrad_rows(w.data_ptr(), g, x, N):
-                part = ops.linear_wgrad(g, x)
-                gw = (part.sum(dim=0) if part.shape[0] > 1 else part[0])[:N]
+                gw = _sum_splits(ops.linear_wgrad(g, x))[:N]
         return gx, gw
 
 
 def linear_pad_n_usable(x, w):
     """Can _LinearPadN serve F.linear(x, w) for an (N,K) weight with N % 4 != 0?  HIP f32 rows, the split-bf16 kernel takes (M, ceil4(N), K),
     and the weight is frozen or managed by a step driver (persistent plane image and padded W^T, refreshed once per step)."""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and _aligned(x)
             and w.dim() == 2 and w.dtype == torch.float32 and w.stride(1) == 1 and x.shape[1] == w.shape[1] and w.shape[0] % 4 != 0):
         return False
     if w.requires_grad and torch.is_grad_enabled() and not (ops.PLANES.managed and TRANSPOSED.managed and isinstance(w._base if w._base is not None else w, torch.nn.Parameter)):

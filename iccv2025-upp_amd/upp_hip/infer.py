@@ -126,14 +126,8 @@ class _CapturedStep:
 
     def _evaluate(self):
         """The captured region."""
-        was = ops.PLANES.managed
-        ops.PLANES.managed = True
-        try:
-            with torch.no_grad():
-                ops.PLANES.refresh_trainable(self._owners)     # (the graph's first launch: the model's trainable weights, split)
-                self._body()
-        finally:
-            ops.PLANES.managed = was
+        with torch.no_grad(), HF.managed_weights(transposes=False, owners=self._owners):   # (the graph's first launch: the model's
+            self._body()                                                                   #  trainable weights, split)
 
     def _params(self):
         return list(self.model.parameters()) + list(self.model.buffers())

@@ -6,11 +6,10 @@ never allocates), and enqueues the HIP kernels on torch's current stream.
 CPU tensors raise: there is no fallback path.
 """
 import os
-import weakref
 
 import torch
 
-from . import _abi
+from . import _abi, _derived
 
 
 def _need(t, name, dtype, ndim=None, last=None):
@@ -1156,6 +1155,7 @@ class time_linear_calls:
     def __enter__(self):
         self.calls = []
         self.wgrad_groups = []          # [(M, N, K), ...] per upp_linear_wgrad_grouped_f32 launch
+        self.group_bias = []            # (M, N, K) per group-bias launch (also listed in `calls`)
         time_linear_calls.active = self
         return self
 
@@ -1167,27 +1167,44 @@ class time_linear_calls:
         torch.cuda.synchronize()
         return [(M, N, K, e, a.elapsed_time(b), sb) for (M, N, K, e, a, b, sb) in self.calls]
 
+    @classmethod
+    def bracket(cls, ev0=None, *what):
+        """bracket() before a launch -> its start event (None outside a scope); bracket(ev0, M, N, K, epilogue, sb) after it."""
+        if cls.active is None:
+            return None
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record()
+        if what:
+            cls.active.calls.append(what[:4] + (ev0, ev) + what[4:])
+        return ev
+
+
+def _is_matrix(t):                     # a 2-D f32 HIP matrix with contiguous rows: what the Linear kernels read through a row stride
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1
+
+
+def _need_matrix(t, name):
+    if not _is_matrix(t):
+        raise RuntimeError(f"{name} must be a 2-D f32 HIP (cuda) matrix with contiguous rows; upp_hip has no CPU path")
+
+
+def aligned_rows(t):                   # rows the matrix-core kernels load 16 bytes at a time: whole float4s from a 16-byte aligned base
+    return t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
+
 
 SPLIT_BF16 = os.environ.get("UPP_SPLIT_BF16", "1") != "0"      # frozen weights on the bf16 matrix pipe at f32 accuracy (csrc/linear_sb.hip)
 
 
-class _WeightPlanes:
-    """bf16 plane images (upp_linear_sb_prep) of FROZEN weights and of their cached transposes.  Cached -- one image per weight, made on
-    first use (the eager warm-up of a captured step) and refreshed IN PLACE when the version counter of the weight's storage moved
-    (load_state_dict, the in-place refresh of a cached W^T), so that HIP graphs that captured the image's address stay valid -- only for
-    weights whose storage owner is PERSISTENT: an nn.Parameter, or a buffer marked `_upp_persistent` by its keeper (functional.TRANSPOSED's
-    W^T copies, the patch embedding's zero-padded first-layer weight).  An entry is valid for the owner OBJECT it was made for: another
-    tensor that lands on the same address gets a new image.  Any other weight (a `.contiguous()` copy of a misaligned column window, a
-    padded temporary) is split afresh at every use into a buffer of its own: replacing a cached image would free memory that an already
-    captured graph still reads.  `refresh()` re-splits every live entry (functional.refresh_caches: weights loaded into a model whose
-    step is already captured).
-    CONTRACT: validity is keyed on torch's version counter of the owner.  A write that bypasses it -- `p.data.copy_()`, `p.data.mul_()`, a
-    custom kernel writing a frozen weight -- leaves the image stale without any error: call functional.refresh_caches(model) after such
-    a write (README "Changing frozen weights").  train.TrainStep calls it at construction."""
+class _WeightPlanes(_derived.DerivedWeights):
+    """bf16 plane images (upp_linear_sb_prep) of weights and of their cached transposes: the _derived.DerivedWeights (protocol and CONTRACT
+    there) of the split-bf16 kernels, kept only for PERSISTENT owners -- an nn.Parameter, or a buffer marked `_upp_persistent` by its keeper
+    (functional.TRANSPOSED's W^T copies, the patch embedding's zero-padded first-layer weight).  A step driver's trainable weights have the
+    images of W (forward) and of W^T (data gradient, split straight from W: the entry's tag) re-split by one launch per step; outside a
+    driver a trainable weight stays on the exact-f32 kernel."""
 
     def __init__(self):
-        self.entries = {}
-        self.trainable = {}
+        super().__init__("bf16 plane image", lambda w, transposed: self._split(w, None, bool(transposed)),
+                         lambda w, planes, transposed: self._split(w, planes, bool(transposed)), _derived.persistent_owner, self._split_batched)
 
     @staticmethod
     def _split(w, planes=None, transposed=False):
@@ -1198,38 +1215,10 @@ class _WeightPlanes:
         _call(w.device, "upp_linear_sb_prep", _abi.ptr(w), w.stride(0), N, K, 1 if transposed else 0, _abi.ptr(planes))
         return planes
 
-    # -- trainable weights inside a step driver (train.TrainStep sets `managed`): the plane images of W (forward) and of W^T (data gradient,
-    #    split straight from W) are persistent and ALL re-split by one launch at the start of every step (`refresh_trainable`), i.e. after
-    #    whatever changed the weights since the last step (the flat AdamW kernel writes them without touching torch's version counters).
-    #    Outside a step driver a trainable weight stays on the exact-f32 kernel (it may have changed by any means).
-    managed = False
-
-    def get_trainable(self, w, transposed=False):
-        owner = w._base if w._base is not None else w
-        if not isinstance(owner, torch.nn.Parameter):           # a computed weight (padded, concatenated ...): split where it is used
-            return self._split(w.detach(), None, transposed)
-        key = (w.data_ptr(), tuple(w.shape), tuple(w.stride()), bool(transposed))
-        e = self.trainable.get(key)
-        if e is None or e[0]() is not owner:
-            planes = self._split(w.detach(), None, transposed)
-            self.trainable[key] = [weakref.ref(owner), planes, bool(transposed), (tuple(w.shape), tuple(w.stride()), w.storage_offset())]
-            return planes
-        return e[1]
-
-    def refresh_trainable(self, owners=None):
-        """owners: a set of id()s of parameters -- only their images (an evaluation graph refreshes the weights of ITS model)."""
+    @staticmethod
+    def _split_batched(jobs):
+        """jobs: [(w, planes, transposed)] -- every image re-split by ONE launch (upp_linear_sb_prep_batched)."""
         import ctypes
-        jobs = []
-        for key, e in list(self.trainable.items()):
-            owner = e[0]()
-            if owner is None:
-                del self.trainable[key]
-            elif owners is not None and id(owner) not in owners:
-                continue
-            else:
-                jobs.append((torch.as_strided(owner.detach(), e[3][0], e[3][1], e[3][2]), e[1], e[2]))
-        if not jobs:
-            return
         k = len(jobs)
         W = (ctypes.c_void_p * k)(*[w.data_ptr() for w, _, _ in jobs])
         ld = (ctypes.c_longlong * k)(*[w.stride(0) for w, _, _ in jobs])
@@ -1238,35 +1227,6 @@ class _WeightPlanes:
         T = (ctypes.c_int * k)(*[1 if tr else 0 for _, _, tr in jobs])
         P = (ctypes.c_void_p * k)(*[p.data_ptr() for _, p, _ in jobs])
         _call(jobs[0][0].device, "upp_linear_sb_prep_batched", W, ld, N, K, T, P, k)
-
-    def get(self, w):
-        owner = w._base if w._base is not None else w
-        if not (isinstance(owner, torch.nn.Parameter) or getattr(owner, "_upp_persistent", False)):
-            return self._split(w)
-        key = (w.data_ptr(), tuple(w.shape), tuple(w.stride()))
-        e = self.entries.get(key)
-        if e is None or e[0]() is not owner:
-            if len(self.entries) > 1024:
-                self.entries = {k: v for k, v in self.entries.items() if v[0]() is not None}
-            planes = self._split(w)
-            self.entries[key] = [weakref.ref(owner), owner._version, planes, (tuple(w.shape), tuple(w.stride()), w.storage_offset())]
-            return planes
-        if e[1] != owner._version:
-            if torch.cuda.is_current_stream_capturing():
-                # the image is stale and a re-split here would be baked into the graph as a launch of its own: refuse loudly instead of
-                # multiplying by the old weight (round-4 advisor).  Weights change BETWEEN captures: refresh the caches there.
-                raise RuntimeError("upp_hip: a frozen weight changed after its bf16 plane image was made and the stream is capturing; call "
-                                   "upp_hip.functional.refresh_caches(model) after changing weights and before capturing a step")
-            self._split(w, e[2])
-            e[1] = owner._version
-        return e[2]
-
-    def refresh(self):
-        for e in self.entries.values():
-            owner = e[0]()
-            if owner is not None:
-                self._split(torch.as_strided(owner.detach(), e[3][0], e[3][1], e[3][2]), e[2])
-                e[1] = owner._version
 
 
 PLANES = _WeightPlanes()
@@ -1298,8 +1258,7 @@ def linear_f32(a, w, bias=None, epilogue=LIN_NONE, aux=None, tile=0, out=None, f
     if planes is not None:
         N, Kw = wshape
     else:
-        if not (isinstance(w, torch.Tensor) and w.is_cuda and w.dtype == torch.float32 and w.dim() == 2 and w.stride(1) == 1):
-            raise RuntimeError("w must be a 2-D f32 HIP (cuda) matrix with contiguous rows; upp_hip has no CPU path")
+        _need_matrix(w, "w")
         _same_device(a, w)
         N, Kw = w.shape
     if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == torch.float32):
@@ -1308,7 +1267,7 @@ def linear_f32(a, w, bias=None, epilogue=LIN_NONE, aux=None, tile=0, out=None, f
     if Kw != K:
         raise RuntimeError(f"linear_f32: a (...,{K}) against w ({N},{Kw})")
     a2 = a.reshape(-1, K)
-    if a2.stride(1) != 1 or a2.stride(0) % 4 != 0 or a2.data_ptr() % 16 != 0:      # (a column window with a misaligned base: one copy)
+    if not aligned_rows(a2):                                                        # (a column window with a misaligned base: one copy)
         a2 = a2.contiguous()
     M = a2.shape[0]
     lead = tuple(a.shape[:-1])
@@ -1333,25 +1292,20 @@ def linear_f32(a, w, bias=None, epilogue=LIN_NONE, aux=None, tile=0, out=None, f
         sb = linear_sb_tile(M, N, K)
         if not (sb and _sb_servable(N, K, out, bias, aux)):
             raise RuntimeError("linear_f32: plane images given for a problem the split-bf16 kernel does not take (ask linear_sb_usable first)")
-    scope = time_linear_calls.active
-    if scope is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = time_linear_calls.bracket()
     if sb:
         _call(a.device, "upp_linear_sb_f32", _abi.ptr(a2), a2.stride(0), _abi.ptr(planes), _abi.ptr(bias), _abi.ptr(out), N,
               _abi.ptr(aux), N, M, N, K, int(epilogue), sb)
     else:
         _call(a.device, "upp_linear_f32", _abi.ptr(a2), a2.stride(0), _abi.ptr(w), w.stride(0), _abi.ptr(bias), _abi.ptr(out), N,
               _abi.ptr(aux), N, M, N, K, int(epilogue), int(tile))
-    if scope is not None:
-        ev1.record()
-        scope.calls.append((M, N, K, int(epilogue), ev0, ev1, sb))
+    time_linear_calls.bracket(ev0, M, N, K, int(epilogue), sb)
     return (out, d) if epilogue == LIN_BIAS_GELU_D else out
 
 
 def colsum_partials(part, offset, length, chunks=None):
     """(chunks, length) partial column sums of columns [offset, offset + length) of the tall 2-D matrix `part` (upp_colsum_partials)."""
-    if not (isinstance(part, torch.Tensor) and part.is_cuda and part.dtype == torch.float32 and part.dim() == 2 and part.stride(1) == 1):
+    if not _is_matrix(part):
         raise RuntimeError("colsum_partials: a 2-D f32 HIP (cuda) matrix with contiguous rows is required; upp_hip has no CPU path")
     if offset < 0 or length < 1 or offset + length > part.shape[1]:
         raise RuntimeError(f"colsum_partials: columns [{offset}, {offset + length}) outside {tuple(part.shape)}")
@@ -1551,9 +1505,8 @@ def linear_smallk(x, w, bias=None, act=0):
 def linear_smallk_wgrad(g, x, chunks=None):
     """(chunks, N, K) partial weight gradients of a small Linear: sum over dim 0 = g^T . x (g (M,N), x (M,K), N K <= 2048);
     upp_linear_smallk_wgrad_f32."""
-    for t_, n_ in ((g, "g"), (x, "x")):
-        if not (isinstance(t_, torch.Tensor) and t_.is_cuda and t_.dtype == torch.float32 and t_.dim() == 2 and t_.stride(1) == 1):
-            raise RuntimeError(f"{n_} must be a 2-D f32 HIP (cuda) matrix with contiguous rows; upp_hip has no CPU path")
+    _need_matrix(g, "g")
+    _need_matrix(x, "x")
     M, N = g.shape
     K = x.shape[1]
     if x.shape[0] != M or N * K > 2048:
@@ -1590,7 +1543,7 @@ def linear_smallk_gelu_d(x, w, bias):
 
 def transpose(w, out=None):
     """W^T of a 2-D f32 matrix with contiguous rows (upp_transpose_f32); `out` (cols, rows) is overwritten in place when given."""
-    if not (isinstance(w, torch.Tensor) and w.is_cuda and w.dtype == torch.float32 and w.dim() == 2 and w.stride(1) == 1):
+    if not _is_matrix(w):
         raise RuntimeError("transpose: a 2-D f32 HIP (cuda) matrix with contiguous rows is required (column windows are fine)")
     rows, cols = w.shape
     if out is None:
@@ -1602,9 +1555,8 @@ def transpose(w, out=None):
 def linear_wgrad(g, x):
     """Partial weight gradients (splits, N, K) of y = x . W^T: sum over dim 0 = g^T . x  (g (M,N), x (M,K); upp_linear_wgrad_f32).
     The caller sums the splits (batched_sum / the deferred sums of a training step)."""
-    for t, name in ((g, "g"), (x, "x")):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1):
-            raise RuntimeError(f"{name} must be a 2-D f32 HIP (cuda) matrix with contiguous rows; upp_hip has no CPU path")
+    _need_matrix(g, "g")
+    _need_matrix(x, "x")
     _same_device(g, x)
     M, N = g.shape
     K = x.shape[1]
@@ -1631,9 +1583,9 @@ def linear_group_bias(a, w, bias, rows_per_group, frozen=False, planes=None):
     """C (M,N) = a (M,K) . w (N,K)^T + bias[m // rows_per_group] -- the bias of a GROUP of rows added in the GEMM's epilogue
     (upp_linear_group_bias_f32, or upp_linear_sb_group_bias_f32 for a frozen weight / a plane image handed over by the caller: see
     linear_f32); bias (M / rows_per_group, N) contiguous."""
-    for t, name in ((a, "a"), (w, "w"), (bias, "bias")):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1):
-            raise RuntimeError(f"{name} must be a 2-D f32 HIP (cuda) matrix with contiguous rows; upp_hip has no CPU path")
+    _need_matrix(a, "a")
+    _need_matrix(w, "w")
+    _need_matrix(bias, "bias")
     _same_device(a, w, bias)
     M, K = a.shape
     N = w.shape[0]
@@ -1646,20 +1598,16 @@ def linear_group_bias(a, w, bias, rows_per_group, frozen=False, planes=None):
         sb = linear_sb_tile(M, N, K)
         if planes is None:
             planes = PLANES.get(w)
-    scope = time_linear_calls.active
-    if scope is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = time_linear_calls.bracket()
     if sb:
         _call(a.device, "upp_linear_sb_group_bias_f32", _abi.ptr(a), a.stride(0), _abi.ptr(planes), _abi.ptr(bias), r.bit_length() - 1,
               _abi.ptr(out), N, M, N, K)
     else:
         _call(a.device, "upp_linear_group_bias_f32", _abi.ptr(a), a.stride(0), _abi.ptr(w), w.stride(0), _abi.ptr(bias), r.bit_length() - 1,
               _abi.ptr(out), N, M, N, K)
-    if scope is not None:
-        ev1.record()
-        scope.group_bias = getattr(scope, "group_bias", []) + [(M, N, K)]
-        scope.calls.append((M, N, K, LIN_BIAS, ev0, ev1, sb))
+    if ev0 is not None:
+        time_linear_calls.active.group_bias.append((M, N, K))
+    time_linear_calls.bracket(ev0, M, N, K, LIN_BIAS, sb)
     return out
 
 
@@ -1676,7 +1624,7 @@ def linear_wgrad_grouped(pairs):
     dev = pairs[0][0].device
     for g, x in pairs:
         for t, name in ((g, "g"), (x, "x")):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.device == dev):
+            if not (_is_matrix(t) and t.device == dev):
                 raise RuntimeError(f"{name} must be a 2-D f32 matrix with contiguous rows on one HIP (cuda) device; upp_hip has no CPU path")
         if x.shape[0] != g.shape[0]:
             raise RuntimeError("linear_wgrad_grouped: row counts differ")

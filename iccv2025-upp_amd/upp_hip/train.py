@@ -257,7 +257,7 @@ class TrainStep:
                               if self.device.type == 'cuda' else None)
         if self.device.type == 'cuda':
             # derived copies of frozen weights (W^T, bf16 plane images) that an earlier eager forward cached are brought up to date before
-            # anything is captured: a weight written through `.data` since then moved no version counter (ops._WeightPlanes CONTRACT)
+            # anything is captured: a weight written through `.data` since then moved no version counter (_derived.DerivedWeights CONTRACT)
             HF.refresh_caches(model)
 
     # -- the two halves of a step ------------------------------------------------------------
@@ -276,13 +276,9 @@ class TrainStep:
         self.flat.zero()
         for p in self.trainable:
             p.grad = None              # let autograd write fresh gradients: no per-parameter accumulate kernels
-        # W^T copies of the trainable weights (data-gradient GEMMs): persistent inside this driver, all refreshed by one launch here,
+        # W^T copies and bf16 plane images of the trainable weights: persistent inside this driver, each kind refreshed by one launch here,
         # i.e. after whatever changed the weights since the last step (optimizer, load_state_dict, a restore)
-        was, was_p = HF.TRANSPOSED.managed, HF.ops.PLANES.managed
-        HF.TRANSPOSED.managed = HF.ops.PLANES.managed = True
-        try:
-            HF.TRANSPOSED.refresh_trainable()
-            HF.ops.PLANES.refresh_trainable()          # (the bf16 plane images of the trainable weights and of their transposes: one launch)
+        with HF.managed_weights():
             if self.loss_fn is not None:
                 loss, acc = self.loss_fn(self.model, *self.inputs)
             else:
@@ -294,8 +290,6 @@ class TrainStep:
                 if self._seed is None or self._seed.device != loss.device or self._seed.dtype != loss.dtype:
                     self._seed = torch.ones((), dtype=loss.dtype, device=loss.device)
                 torch.autograd.backward(loss, grad_tensors=self._seed)
-        finally:
-            HF.TRANSPOSED.managed, HF.ops.PLANES.managed = was, was_p
         # by-products the model keeps of its last forward (`aux`: the completion prompter's rebuilt points) must not keep this pass's autograd
         # graph alive: its AccumulateGrad nodes would be reused by the next pass with the stream THIS pass ran on -- under capture that is a
         # fork into the warm-up's stream inside the graph (torch warns "AccumulateGrad node's stream does not match"; a fork costs 65-115 us)

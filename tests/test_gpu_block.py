@@ -882,18 +882,13 @@ def test_column_windows_of_a_weight_train_without_copies(N, Kt, a):
     ref = torch.nn.functional.linear(x1, w[:, :a]) + torch.nn.functional.linear(x2, w[:, a:])
     gx1, gx2, gP = torch.autograd.grad(ref, (x1, x2, P), g)
     buf = torch.full((N * Kt,), 0.25, device='cuda')
-    was = ops.PLANES.managed
-    ops.PLANES.managed = True
-    try:
-        ops.PLANES.refresh_trainable()
+    with HF.managed_weights(transposes=False):
         with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
             with HF.deferred_sums({P.data_ptr(): buf.view(N, Kt, 1)}) as scope:
                 out = HF.linear(x1, w[:, :a]) + HF.linear(x2, w[:, a:])
                 ops.PLANES.refresh_trainable()                                       # (windows first seen in this pass get their images)
                 hx1, hx2, hP = torch.autograd.grad(out, (x1, x2, P), g, allow_unused=True)
             torch.cuda.synchronize()
-    finally:
-        ops.PLANES.managed = was
     close(out, ref, rtol=1e-5, atol_scale=2e-6)
     close(hx1, gx1, rtol=1e-5, atol_scale=2e-6)
     close(hx2, gx2, rtol=1e-5, atol_scale=2e-6)

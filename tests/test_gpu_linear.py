@@ -378,7 +378,7 @@ def test_activation_epilogues_through_hf_linear(act):
         close(HF.linear(x, w, None, act=act), _a(F.linear(x, w), act))
     xg = x.clone().requires_grad_(True)                      # with a gradient: the activation is torch's, the GEMMs ours
     wg = w.clone().requires_grad_(True)
-    out = HF.linear(xg, wg, b, act=act, own_wgrad=True)
+    out = HF.linear(xg, wg, b, act=act)
     close(out, ref)
     out.backward(torch.ones_like(out))
     xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
@@ -513,9 +513,7 @@ def test_trainable_weight_transposes_follow_the_weights_inside_a_step_driver():
     def refs():
         return [torch.ones(50, w.shape[0], device='cuda') @ w.detach() for w in ws]
 
-    HF.TRANSPOSED.managed = True
-    try:
-        HF.TRANSPOSED.refresh_trainable()
+    with HF.managed_weights(planes=False):
         for a, b in zip(grads(), refs()):
             close(a, b)
         with torch.no_grad():
@@ -526,8 +524,6 @@ def test_trainable_weight_transposes_follow_the_weights_inside_a_step_driver():
         HF.TRANSPOSED.refresh_trainable()                    # what TrainStep._forward_backward does first
         for a, b in zip(grads(), refs()):
             close(a, b)
-    finally:
-        HF.TRANSPOSED.managed = False
     with torch.no_grad():
         ws[0].mul_(0.5)
     close(grads()[0], refs()[0])                             # unmanaged: transposed at every use
@@ -535,3 +531,38 @@ def test_trainable_weight_transposes_follow_the_weights_inside_a_step_driver():
     ops.transpose_batched(pairs)
     for src, dst in pairs:
         assert torch.equal(dst, src.t().contiguous())
+
+
+def test_pad_n_weight_gradient_outside_a_deferred_scope_sums_its_splits_on_own_kernels():
+    """HF._LinearPadN (the 50-class layer of the segmentation head) called where no deferred_sums scope takes its weight gradient: the
+    (splits, 52, 128) partials of ops.linear_wgrad -- 16 splits at 4,096 rows, no need for more rows -- are summed at once by
+    ops.sum_rows, as weight_grad does, and not by a torch reduction (which zeroes its semaphores with a memset: wrong from the second
+    replay of a captured step on).  Against the float64 product under the weight-gradient bound of this file."""
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path[:0] = [p for p in (root, os.path.join(root, "tools")) if p not in sys.path]
+    from memset_census import memsets_of
+    M, N, K, Np = 4096, 50, 128, 52
+    gen = torch.Generator(device='cuda').manual_seed(M + N + K)
+    w = torch.nn.Parameter(torch.randn(N, K, device='cuda', generator=gen) * K ** -0.5)
+    x = torch.randn(M, K, device='cuda', generator=gen)
+    g = torch.randn(M, Np, device='cuda', generator=gen)
+    g[:, N:] = 0.0                                                        # (what the log-softmax backward hands over)
+    assert ops.linear_sb_usable(M, Np, K)
+    assert ops.linear_wgrad(g, x).shape[0] > 1
+    ref = (g.double().t() @ x.double())[:N]
+    with HF.managed_weights():
+        assert HF.linear_pad_n_usable(x, w)
+        y = HF._LinearPadN.apply(x, w)
+        y.backward(g, retain_graph=True)
+        close(w.grad, ref, rtol=2e-5, atol_scale=2e-5)
+        w.grad = None
+        found = memsets_of(lambda: y.backward(g, retain_graph=True))
+        close(w.grad, ref, rtol=2e-5, atol_scale=2e-5)
+        with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
+            torch.autograd.grad(y, w, g)
+            torch.cuda.synchronize()
+    assert not found, found
+    names = [e.key for e in prof.key_averages()]
+    assert names and not any("reduce_kernel" in n_ or "memset" in n_.lower() for n_ in names), names

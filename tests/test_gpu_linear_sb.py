@@ -306,20 +306,18 @@ def test_trainable_weights_take_the_split_kernel_inside_a_step_driver_only():
     assert [c[6] for c in scope.calls] == [0, 0]                                  # outside a driver: exact-f32 kernel, forward and data gradient
     g_ref = x.grad.clone()
     x.grad = None
-    ops.PLANES.managed = True
     try:
-        ops.PLANES.refresh_trainable()
-        with ops.time_linear_calls() as scope:
-            y = HF.linear(x, lin.weight, lin.bias)
-            y.sum().backward()
-        assert all(c[6] for c in scope.calls) and len(scope.calls) == 2
-        torch.testing.assert_close(x.grad, g_ref, rtol=1e-5, atol=1e-4)
-        with torch.no_grad():
-            lin.weight.mul_(0.5)
-        ops.PLANES.refresh_trainable()                                            # what TrainStep does at the start of every step
-        torch.testing.assert_close(HF.linear(x, lin.weight, lin.bias) - lin.bias, 0.5 * (y - lin.bias), rtol=1e-5, atol=5e-6)
+        with HF.managed_weights(transposes=False):
+            with ops.time_linear_calls() as scope:
+                y = HF.linear(x, lin.weight, lin.bias)
+                y.sum().backward()
+            assert all(c[6] for c in scope.calls) and len(scope.calls) == 2
+            torch.testing.assert_close(x.grad, g_ref, rtol=1e-5, atol=1e-4)
+            with torch.no_grad():
+                lin.weight.mul_(0.5)
+            ops.PLANES.refresh_trainable()                                        # what TrainStep does at the start of every step
+            torch.testing.assert_close(HF.linear(x, lin.weight, lin.bias) - lin.bias, 0.5 * (y - lin.bias), rtol=1e-5, atol=5e-6)
     finally:
-        ops.PLANES.managed = False
         ops.PLANES.trainable.clear()
 
 

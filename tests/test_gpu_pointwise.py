@@ -622,9 +622,7 @@ def test_linear_with_an_output_width_that_is_no_multiple_of_4_needs_no_padded_we
     ref = torch.nn.functional.linear(x, w)
     gx_t, gw_t = torch.autograd.grad(ref, (x, w), gy[:, :N])
     buf = torch.full((N * K,), 0.125, device='cuda')
-    was = ops.PLANES.managed, HF.TRANSPOSED.managed
-    ops.PLANES.managed = HF.TRANSPOSED.managed = True
-    try:
+    with HF.managed_weights():
         assert HF.linear_pad_n_usable(x, w)
         warm = torch.zeros(N * K, device='cuda')                          # first use: the persistent plane image and padded W^T are made (one zero-fill)
         with HF.deferred_sums({w.data_ptr(): warm.view(N, K)}):
@@ -635,8 +633,6 @@ def test_linear_with_an_output_width_that_is_no_multiple_of_4_needs_no_padded_we
                 y = HF._LinearPadN.apply(x, w)
                 hx, hw = torch.autograd.grad(y, (x, w), gy, allow_unused=True)
             torch.cuda.synchronize()
-    finally:
-        ops.PLANES.managed, HF.TRANSPOSED.managed = was
     assert tuple(y.shape) == (M, Np) and hw is None and w.data_ptr() in scope.routed
     close(y[:, :N], ref, rtol=1e-5, atol_scale=2e-6)
     assert Np == N or float(y[:, N:].abs().max()) == 0.0
