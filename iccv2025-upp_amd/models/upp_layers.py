@@ -886,13 +886,27 @@ class Block(nn.Module):
         """_propagate_prompts on the row kernels of csrc/prop.hip."""
         B, Lp, D = x.shape
         G2 = kw['center2'].shape[1]
+        bn, sync = self.bnorm, sync_bn_active(self.training)
+        if not sync and not HF.bn_momentum_usable(bn, self.training):
+            # the cumulative average 1 / num_batches_tracked is formed by neither the fused step nor _bn_rows below (outside synchronised
+            # BatchNorm): nn.BatchNorm1d forms it, and counts the batch itself
+            HF.note_declined("Block prompt propagation", "BatchNorm1d with momentum=None (cumulative moving average)")
+            return self._propagate_prompts(x, kw)[0]
         entry, w8, u, keep = self._prop_inputs(x.shape, kw)
-        bn = self.bnorm
-        if bn.affine and (bn.track_running_stats or self.training) and B * Lp <= 15360 and not sync_bn_active(self.training):
+        if HF.propagate_usable(B * Lp, bn, self.training, sync):
             return HF.propagate(x, bn, entry, u, keep, self.training, w8=w8)
         pooled = HF.prop_pool(x, entry.i1, u, keep)
         lc = _bn_rows(pooled, bn, self.training).view(B, G2, D)
         return HF.prop_interp(x, lc, entry.i2, entry.idx8, w8)
+
+    def _adapter_fusable(self, adapter, D):
+        """Do the adapter kernels (csrc/adapter.hip: 384 -> 32 -> GELU -> 384) serve this adapter?"""
+        return D == 384 and adapter.ln1.weight.shape[0] == 32 and isinstance(adapter.activate, nn.GELU)
+
+    def _adapter_drop(self, adapter, rows, device):
+        """(p, uniforms) of the adapter's dropout over `rows` rows of its 32 hidden columns; (0.0, None) where nothing is dropped."""
+        pd = adapter.dropout.p if self.training else 0.0
+        return pd, (UNIFORMS.take((rows, 32), device) if pd > 0 else None)
 
     def fusable(self, x):
         return (x.is_cuda and x.dtype == torch.float32 and x.shape[-1] <= 512 and self.attn.fusable(x)
@@ -946,20 +960,17 @@ class Block(nn.Module):
         if path in _PATHS and kw.get(f'{path}_adapter', False):
             assert adapter is not None, 'No adapter inserted in block!'
         u2 = None if u is None else u[1]
-        tail_fused = (adapter is not None and D == 384 and adapter.ln1.weight.shape[0] == 32 and isinstance(adapter.activate, nn.GELU)
-                      and FUSE_LN_ADAPTER)
+        tail_fused = adapter is not None and self._adapter_fusable(adapter, D) and FUSE_LN_ADAPTER
         if P and kw.get('prompt_propagation_after'):
             prop_fused = (kw['center1_idx'].numel() == B * kw['center2'].shape[1] * 8 and kw['center1'].dtype == torch.float32
                           and POOL_TRACE is None)
             bn = self.bnorm
             if (FUSE_PROP_TAIL and tail_fused and prop_fused and _no_grad_needed(kw['center1'], kw['center2'])
-                    and (bn.track_running_stats or self.training) and not sync_bn_active(self.training)
-                    and HF.prop_tail_usable(x2, bn, kw['center1'].shape[1], P, rem)):
+                    and HF.prop_tail_usable(x2, bn, kw['center1'].shape[1], P, rem, self.training, sync_bn_active(self.training))):
                 # residual + propagation + tail as one node: x3 and the interpolated rows are never stored (HF.prop_tail).  Stage 2 (the
                 # interpolation weights carry a gradient, whose kernel reads x3) and everything else take the launches below.
                 entry, _, ug, keepg = self._prop_inputs(x2.shape, kw)
-                pd = adapter.dropout.p if self.training else 0.0
-                ud = UNIFORMS.take((B * (x2.shape[1] - P), 32), x.device) if pd > 0 else None
+                pd, ud = self._adapter_drop(adapter, B * (x2.shape[1] - P), x.device)
                 return HF.prop_tail(x2, m, mb, u2, keep, rem, P, bn, entry, ug, keepg, self.training, adapter.layer_norm, adapter.ln1.weight,
                                     adapter.ln1.bias, adapter.ln2.weight, adapter.ln2.bias, ud, pd, 0.7)
             x3, _ = HF.rowln(x2, y=m, ybias=mb, u=u2, keep=keep)
@@ -976,15 +987,12 @@ class Block(nn.Module):
         ln = adapter.layer_norm
         if tail_fused:
             # one launch: residual + strip + the adapter's LayerNorm + the adapter (csrc/adapter.hip ln_adapter_fwd_kernel)
-            pd = adapter.dropout.p if self.training else 0.0
-            Lo = x2.shape[1] - (P if rem != HF.ROW_IDENTITY else 0)
-            ud = UNIFORMS.take((B * Lo, 32), x.device) if pd > 0 else None
+            pd, ud = self._adapter_drop(adapter, B * (x2.shape[1] - (P if rem != HF.ROW_IDENTITY else 0)), x.device)
             return HF.ln_adapter(x2, m, mb, u2, keep, rem, P, ln, adapter.ln1.weight, adapter.ln1.bias, adapter.ln2.weight,
                                  adapter.ln2.bias, ud, pd, 0.7)
         x4, ha = HF.rowln(x2, y=m, ybias=mb, u=u2, keep=keep, mode=rem, P=P, gamma=ln.weight, beta=ln.bias, eps=ln.eps)
-        if D == 384 and adapter.ln1.weight.shape[0] == 32 and isinstance(adapter.activate, nn.GELU):
-            pd = adapter.dropout.p if self.training else 0.0
-            ud = UNIFORMS.take((x4.shape[0] * x4.shape[1], 32), x.device) if pd > 0 else None
+        if self._adapter_fusable(adapter, D):
+            pd, ud = self._adapter_drop(adapter, x4.shape[0] * x4.shape[1], x.device)
             return HF.adapter(ha, x4, adapter.ln1.weight, adapter.ln1.bias, adapter.ln2.weight, adapter.ln2.bias, ud, pd, 0.7)
         z = adapter.ln2(adapter.dropout(adapter.activate(adapter.ln1(ha))))
         return torch.add(x4, z, alpha=0.7)

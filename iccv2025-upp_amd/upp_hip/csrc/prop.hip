@@ -1,6 +1,6 @@
 // prop.hip -- the prompt-propagation step of Block.forward
 // (reference models/Point_MAE_pretask_dev.py:275-303, `pooling` per SURVEY D.3, `propagate`
-// models/Point_MAE_unify.py:22-48) as four row kernels for gfx950.
+// models/Point_MAE_unify.py:22-48) as row kernels for gfx950, one wavefront per row.
 //
 // Reference data flow per block (6 blocks per forward), on the token matrix X (B, L', D) whose rows are
 // [cls | P prompts | 64 centre tokens]:
@@ -13,8 +13,13 @@
 // sorts, a full sort of the distances in every block).  Here: idx8 / w8 depend only on the centres and are
 // computed once per forward by the host; the row indices are handed over as absolute rows of X (the host
 // converts the reference's flat / per-sample index conventions, including its stride-64-into-stride-74
-// behaviour, into that form); pool and interpolate are one kernel each, one wavefront per row, and the
-// backward scatter-adds are done as deterministic "scan the index list for my row" gathers, no atomics.
+// behaviour, into that form); no scatter-add uses atomics, so every result is deterministic.
+//
+// Each operation has ONE body (prop_pool_body, prop_interp_row, prop_x_csr_row: device functions inside thin __global__ kernels <name>_kernel),
+// and the entry points launch them as three forms of the same step; the last two share prop_pool_stats_launch / prop_bwd_launch, check included:
+//   unfused pair   upp_prop_pool_fwd: prop_pool_fwd; upp_prop_interp_fwd: prop_interp_fwd   _bwd: prop_pool_bwd; prop_interp_bwd_c2 | prop_interp_bwd_x
+//   fused step     upp_prop_fwd: prop_pool_stats | bn finalize (pointwise.hip) | prop_interp_bn     upp_prop_bwd: prop_c2_csr | prop_bn_grad | prop_x_csr
+//   residual/tail  upp_prop_res_pool_fwd: prop_pool_res_stats | bn finalize (interpolation: adapter.hip)   upp_prop_res_bwd: ... | prop_x_csr_res
 //
 // The row walk of the fused step's backward kernels (prop_c2_csr, prop_x_csr, prop_x_csr_res), as built: a kernel's time is the longest
 // chain of address-dependent loads among its waves (~0.5 us per round), so a CSR row costs four rounds whatever its length --
@@ -45,40 +50,78 @@ constexpr int kMaxE = 8;   // D <= 512
     } while (0)
 constexpr int kNb = 8;     // neighbours per level-2 group and per interpolation (reference: group_size=8, de_neighbors=8)
 
-// pooled[g][c] = max_k v_k + (sum_k v_k) / 8,  v_k = X[i1[g][k]][c] * (1 + s_g);  amax[g][c] = arg max
+__device__ __forceinline__ float res_scale(const float *u_dp, float keep_dp, int b) {
+    return u_dp ? floorf(keep_dp + u_dp[b]) / keep_dp : 1.0f;
+}
+
+// The guarded row store: slot e of a lane is column c = lane + 64 e, live below D (loads clamp their column instead: no branch).
+#define FOR_LIVE_COLS(E, e, c) _Pragma("unroll") for (int e = 0; e < (E); ++e) if (const int c = lane + 64 * e; c < D)
+
+// The pool, one wavefront per level-2 group g = wgx * 4 + wave:
+//   pooled[g][c] = max_k v_k + (sum_k v_k) / 8,  v_k = X[i1[g][k]][c] * (1 + s_g);  amax[g][c] = arg max
+// STATS: the workgroup also emits its BatchNorm column partials, part[(wgx*2+0)*D + c] = sum of its (<= 4) pooled values of column c,
+// part[(wgx*2+1)*D + c] = their M2 about the workgroup mean; sh is its LDS, one row per wave.
+// RES: X is x2 and the gathered row x3[r] = x2[r] + dp_scale(u_dp, r / Lp) * (m[r] + mbias) is formed in place (see prop_pool_res_stats_kernel).
+template <bool STATS, bool RES>
+__device__ __forceinline__ void prop_pool_body(const float *__restrict__ X, const float *__restrict__ m, const float *__restrict__ mbias,
+                                               const float *__restrict__ u_dp, float keep_dp, int Lp, const int32_t *__restrict__ i1,
+                                               const float *__restrict__ u, float keep, float *__restrict__ pooled, uint8_t *__restrict__ amax,
+                                               float *__restrict__ part, float (*sh)[64 * kMaxE], int wgx, int groups, int D) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), g = wgx * 4 + wave;   // wave, g: wave-uniform
+    if (g < groups) {
+        const float f = 1.0f + (u ? floorf(keep + u[g]) / keep : 1.0f);   // x + drop_path(x): factor 1 + s
+        // index loads, then all 8 x kMaxE row loads, then the arithmetic: a dependent global load is ~1 us
+        int rows8[kNb];
+        float sc[kNb], xv[kNb][kMaxE], mv[kNb][kMaxE], mb[kMaxE];
+#pragma unroll
+        for (int k = 0; k < kNb; ++k) rows8[k] = i1[g * kNb + k];
+#pragma unroll
+        for (int k = 0; k < kNb; ++k) sc[k] = RES ? res_scale(u_dp, keep_dp, rows8[k] / Lp) : 1.0f;   // the sample of the gathered row, not of the group
+#pragma unroll
+        for (int k = 0; k < kNb; ++k)
+#pragma unroll
+            for (int e = 0; e < kMaxE; ++e) {
+                const size_t o = (size_t)rows8[k] * D + min(lane + 64 * e, D - 1);   // clamped: no branch
+                xv[k][e] = X[o]; mv[k][e] = RES ? m[o] : 0.0f;
+            }
+#pragma unroll
+        for (int e = 0; e < kMaxE; ++e) mb[e] = RES && mbias ? mbias[min(lane + 64 * e, D - 1)] : 0.0f;
+#pragma unroll
+        for (int e = 0; e < kMaxE; ++e) {
+            float mx = -__builtin_inff(), sm = 0.0f;
+            int am = 0;
+#pragma unroll
+            for (int k = 0; k < kNb; ++k) {
+                const float v = (RES ? __builtin_fmaf(mv[k][e] + mb[e], sc[k], xv[k][e]) : xv[k][e]) * f;
+                if (v > mx) { mx = v; am = k; }   // first maximum wins, as torch.max
+                sm += v;
+            }
+            const int c = lane + 64 * e;
+            const float pv = mx + sm * 0.125f;
+            if (c < D) {
+                pooled[(size_t)g * D + c] = pv; amax[(size_t)g * D + c] = (uint8_t)am;
+                if (STATS) sh[wave][c] = pv;
+            }
+        }
+    }
+    if (!STATS) return;
+    __syncthreads();
+    const int nw = min(4, groups - wgx * 4);
+    for (int c = threadIdx.x; c < D; c += 256) {
+        float sum = 0.0f;
+        for (int w = 0; w < nw; ++w) sum += sh[w][c];
+        const float mean = sum / (float)nw;
+        float m2 = 0.0f;
+        for (int w = 0; w < nw; ++w) { const float dv = sh[w][c] - mean; m2 = __builtin_fmaf(dv, dv, m2); }
+        part[((size_t)wgx * 2 + 0) * D + c] = sum;
+        part[((size_t)wgx * 2 + 1) * D + c] = m2;
+    }
+}
+
 __global__ __launch_bounds__(256) void prop_pool_fwd_kernel(const float *__restrict__ X, const int32_t *__restrict__ i1,
                                                             const float *__restrict__ u, float keep, float *__restrict__ pooled,
                                                             uint8_t *__restrict__ amax, int groups, int D) {
-    const int lane = threadIdx.x & 63;
-    const int g = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
-    if (g >= groups) return;
-    const float f = 1.0f + (u ? floorf(keep + u[g]) / keep : 1.0f);   // x + drop_path(x): factor 1 + s
-    float mx[kMaxE], sm[kMaxE];
-    int am[kMaxE];
-#pragma unroll
-    for (int e = 0; e < kMaxE; ++e) { mx[e] = -__builtin_inff(); sm[e] = 0.0f; am[e] = 0; }
-    // index loads, then all 8 x kMaxE row loads, then the arithmetic: a dependent global load is ~1 us
-    int rows8[kNb];
-#pragma unroll
-    for (int k = 0; k < kNb; ++k) rows8[k] = i1[g * kNb + k];
-    float val[kNb][kMaxE];
-#pragma unroll
-    for (int k = 0; k < kNb; ++k)
-#pragma unroll
-        for (int e = 0; e < kMaxE; ++e) val[k][e] = X[(size_t)rows8[k] * D + min(lane + 64 * e, D - 1)];   // clamped: no branch
-#pragma unroll
-    for (int k = 0; k < kNb; ++k)
-#pragma unroll
-        for (int e = 0; e < kMaxE; ++e) {
-            const float v = val[k][e] * f;
-            if (v > mx[e]) { mx[e] = v; am[e] = k; }   // first maximum wins, as torch.max
-            sm[e] += v;
-        }
-#pragma unroll
-    for (int e = 0; e < kMaxE; ++e) {
-        const int c = lane + 64 * e;
-        if (c < D) { pooled[(size_t)g * D + c] = mx[e] + sm[e] * 0.125f; amax[(size_t)g * D + c] = (uint8_t)am[e]; }
-    }
+    prop_pool_body<false, false>(X, nullptr, nullptr, nullptr, 1.0f, 1, i1, u, keep, pooled, amax, nullptr, nullptr, (int)blockIdx.x, groups, D);
 }
 
 // Positions q in [q0, n) with list[q] == key, appended to hits[] (LDS, per wave) until `cap` could overflow.
@@ -154,18 +197,18 @@ __global__ __launch_bounds__(256) void prop_pool_bwd_kernel(const float *__restr
         }
         __builtin_amdgcn_wave_barrier();
     }
-#pragma unroll
-    for (int e = 0; e < kMaxE; ++e) { const int c = lane + 64 * e; if (c < D) g_X[(size_t)r * D + c] = acc[e]; }
+    FOR_LIVE_COLS(kMaxE, e, c) g_X[(size_t)r * D + c] = acc[e];
 }
 
 // out[b][t] = X[b][t]                                                     for t < L' - T   (cls, prompts)
 //           = X[b][t] + 0.3 * sum_k w8[b][i][k] * (lc[b][j] + 0.3 * X[i2[b][j]]),  j = idx8[b][i][k], i = t - (L' - T)
-__global__ __launch_bounds__(256) void prop_interp_fwd_kernel(const float *__restrict__ X, const float *__restrict__ lc,
-                                                              const int32_t *__restrict__ i2, const int32_t *__restrict__ idx8,
-                                                              const float *__restrict__ w8, float *__restrict__ out, int B, int Lp,
-                                                              int T, int G2, int D) {
+// by the wave that holds row r.  BN: lc holds the PRE-BatchNorm pooled rows and  lc = ((pooled - mean) * rstd) * gamma + beta  is applied on the fly.
+template <bool BN>
+__device__ __forceinline__ void prop_interp_row(const float *__restrict__ X, const float *__restrict__ lc, const float *__restrict__ mean,
+                                                const float *__restrict__ rstd, const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                const int32_t *__restrict__ i2, const int32_t *__restrict__ idx8, const float *__restrict__ w8,
+                                                float *__restrict__ out, int r, int B, int Lp, int T, int G2, int D) {
     const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
     if (r >= B * Lp) return;
     const int b = r / Lp, t = r - b * Lp;
     const int i = t - (Lp - T);
@@ -179,6 +222,11 @@ __global__ __launch_bounds__(256) void prop_interp_fwd_kernel(const float *__res
         float w[kNb];
 #pragma unroll
         for (int k = 0; k < kNb; ++k) { j[k] = idx8[((size_t)b * T + i) * kNb + k]; w[k] = w8[((size_t)b * T + i) * kNb + k]; }
+        float mu[kMaxE], rs[kMaxE], ga[kMaxE], be[kMaxE];
+        if (BN) {
+#pragma unroll
+            for (int e = 0; e < kMaxE; ++e) { mu[e] = mean[cc[e]]; rs[e] = rstd[cc[e]]; ga[e] = gamma[cc[e]]; be[e] = beta[cc[e]]; }
+        }
 #pragma unroll
         for (int k = 0; k < kNb; ++k) cr[k] = i2[b * G2 + j[k]];
 #pragma unroll
@@ -191,15 +239,22 @@ __global__ __launch_bounds__(256) void prop_interp_fwd_kernel(const float *__res
 #pragma unroll
             for (int e = 0; e < 4; ++e)
 #pragma unroll
-                for (int k = 0; k < kNb; ++k) acc[h + e] += (lv[e][k] + 0.3f * cv[e][k]) * w[k];
+                for (int k = 0; k < kNb; ++k) {
+                    const float lcv = BN ? ((lv[e][k] - mu[h + e]) * rs[h + e]) * ga[h + e] + be[h + e] : lv[e][k];
+                    acc[h + e] += (lcv + 0.3f * cv[e][k]) * w[k];
+                }
             if (64 * (h + 4) >= D) break;             // wave-uniform: no live column beyond
         }
     }
-#pragma unroll
-    for (int e = 0; e < kMaxE; ++e) {
-        const int c = lane + 64 * e;
-        if (c < D) out[(size_t)r * D + c] = xv[e] + (i >= 0 ? 0.3f * acc[e] : 0.0f);
-    }
+    FOR_LIVE_COLS(kMaxE, e, c) out[(size_t)r * D + c] = xv[e] + (i >= 0 ? 0.3f * acc[e] : 0.0f);
+}
+
+__global__ __launch_bounds__(256) void prop_interp_fwd_kernel(const float *__restrict__ X, const float *__restrict__ lc,
+                                                              const int32_t *__restrict__ i2, const int32_t *__restrict__ idx8,
+                                                              const float *__restrict__ w8, float *__restrict__ out, int B, int Lp,
+                                                              int T, int G2, int D) {
+    const int r = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
+    prop_interp_row<false>(X, lc, nullptr, nullptr, nullptr, nullptr, i2, idx8, w8, out, r, B, Lp, T, G2, D);
 }
 
 // g_c2[b][j][c] = 0.3 * sum over (i,k) with idx8[b][i][k] == j of w8[b][i][k] * g_out[b][L'-T+i][c]
@@ -257,8 +312,7 @@ __global__ __launch_bounds__(256) void prop_interp_bwd_c2_kernel(const float *__
         }
         __builtin_amdgcn_wave_barrier();
     }
-#pragma unroll
-    for (int e = 0; e < kMaxE; ++e) { const int c = lane + 64 * e; if (c < D) g_c2[(size_t)gj * D + c] = 0.3f * acc[e]; }
+    FOR_LIVE_COLS(kMaxE, e, c) g_c2[(size_t)gj * D + c] = 0.3f * acc[e];
 }
 
 // g_X[r] = g_out[r] + 0.3 * g_c2[m]  for the (unique) m with i2[m] == r, else g_out[r]
@@ -289,8 +343,7 @@ __global__ __launch_bounds__(256) void prop_interp_bwd_x_kernel(const float *__r
             }
         }
     }
-#pragma unroll
-    for (int e = 0; e < kMaxE; ++e) { const int c = lane + 64 * e; if (c < D) g_X[(size_t)r * D + c] = acc[e]; }
+    FOR_LIVE_COLS(kMaxE, e, c) g_X[(size_t)r * D + c] = acc[e];
 }
 
 inline dim3 rows_grid(long long rows) { return dim3((unsigned)((rows + 3) / 4)); }
@@ -402,54 +455,16 @@ __global__ __launch_bounds__(kCsrThreads) void csr_build_kernel(const int32_t *_
     }
 }
 
-// pool forward + BatchNorm column partials.  part[(wg*2+0)*D + c] = sum of the workgroup's (<= 4) pooled values of
-// column c, part[(wg*2+1)*D + c] = their M2 about the workgroup mean.
+// pool forward + BatchNorm column partials (prop_pool_body<STATS>)
 __global__ __launch_bounds__(256) void prop_pool_stats_kernel(const float *__restrict__ X, const int32_t *__restrict__ i1,
                                                               const float *__restrict__ u, float keep, float *__restrict__ pooled,
                                                               uint8_t *__restrict__ amax, float *__restrict__ part, int groups, int D) {
     const int wgx = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);   // XCD x owns a contiguous eighth of the rows / groups (common.h)
     __shared__ float sh[4][64 * kMaxE];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int g = wgx * 4 + wave;
-    if (g < groups) {
-        const float f = 1.0f + (u ? floorf(keep + u[g]) / keep : 1.0f);
-        int rows8[kNb];
-#pragma unroll
-        for (int k = 0; k < kNb; ++k) rows8[k] = i1[g * kNb + k];
-        float val[kNb][kMaxE];
-#pragma unroll
-        for (int k = 0; k < kNb; ++k)
-#pragma unroll
-            for (int e = 0; e < kMaxE; ++e) val[k][e] = X[(size_t)rows8[k] * D + min(lane + 64 * e, D - 1)];
-#pragma unroll
-        for (int e = 0; e < kMaxE; ++e) {
-            float mx = -__builtin_inff(), sm = 0.0f;
-            int am = 0;
-#pragma unroll
-            for (int k = 0; k < kNb; ++k) {
-                const float v = val[k][e] * f;
-                if (v > mx) { mx = v; am = k; }
-                sm += v;
-            }
-            const int c = lane + 64 * e;
-            const float pv = mx + sm * 0.125f;
-            if (c < D) { pooled[(size_t)g * D + c] = pv; amax[(size_t)g * D + c] = (uint8_t)am; sh[wave][c] = pv; }
-        }
-    }
-    __syncthreads();
-    const int nw = min(4, groups - (int)wgx * 4);
-    for (int c = threadIdx.x; c < D; c += 256) {
-        float sum = 0.0f;
-        for (int w = 0; w < nw; ++w) sum += sh[w][c];
-        const float mean = sum / (float)nw;
-        float m2 = 0.0f;
-        for (int w = 0; w < nw; ++w) { const float dv = sh[w][c] - mean; m2 = __builtin_fmaf(dv, dv, m2); }
-        part[((size_t)wgx * 2 + 0) * D + c] = sum;
-        part[((size_t)wgx * 2 + 1) * D + c] = m2;
-    }
+    prop_pool_body<true, false>(X, nullptr, nullptr, nullptr, 1.0f, 1, i1, u, keep, pooled, amax, part, sh, wgx, groups, D);
 }
 
-// interpolate forward reading the PRE-BatchNorm pooled rows: lc = ((pooled - mean) * rstd) * gamma + beta on the fly
+// interpolate forward reading the PRE-BatchNorm pooled rows (prop_interp_row<BN>)
 __global__ __launch_bounds__(256) void prop_interp_bn_fwd_kernel(const float *__restrict__ X, const float *__restrict__ pooled,
                                                                  const float *__restrict__ mean, const float *__restrict__ rstd,
                                                                  const float *__restrict__ gamma, const float *__restrict__ beta,
@@ -457,47 +472,8 @@ __global__ __launch_bounds__(256) void prop_interp_bn_fwd_kernel(const float *__
                                                                  const float *__restrict__ w8, float *__restrict__ out, int B, int Lp,
                                                                  int T, int G2, int D) {
     const int wgx = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);   // XCD x owns a contiguous eighth of the rows / groups (common.h)
-    const int lane = threadIdx.x & 63;
     const int r = wgx * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (r >= B * Lp) return;
-    const int b = r / Lp, t = r - b * Lp;
-    const int i = t - (Lp - T);
-    int cc[kMaxE];
-    float xv[kMaxE], acc[kMaxE];
-#pragma unroll
-    for (int e = 0; e < kMaxE; ++e) { cc[e] = min(lane + 64 * e, D - 1); xv[e] = X[(size_t)r * D + cc[e]]; acc[e] = 0.0f; }
-    if (i >= 0) {
-        int j[kNb], cr[kNb];
-        float w[kNb];
-#pragma unroll
-        for (int k = 0; k < kNb; ++k) { j[k] = idx8[((size_t)b * T + i) * kNb + k]; w[k] = w8[((size_t)b * T + i) * kNb + k]; }
-        float mu[kMaxE], rs[kMaxE], ga[kMaxE], be[kMaxE];
-#pragma unroll
-        for (int e = 0; e < kMaxE; ++e) { mu[e] = mean[cc[e]]; rs[e] = rstd[cc[e]]; ga[e] = gamma[cc[e]]; be[e] = beta[cc[e]]; }
-#pragma unroll
-        for (int k = 0; k < kNb; ++k) cr[k] = i2[b * G2 + j[k]];
-#pragma unroll
-        for (int h = 0; h < kMaxE; h += 4) {
-            float lv[4][kNb], cv[4][kNb];
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int k = 0; k < kNb; ++k) { lv[e][k] = pooled[((size_t)b * G2 + j[k]) * D + cc[h + e]]; cv[e][k] = X[(size_t)cr[k] * D + cc[h + e]]; }
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int k = 0; k < kNb; ++k) {
-                    const float lcv = ((lv[e][k] - mu[h + e]) * rs[h + e]) * ga[h + e] + be[h + e];
-                    acc[h + e] += (lcv + 0.3f * cv[e][k]) * w[k];
-                }
-            if (64 * (h + 4) >= D) break;
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < kMaxE; ++e) {
-        const int c = lane + 64 * e;
-        if (c < D) out[(size_t)r * D + c] = xv[e] + (i >= 0 ? 0.3f * acc[e] : 0.0f);
-    }
+    prop_interp_row<true>(X, pooled, mean, rstd, gamma, beta, i2, idx8, w8, out, r, B, Lp, T, G2, D);
 }
 
 // The backward row kernels walk a CSR row as  start -> entries -> per-entry scalars -> data rows, whatever the row's length: the lanes of
@@ -560,15 +536,11 @@ __global__ __launch_bounds__(256) void prop_c2_csr_kernel(const float *__restric
             for (; b + 2 < nb; b += 2) { load(gb, b + 1); add(ga, b); load(ga, b + 2); add(gb, b + 1); }
             if (b + 1 < nb) { load(gb, b + 1); add(ga, b); add(gb, b + 1); } else add(ga, b);
         }
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const int c = lane + 64 * e;
-            if (c < D) {
-                const float gl = 0.3f * acc[e];
-                g_c2[(size_t)gj * D + c] = gl;
-                sh[0][wave][c] = gl;
-                sh[1][wave][c] = gl * ((pv[e] - mu[e]) * rs[e]);
-            }
+        FOR_LIVE_COLS(E, e, c) {
+            const float gl = 0.3f * acc[e];
+            g_c2[(size_t)gj * D + c] = gl;
+            sh[0][wave][c] = gl;
+            sh[1][wave][c] = gl * ((pv[e] - mu[e]) * rs[e]);
         }
     }
     __syncthreads();
@@ -611,10 +583,6 @@ __global__ __launch_bounds__(256) void prop_bn_grad_kernel(const float *__restri
         g_beta[c] = (sb[0][lane] + sb[1][lane]) + (sb[2][lane] + sb[3][lane]);
         g_gamma[c] = (sg[0][lane] + sg[1][lane]) + (sg[2][lane] + sg[3][lane]);
     }
-}
-
-__device__ __forceinline__ float res_scale(const float *u_dp, float keep_dp, int b) {
-    return u_dp ? floorf(keep_dp + u_dp[b]) / keep_dp : 1.0f;
 }
 
 // The whole g_X of the step, one wavefront per row r of X:
@@ -727,14 +695,7 @@ __device__ __forceinline__ void prop_x_csr_row(const float *__restrict__ g_out, 
 #pragma unroll
         for (int e = 0; e < E; ++e) acc[e] += head[e];
     }
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const int c = lane + 64 * e;
-        if (c < D) {
-            g_X[(size_t)r * D + c] = acc[e];
-            if (RES) g_m[(size_t)r * D + c] = acc[e] * sc;
-        }
-    }
+    FOR_LIVE_COLS(E, e, c) { g_X[(size_t)r * D + c] = acc[e]; if (RES) g_m[(size_t)r * D + c] = acc[e] * sc; }
 }
 
 template <int E>
@@ -755,8 +716,8 @@ __global__ __launch_bounds__(256) void prop_x_csr_kernel(const float *__restrict
 //     x3[r] = x2[r] + dp_scale(u_dp, r / Lp) * (m[r] + mbias)          (rowln_fwd_kernel without a LayerNorm, block.hip)
 // and was written by a launch of its own only to be gathered here.  The two kernels below are prop_pool_stats_kernel and
 // prop_x_csr_kernel with that row formed (forward) / its two gradients written (backward) in place: the same operations in the
-// same order, so every output is bit-identical to the composition with the row kernels.  The forward one is a kernel of its own so that
-// the plain one keeps its code; the backward pair shares prop_x_csr_row above.
+// same order, so every output is bit-identical to the composition with the row kernels.  The forward pair shares prop_pool_body,
+// the backward pair prop_x_csr_row above.
 __global__ __launch_bounds__(256) void prop_pool_res_stats_kernel(const float *__restrict__ x2, const float *__restrict__ m,
                                                                   const float *__restrict__ mbias, const float *__restrict__ u_dp,
                                                                   float keep_dp, int Lp, const int32_t *__restrict__ i1,
@@ -764,66 +725,18 @@ __global__ __launch_bounds__(256) void prop_pool_res_stats_kernel(const float *_
                                                                   uint8_t *__restrict__ amax, float *__restrict__ part, int groups, int D) {
     const int wgx = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);
     __shared__ float sh[4][64 * kMaxE];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int g = wgx * 4 + wave;
-    if (g < groups) {
-        const float f = 1.0f + (u ? floorf(keep + u[g]) / keep : 1.0f);
-        int rows8[kNb];
-        float sc[kNb];
-#pragma unroll
-        for (int k = 0; k < kNb; ++k) rows8[k] = i1[g * kNb + k];
-#pragma unroll
-        for (int k = 0; k < kNb; ++k) sc[k] = res_scale(u_dp, keep_dp, rows8[k] / Lp);   // the sample of the gathered row, not of the group
-        float xv[kNb][kMaxE], mv[kNb][kMaxE], mb[kMaxE];
-#pragma unroll
-        for (int k = 0; k < kNb; ++k)
-#pragma unroll
-            for (int e = 0; e < kMaxE; ++e) {
-                const size_t o = (size_t)rows8[k] * D + min(lane + 64 * e, D - 1);
-                xv[k][e] = x2[o]; mv[k][e] = m[o];
-            }
-#pragma unroll
-        for (int e = 0; e < kMaxE; ++e) mb[e] = mbias ? mbias[min(lane + 64 * e, D - 1)] : 0.0f;
-#pragma unroll
-        for (int e = 0; e < kMaxE; ++e) {
-            float mx = -__builtin_inff(), sm = 0.0f;
-            int am = 0;
-#pragma unroll
-            for (int k = 0; k < kNb; ++k) {
-                const float v = __builtin_fmaf(mv[k][e] + mb[e], sc[k], xv[k][e]) * f;
-                if (v > mx) { mx = v; am = k; }
-                sm += v;
-            }
-            const int c = lane + 64 * e;
-            const float pv = mx + sm * 0.125f;
-            if (c < D) { pooled[(size_t)g * D + c] = pv; amax[(size_t)g * D + c] = (uint8_t)am; sh[wave][c] = pv; }
-        }
-    }
-    __syncthreads();
-    const int nw = min(4, groups - (int)wgx * 4);
-    for (int c = threadIdx.x; c < D; c += 256) {
-        float sum = 0.0f;
-        for (int w = 0; w < nw; ++w) sum += sh[w][c];
-        const float mean = sum / (float)nw;
-        float m2 = 0.0f;
-        for (int w = 0; w < nw; ++w) { const float dv = sh[w][c] - mean; m2 = __builtin_fmaf(dv, dv, m2); }
-        part[((size_t)wgx * 2 + 0) * D + c] = sum;
-        part[((size_t)wgx * 2 + 1) * D + c] = m2;
-    }
+    prop_pool_body<true, true>(x2, m, mbias, u_dp, keep_dp, Lp, i1, u, keep, pooled, amax, part, sh, wgx, groups, D);
 }
 
 // prop_x_csr_kernel writing the gradient of x3 as the two gradients of the residual (prop_x_csr_row<E, true>)
 template <int E>
 __global__ __launch_bounds__(256) void prop_x_csr_res_kernel(const float *__restrict__ g_out, const float *__restrict__ g_c2,
-                                                             const float *__restrict__ pooled, const uint8_t *__restrict__ amax,
-                                                             const float *__restrict__ mean, const float *__restrict__ rstd,
-                                                             const float *__restrict__ gamma, const float *__restrict__ g_gamma,
-                                                             const float *__restrict__ g_beta, const float *__restrict__ u, float keep,
-                                                             const int32_t *__restrict__ start1, const int32_t *__restrict__ perm1,
-                                                             const int32_t *__restrict__ start2, const int32_t *__restrict__ perm2,
-                                                             const float *__restrict__ u_dp, float keep_dp, int Lp,
-                                                             float *__restrict__ g_x2, float *__restrict__ g_m, int rows, int groups, int D,
-                                                             int training) {
+                             const float *__restrict__ pooled, const uint8_t *__restrict__ amax, const float *__restrict__ mean,
+                             const float *__restrict__ rstd, const float *__restrict__ gamma, const float *__restrict__ g_gamma,
+                             const float *__restrict__ g_beta, const float *__restrict__ u, float keep, const int32_t *__restrict__ start1,
+                             const int32_t *__restrict__ perm1, const int32_t *__restrict__ start2, const int32_t *__restrict__ perm2,
+                             const float *__restrict__ u_dp, float keep_dp, int Lp, float *__restrict__ g_x2, float *__restrict__ g_m, int rows,
+                             int groups, int D, int training) {
     prop_x_csr_row<E, true>(g_out, g_c2, pooled, amax, mean, rstd, gamma, g_gamma, g_beta, u, keep, start1, perm1, start2, perm2, u_dp, keep_dp, Lp,
                             g_x2, g_m, rows, groups, D, training);
 }
@@ -1066,7 +979,7 @@ extern "C" int upp_csr_build(const int32_t *keys, int n, int seg_len, int seg_ro
                              void *stream) {
     if (!keys || !start || !perm || n < 1 || rows < 1 || seg_len < 1 || seg_rows < 0) return UPP_E_BADARG;
     const size_t lds = ((size_t)rows + kCsrThreads) * sizeof(int32_t);
-    if (lds > 64 * 1024) return UPP_E_RANGE;    // counts of every row live in LDS (rows <= 15360)
+    if (lds > 64 * 1024) return UPP_E_RANGE;    // counts of every row live in LDS (rows <= 16384 - kCsrThreads: ops.CSR_MAX_ROWS)
     const size_t lds_perm = lds + (size_t)2 * n * sizeof(int32_t);      // + permutation and its row ids
     if (lds_perm <= 150 * 1024) {
         static std::atomic<bool> raised{false};
@@ -1090,57 +1003,74 @@ extern "C" long long upp_prop_part_floats(int groups, int D) {
     return (long long)((groups + 3) / 4) * 2 * D;
 }
 
+// The forward launches of both: pool + column partials (on rows of x3 formed in place when m is given) | BatchNorm finalize (pointwise.hip).
+static int prop_pool_stats_launch(const float *X, const float *m, const float *mbias, const float *u_dp, float keep_dp, int Lp,
+                                  const int32_t *i1, const float *u, float keep, float *running_mean, float *running_var, float momentum,
+                                  float eps, int training, float *pooled, uint8_t *amax, float *part, float *mean, float *rstd, int groups,
+                                  int D, hipStream_t st) {
+    if (!X || !i1 || !pooled || !amax || !part || !mean || !rstd || groups < 1 || D < 1) return UPP_E_BADARG;
+    if (!training && (!running_mean || !running_var)) return UPP_E_BADARG;
+    if (D > 64 * kMaxE) return UPP_E_RANGE;
+    const int wgs = (groups + 3) / 4;
+    if (m)
+        hipLaunchKernelGGL(prop_pool_res_stats_kernel, dim3(wgs), dim3(256), 0, st, X, m, mbias, u_dp, keep_dp, Lp, i1, u, keep, pooled, amax,
+                           part, groups, D);
+    else
+        hipLaunchKernelGGL(prop_pool_stats_kernel, dim3(wgs), dim3(256), 0, st, X, i1, u, keep, pooled, amax, part, groups, D);
+    upp_bn_finalize_launch(part, wgs, 4, groups, D, training, momentum, eps, running_mean, running_var, mean, rstd, st);
+    return upp_launch_status();
+}
+
+// The backward launches of both: c2 + column partials | g_gamma, g_beta | the whole g_X, leaving as (g_x2, g_m) of the residual when g_m is given.
+static int prop_bwd_launch(const float *g_out, const float *pooled, const uint8_t *amax, const float *mean, const float *rstd, const float *gamma,
+                           const float *u, float keep, const float *w8, const int32_t *start1, const int32_t *perm1, const int32_t *start2,
+                           const int32_t *perm2, const int32_t *start8, const int32_t *perm8, int training, const float *u_dp, float keep_dp,
+                           float *g_c2, float *part, float *g_gamma, float *g_beta, float *g_X, float *g_m, int B, int Lp, int T, int G2, int D,
+                           hipStream_t st) {
+    if (!g_out || !pooled || !amax || !mean || !rstd || !gamma || !w8 || !start1 || !perm1 || !start2 || !perm2 || !start8 || !perm8 ||
+        !g_c2 || !part || !g_gamma || !g_beta || !g_X || B < 1 || Lp < T || T < 1 || G2 < 1 || D < 1)
+        return UPP_E_BADARG;
+    if (D > 64 * kMaxE) return UPP_E_RANGE;
+    const int groups = B * G2, wgs = (groups + 3) / 4;
+    PROP_LAUNCH_E(D, prop_c2_csr_kernel, dim3(wgs), dim3(256), 0, st, g_out, start8, perm8, w8, pooled, mean, rstd, g_c2, part, B, Lp, T, G2, D);
+    hipLaunchKernelGGL(prop_bn_grad_kernel, dim3((D + 63) / 64), dim3(256), 0, st, part, wgs, D, g_gamma, g_beta);
+    if (g_m)
+        PROP_LAUNCH_E(D, prop_x_csr_res_kernel, rows_grid((long long)B * Lp), dim3(256), 0, st, g_out, g_c2, pooled, amax, mean, rstd, gamma,
+                           g_gamma, g_beta, u, keep, start1, perm1, start2, perm2, u_dp, keep_dp, Lp, g_X, g_m, B * Lp, groups, D, training);
+    else
+        PROP_LAUNCH_E(D, prop_x_csr_kernel, rows_grid((long long)B * Lp), dim3(256), 0, st, g_out, g_c2, pooled, amax, mean, rstd, gamma,
+                           g_gamma, g_beta, u, keep, start1, perm1, start2, perm2, g_X, B * Lp, groups, D, training);
+    return upp_launch_status();
+}
+
 extern "C" int upp_prop_fwd(const float *X, const int32_t *i1, const float *u, float keep, const int32_t *i2, const int32_t *idx8,
                             const float *w8, const float *gamma, const float *beta, float *running_mean, float *running_var,
                             float momentum, float eps, int training, float *pooled, uint8_t *amax, float *part, float *mean,
                             float *rstd, float *out, int B, int Lp, int T, int G2, int D, void *stream) {
-    if (!X || !i1 || !i2 || !idx8 || !w8 || !gamma || !beta || !pooled || !amax || !part || !mean || !rstd || !out) return UPP_E_BADARG;
-    if (B < 1 || Lp < T || T < 1 || G2 < 1 || D < 1) return UPP_E_BADARG;
-    if (!training && (!running_mean || !running_var)) return UPP_E_BADARG;
-    if (D > 64 * kMaxE) return UPP_E_RANGE;
-    hipStream_t st = (hipStream_t)stream;
-    const int groups = B * G2, wgs = (groups + 3) / 4;
-    hipLaunchKernelGGL(prop_pool_stats_kernel, dim3(wgs), dim3(256), 0, st, X, i1, u, keep, pooled, amax, part, groups, D);
-    upp_bn_finalize_launch(part, wgs, 4, groups, D, training, momentum, eps, running_mean, running_var, mean, rstd, st);
-    hipLaunchKernelGGL(prop_interp_bn_fwd_kernel, rows_grid((long long)B * Lp), dim3(256), 0, st, X, pooled, mean, rstd, gamma, beta, i2,
-                       idx8, w8, out, B, Lp, T, G2, D);
+    if (!i2 || !idx8 || !w8 || !gamma || !beta || !out || B < 1 || Lp < T || T < 1 || G2 < 1) return UPP_E_BADARG;
+    if (int e = prop_pool_stats_launch(X, nullptr, nullptr, nullptr, 1.0f, Lp, i1, u, keep, running_mean, running_var, momentum, eps, training,
+                                       pooled, amax, part, mean, rstd, B * G2, D, (hipStream_t)stream))
+        return e;
+    hipLaunchKernelGGL(prop_interp_bn_fwd_kernel, rows_grid((long long)B * Lp), dim3(256), 0, (hipStream_t)stream, X, pooled, mean, rstd, gamma,
+                       beta, i2, idx8, w8, out, B, Lp, T, G2, D);
     return upp_launch_status();
 }
 
-extern "C" int upp_prop_bwd(const float *g_out, const float *pooled, const uint8_t *amax, const float *mean, const float *rstd,
-                            const float *gamma, const float *u, float keep, const float *w8, const int32_t *start1,
-                            const int32_t *perm1, const int32_t *start2, const int32_t *perm2, const int32_t *start8,
-                            const int32_t *perm8, int training, float *g_c2, float *part, float *g_gamma, float *g_beta, float *g_X,
-                            int B, int Lp, int T, int G2, int D, void *stream) {
-    if (!g_out || !pooled || !amax || !mean || !rstd || !gamma || !w8 || !start1 || !perm1 || !start2 || !perm2 || !start8 || !perm8 ||
-        !g_c2 || !part || !g_gamma || !g_beta || !g_X)
-        return UPP_E_BADARG;
-    if (B < 1 || Lp < T || T < 1 || G2 < 1 || D < 1) return UPP_E_BADARG;
-    if (D > 64 * kMaxE) return UPP_E_RANGE;
-    hipStream_t st = (hipStream_t)stream;
-    const int groups = B * G2, wgs = (groups + 3) / 4;
-    PROP_LAUNCH_E(D, prop_c2_csr_kernel, dim3(wgs), dim3(256), 0, st, g_out, start8, perm8, w8, pooled, mean, rstd, g_c2, part, B, Lp, T,
-                       G2, D);
-    hipLaunchKernelGGL(prop_bn_grad_kernel, dim3((D + 63) / 64), dim3(256), 0, st, part, wgs, D, g_gamma, g_beta);
-    PROP_LAUNCH_E(D, prop_x_csr_kernel, rows_grid((long long)B * Lp), dim3(256), 0, st, g_out, g_c2, pooled, amax, mean, rstd, gamma,
-                       g_gamma, g_beta, u, keep, start1, perm1, start2, perm2, g_X, B * Lp, groups, D, training);
-    return upp_launch_status();
+extern "C" int upp_prop_bwd(const float *g_out, const float *pooled, const uint8_t *amax, const float *mean, const float *rstd, const float *gamma,
+                            const float *u, float keep, const float *w8, const int32_t *start1, const int32_t *perm1, const int32_t *start2,
+                            const int32_t *perm2, const int32_t *start8, const int32_t *perm8, int training, float *g_c2, float *part, float *g_gamma,
+                            float *g_beta, float *g_X, int B, int Lp, int T, int G2, int D, void *stream) {
+    return prop_bwd_launch(g_out, pooled, amax, mean, rstd, gamma, u, keep, w8, start1, perm1, start2, perm2, start8, perm8, training, nullptr,
+                           1.0f, g_c2, part, g_gamma, g_beta, g_X, nullptr, B, Lp, T, G2, D, (hipStream_t)stream);
 }
 
 extern "C" int upp_prop_res_pool_fwd(const float *x2, const float *m, const float *mbias, const float *u_dp, float keep_dp,
                                      const int32_t *i1, const float *u, float keep, float *running_mean, float *running_var,
                                      float momentum, float eps, int training, float *pooled, uint8_t *amax, float *part, float *mean,
                                      float *rstd, int B, int Lp, int G2, int D, void *stream) {
-    if (!x2 || !m || !i1 || !pooled || !amax || !part || !mean || !rstd) return UPP_E_BADARG;
-    if (B < 1 || Lp < 1 || G2 < 1 || D < 1 || !(keep_dp > 0.0f) || !(keep > 0.0f)) return UPP_E_BADARG;
-    if (!training && (!running_mean || !running_var)) return UPP_E_BADARG;
-    if (D > 64 * kMaxE) return UPP_E_RANGE;
-    hipStream_t st = (hipStream_t)stream;
-    const int groups = B * G2, wgs = (groups + 3) / 4;
-    hipLaunchKernelGGL(prop_pool_res_stats_kernel, dim3(wgs), dim3(256), 0, st, x2, m, mbias, u_dp, keep_dp, Lp, i1, u, keep, pooled, amax,
-                       part, groups, D);
-    upp_bn_finalize_launch(part, wgs, 4, groups, D, training, momentum, eps, running_mean, running_var, mean, rstd, st);
-    return upp_launch_status();
+    if (!m || B < 1 || Lp < 1 || G2 < 1 || !(keep_dp > 0.0f) || !(keep > 0.0f)) return UPP_E_BADARG;
+    return prop_pool_stats_launch(x2, m, mbias, u_dp, keep_dp, Lp, i1, u, keep, running_mean, running_var, momentum, eps, training, pooled, amax,
+                                  part, mean, rstd, B * G2, D, (hipStream_t)stream);
 }
 
 extern "C" int upp_prop_res_bwd(const float *g_out, const float *pooled, const uint8_t *amax, const float *mean, const float *rstd,
@@ -1148,19 +1078,9 @@ extern "C" int upp_prop_res_bwd(const float *g_out, const float *pooled, const u
                                 const int32_t *perm1, const int32_t *start2, const int32_t *perm2, const int32_t *start8,
                                 const int32_t *perm8, int training, const float *u_dp, float keep_dp, float *g_c2, float *part,
                                 float *g_gamma, float *g_beta, float *g_x2, float *g_m, int B, int Lp, int T, int G2, int D, void *stream) {
-    if (!g_out || !pooled || !amax || !mean || !rstd || !gamma || !w8 || !start1 || !perm1 || !start2 || !perm2 || !start8 || !perm8 ||
-        !g_c2 || !part || !g_gamma || !g_beta || !g_x2 || !g_m)
-        return UPP_E_BADARG;
-    if (B < 1 || Lp < T || T < 1 || G2 < 1 || D < 1 || !(keep_dp > 0.0f)) return UPP_E_BADARG;
-    if (D > 64 * kMaxE) return UPP_E_RANGE;
-    hipStream_t st = (hipStream_t)stream;
-    const int groups = B * G2, wgs = (groups + 3) / 4;
-    PROP_LAUNCH_E(D, prop_c2_csr_kernel, dim3(wgs), dim3(256), 0, st, g_out, start8, perm8, w8, pooled, mean, rstd, g_c2, part, B, Lp, T,
-                       G2, D);
-    hipLaunchKernelGGL(prop_bn_grad_kernel, dim3((D + 63) / 64), dim3(256), 0, st, part, wgs, D, g_gamma, g_beta);
-    PROP_LAUNCH_E(D, prop_x_csr_res_kernel, rows_grid((long long)B * Lp), dim3(256), 0, st, g_out, g_c2, pooled, amax, mean, rstd, gamma,
-                       g_gamma, g_beta, u, keep, start1, perm1, start2, perm2, u_dp, keep_dp, Lp, g_x2, g_m, B * Lp, groups, D, training);
-    return upp_launch_status();
+    if (!g_m || !(keep_dp > 0.0f)) return UPP_E_BADARG;
+    return prop_bwd_launch(g_out, pooled, amax, mean, rstd, gamma, u, keep, w8, start1, perm1, start2, perm2, start8, perm8, training, u_dp,
+                           keep_dp, g_c2, part, g_gamma, g_beta, g_x2, g_m, B, Lp, T, G2, D, (hipStream_t)stream);
 }
 
 extern "C" int upp_prop_w8_grad(const float *g_out, const float *X, const float *pooled, const float *mean, const float *rstd,

@@ -1784,9 +1784,9 @@ class _Propagate(Function):
 
 def propagate(X, bn, index, u=None, keep=1.0, training=True, w8=None):
     """X (B,L',D) -> X with its last T rows += 0.3 * interp(bn(pool(X)) + 0.3 * X[i2]); bn: nn.BatchNorm1d (affine).
-    w8: the interpolation weights when they carry a gradient (prop_weights), default index.w8 (constants of the forward)."""
-    use_batch = training or bn.running_mean is None
-    momentum = 0.0 if bn.momentum is None else bn.momentum
+    w8: the interpolation weights when they carry a gradient (prop_weights), default index.w8 (constants of the forward).
+    Limits: propagate_usable."""
+    use_batch, momentum = _bn_mode(bn, training)
     return _Propagate.apply(X, bn.weight, bn.bias, index, u, float(keep), bn.running_mean, bn.running_var, momentum, bn.eps, use_batch,
                             index.w8 if w8 is None else w8)
 
@@ -1795,18 +1795,35 @@ def _bn_momentum(bn, use_batch):
     """The momentum of the running-statistics update as the row kernels take it: a number.  momentum=None asks nn.BatchNorm for the
     cumulative average 1 / num_batches_tracked, which these kernels do not form: refused where the statistics would be updated (batch
     statistics with running buffers), irrelevant elsewhere."""
-    if bn.momentum is not None:
-        return float(bn.momentum)
-    if use_batch and bn.running_mean is not None:
+    if not bn_momentum_usable(bn, use_batch):
         raise ValueError("BatchNorm with momentum=None (cumulative moving average) is not served by the row kernels")
-    return 0.0
+    return 0.0 if bn.momentum is None else float(bn.momentum)
+
+
+def bn_momentum_usable(bn, training):
+    """Does _bn_momentum have a number for this layer?  Metadata only.  training: the layer's mode, or _bn_momentum's use_batch (training or
+    no running statistics) -- the same answer, since a layer without running statistics updates none."""
+    return bn.momentum is not None or not training or bn.running_mean is None
+
+
+def _bn_mode(bn, training):
+    """(use_batch, momentum) as the BatchNorm kernels take them: batch statistics in training and wherever there are no running ones; raises
+    ValueError through _bn_momentum, before any device call."""
+    use_batch = training or bn.running_mean is None
+    return use_batch, _bn_momentum(bn, use_batch)
+
+
+def propagate_usable(rows, bn, training, sync_bn=False):
+    """Can the fused step (propagate, prop_tail) serve a token matrix of `rows` rows with this BatchNorm1d?  Metadata only.  An affine
+    layer, statistics it can take (running ones in eval), a momentum the kernels form (_bn_momentum), a row count csr_build takes, and no
+    synchronised BatchNorm (sync_bn: the statistics then span the ranks)."""
+    return bool(bn.affine and (bn.track_running_stats or training) and bn_momentum_usable(bn, training) and rows <= ops.CSR_MAX_ROWS and not sync_bn)
 
 
 # ------------------------------------------------------------------ forward-only row operators (frozen prompter branches)
 def bn_rows(x, bn, training, relu=False):
     """BatchNorm(+ReLU) over the rows of a channels-last (R,C) matrix; no autograd (frozen branches only)."""
-    use_batch = training or bn.running_mean is None
-    momentum = _bn_momentum(bn, use_batch)
+    use_batch, momentum = _bn_mode(bn, training)
     return ops.bn_rows_fwd(x.contiguous(), bn.weight, bn.bias, bn.running_mean, bn.running_var, momentum, bn.eps, use_batch, relu)
 
 
@@ -2245,8 +2262,7 @@ class _BnReluDrop(Function):
 
 def bn_relu_drop(z, bn, u=None, p=0.0, training=True):
     """dropout_p(relu(bn(z))) for a (rows, C) matrix with few rows; u: uniforms (rows, C) when p > 0 in training."""
-    use_batch = training or bn.running_mean is None
-    momentum = _bn_momentum(bn, use_batch)
+    use_batch, momentum = _bn_mode(bn, training)
     return _BnReluDrop.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, momentum, bn.eps, use_batch, u, float(p))
 
 
@@ -2442,9 +2458,8 @@ class _PropTail(Function):
         B, Lin, D = x2.shape
         Lout = Lin - P if mode in (ROW_STRIP_CLS, ROW_STRIP) else Lin
         w8 = index.w8
-        _, pooled, amax, bn_mean, bn_rstd = ops.prop_fwd(x2, index.i1, u_g, keep_g, index.i2, index.idx8, w8, bn_gamma, bn_beta, running_mean,
-                                                         running_var, momentum, bn_eps, training, B, Lin, index.T, index.G2,
-                                                         residual=(m, mb, u_dp, keep_dp))
+        pooled, amax, _, bn_mean, bn_rstd = ops.prop_res_pool_fwd(x2, m, mb, u_dp, keep_dp, index.i1, u_g, keep_g, running_mean, running_var,
+                                                                  momentum, bn_eps, training, index.G2)
         out, xo, mean, rstd, s1 = ops.ln_adapter_prop_fwd(x2, m, mb, u_dp, keep_dp, mode, P, pooled, bn_mean, bn_rstd, bn_gamma, bn_beta, index.i2,
                                                           index.idx8, w8, ln_gamma, ln_beta, ln_eps, W1, b1, W2, b2, ud, pd, scale, Lout)
         ctx.save_for_backward(xo, mean, rstd, ln_gamma, ln_beta, None, s1, W1, W2, ud, pooled, amax, bn_mean, bn_rstd, bn_gamma, u_g, w8, u_dp)
@@ -2469,12 +2484,12 @@ class _PropTail(Function):
                 + (g_gamma, g_beta, None, gW1, gb1, gW2, gb2, None, None, None))
 
 
-def prop_tail_usable(x2, bn, T, P, mode):
-    """Can prop_tail serve this block (T centre rows per cloud, P prompts stripped by `mode`)?  f32 rows of D = 384 (the tail kernel), an
-    affine BatchNorm1d, a row count the CSR build takes, a strip map that keeps every centre row."""
+def prop_tail_usable(x2, bn, T, P, mode, training=True, sync_bn=False):
+    """Can prop_tail serve this block (T centre rows per cloud, P prompts stripped by `mode`)?  f32 rows of D = 384 (the tail kernel), a
+    strip map that keeps every centre row, and what the fused step itself asks (propagate_usable)."""
     B, Lin, D = x2.shape
-    return (x2.is_cuda and x2.dtype == torch.float32 and D == 384 and P > 0 and mode in (ROW_STRIP_CLS, ROW_STRIP) and bn.affine
-            and B * Lin <= 15360 and T <= Lin - P)
+    return (x2.is_cuda and x2.dtype == torch.float32 and D == 384 and P > 0 and mode in (ROW_STRIP_CLS, ROW_STRIP) and T <= Lin - P
+            and propagate_usable(B * Lin, bn, training, sync_bn))
 
 
 def prop_tail(x2, m, mb, u_dp, keep_dp, mode, P, bn, index, u_g, keep_g, training, ln, W1, b1, W2, b2, ud=None, pd=0.0, scale=0.7):
@@ -2483,8 +2498,7 @@ def prop_tail(x2, m, mb, u_dp, keep_dp, mode, P, bn, index, u_g, keep_g, trainin
     to the centres: that is stage 2 of the recipe, which needs the stored rows).  Limits: prop_tail_usable."""
     if mb is not None and torch.is_grad_enabled() and mb.requires_grad:
         raise ValueError("mb is the frozen bias of the Linear that produced m")
-    use_batch = training or bn.running_mean is None
-    momentum = 0.0 if bn.momentum is None else bn.momentum
+    use_batch, momentum = _bn_mode(bn, training)
     return _PropTail.apply(x2, m, mb, u_dp, float(keep_dp), int(mode), int(P), index, u_g, float(keep_g), bn.weight, bn.bias, bn.running_mean,
                            bn.running_var, momentum, bn.eps, use_batch, ln.weight, ln.bias, float(ln.eps), W1, b1, W2, b2, ud, float(pd),
                            float(scale))

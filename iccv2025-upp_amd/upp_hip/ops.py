@@ -1924,6 +1924,9 @@ def prop_interp_bwd(g_out, i2, idx8, w8, B, Lp, T, G2):
     return g_c2, g_X
 
 
+CSR_MAX_ROWS = 15360       # upp_csr_build keeps one counter per row beside its 1024-entry scan in 64 KB of LDS; beyond: UPP_E_RANGE
+
+
 def csr_build(keys, rows, seg_len=None, seg_rows=0):
     """Stable inverse of an int32 index list -> (start (rows+1), perm (n)); see upp_csr_build."""
     _need(keys, "keys", torch.int32)
@@ -1954,23 +1957,38 @@ def prop_index(c1, c2, i1, i2, gather_idx, Lp, off, eps):
     return i1a, i2a, idx8, w8
 
 
-def prop_fwd(X, i1, u, keep, i2, idx8, w8, gamma, beta, running_mean, running_var, momentum, eps, training, B, Lp, T, G2, residual=None):
-    """-> (out, pooled, amax, mean, rstd); upp_prop_fwd.  residual = (m, mbias, u_dp, keep_dp): X is x2 and the step runs on the rows
-    x3 = x2 + dp_scale(u_dp) (m + mbias) without storing them (prop_res_pool_fwd): the first two launches only, out is None -- the
-    interpolation is then the row phase of ln_adapter_prop_fwd."""
-    if residual is not None:
-        m, mbias, u_dp, keep_dp = residual
-        pooled, amax, _, mean, rstd = prop_res_pool_fwd(X, m, mbias, u_dp, keep_dp, i1, u, keep, running_mean, running_var, momentum, eps,
-                                                        training, G2)
-        return None, pooled, amax, mean, rstd
-    D = X.shape[-1]
-    groups = B * G2
-    dev = X.device
-    pooled = torch.empty((groups, D), dtype=torch.float32, device=dev)
-    amax = torch.empty((groups, D), dtype=torch.uint8, device=dev)
-    part = torch.empty(_abi.load().upp_prop_part_floats(groups, D), dtype=torch.float32, device=dev)
-    mean = torch.empty(D, dtype=torch.float32, device=dev)
-    rstd = torch.empty(D, dtype=torch.float32, device=dev)
+def _prop_args(B, Lp, D, rows, cols=(), mbias=None, u=None, groups=None, u_dp=None):
+    """The operand check of the fused step's wrappers, metadata only: rows = (name, tensor) token matrices (B, L', D), cols = per-column
+    vectors (D,), all f32; optional: the frozen bias mbias (D,), the stochastic-depth uniforms u (groups,) per group and u_dp (B,) per sample."""
+    for name, t in rows:
+        _need_f32(t, name, (B, Lp, D))
+    for name, t in cols:
+        _need_f32(t, name, (D,))
+    _need_f32(mbias, "mbias", (D,), optional=True)
+    _need_f32(u, "u", (groups,), optional=True)
+    _need_f32(u_dp, "u_dp", (B,), optional=True)
+    _same_device(*[t for _, t in (*rows, *cols)], *[t for t in (mbias, u, u_dp) if t is not None])
+
+
+def _prop_fwd_outputs(groups, D, dev):
+    """(pooled, amax, part, mean, rstd) of the step's forward."""
+    f32 = dict(dtype=torch.float32, device=dev)
+    return (torch.empty((groups, D), **f32), torch.empty((groups, D), dtype=torch.uint8, device=dev),
+            torch.empty(_abi.load().upp_prop_part_floats(groups, D), **f32), torch.empty(D, **f32), torch.empty(D, **f32))
+
+
+def _prop_bwd_outputs(groups, D, dev):
+    """(g_c2, part, g_gamma, g_beta) of the step's backward."""
+    f32 = dict(dtype=torch.float32, device=dev)
+    return (torch.empty((groups, D), **f32), torch.empty(_abi.load().upp_prop_part_floats(groups, D), **f32), torch.empty(D, **f32),
+            torch.empty(D, **f32))
+
+
+def prop_fwd(X, i1, u, keep, i2, idx8, w8, gamma, beta, running_mean, running_var, momentum, eps, training, B, Lp, T, G2):
+    """-> (out, pooled, amax, mean, rstd); upp_prop_fwd."""
+    D, dev = X.shape[-1], X.device
+    _prop_args(B, Lp, D, (("X", X),), (("gamma", gamma), ("beta", beta)), u=u, groups=B * G2)
+    pooled, amax, part, mean, rstd = _prop_fwd_outputs(B * G2, D, dev)
     out = torch.empty_like(X)
     _call(dev, "upp_prop_fwd", _abi.ptr(X), _abi.ptr(i1), _abi.ptr(u), float(keep), _abi.ptr(i2), _abi.ptr(idx8), _abi.ptr(w8),
           _abi.ptr(gamma), _abi.ptr(beta), _abi.ptr(running_mean), _abi.ptr(running_var), float(momentum), float(eps), int(bool(training)),
@@ -1979,13 +1997,10 @@ def prop_fwd(X, i1, u, keep, i2, idx8, w8, gamma, beta, running_mean, running_va
 
 
 def prop_bwd(g_out, pooled, amax, mean, rstd, gamma, u, keep, w8, csr1, csr2, csr8, training, B, Lp, T, G2):
-    D = g_out.shape[-1]
-    groups = B * G2
-    dev = g_out.device
-    g_c2 = torch.empty((groups, D), dtype=torch.float32, device=dev)
-    part = torch.empty(_abi.load().upp_prop_part_floats(groups, D), dtype=torch.float32, device=dev)
-    g_gamma = torch.empty(D, dtype=torch.float32, device=dev)
-    g_beta = torch.empty(D, dtype=torch.float32, device=dev)
+    """-> (g_X, g_gamma, g_beta); upp_prop_bwd."""
+    D, dev = g_out.shape[-1], g_out.device
+    _prop_args(B, Lp, D, (("g_out", g_out),), (("mean", mean), ("rstd", rstd), ("gamma", gamma)), u=u, groups=B * G2)
+    g_c2, part, g_gamma, g_beta = _prop_bwd_outputs(B * G2, D, dev)
     g_X = torch.empty_like(g_out)
     _call(dev, "upp_prop_bwd", _abi.ptr(g_out), _abi.ptr(pooled), _abi.ptr(amax), _abi.ptr(mean), _abi.ptr(rstd), _abi.ptr(gamma), _abi.ptr(u),
           float(keep), _abi.ptr(w8), _abi.ptr(csr1[0]), _abi.ptr(csr1[1]), _abi.ptr(csr2[0]), _abi.ptr(csr2[1]), _abi.ptr(csr8[0]),
@@ -1994,32 +2009,17 @@ def prop_bwd(g_out, pooled, amax, mean, rstd, gamma, u, keep, w8, csr1, csr2, cs
     return g_X, g_gamma, g_beta
 
 
-def _prop_res_args(x2, m, mbias, u_dp, B, Lp, D):
-    _need_f32(x2, "x2", (B, Lp, D))
-    _need_f32(m, "m", (B, Lp, D))
-    _need_f32(mbias, "mbias", (D,), optional=True)
-    _need_f32(u_dp, "u_dp", (B,), optional=True)
-    _same_device(*[t for t in (x2, m, mbias, u_dp) if t is not None])
-
-
 def prop_res_pool_fwd(x2, m, mbias, u_dp, keep_dp, i1, u, keep, running_mean, running_var, momentum, eps, training, G2):
     """The pool + statistics + finalize launches of prop_fwd on the rows x3 = x2 + dp_scale(u_dp) (m + mbias), formed where they are gathered
     -> (pooled, amax, part, mean, rstd); upp_prop_res_pool_fwd."""
     _need(x2, "x2", torch.float32, ndim=3)
     B, Lp, D = x2.shape
-    _prop_res_args(x2, m, mbias, u_dp, B, Lp, D)
-    groups = B * G2
+    _prop_args(B, Lp, D, (("x2", x2), ("m", m)), mbias=mbias, u=u, groups=B * G2, u_dp=u_dp)
     _need(i1, "i1", torch.int32)
-    if i1.numel() != groups * 8:
+    if i1.numel() != B * G2 * 8:
         raise RuntimeError("prop_res_pool_fwd: i1 must hold 8 rows for each of the B * G2 groups")
-    _need_f32(u, "u", (groups,), optional=True)
-    dev = x2.device
-    pooled = torch.empty((groups, D), dtype=torch.float32, device=dev)
-    amax = torch.empty((groups, D), dtype=torch.uint8, device=dev)
-    part = torch.empty(_abi.load().upp_prop_part_floats(groups, D), dtype=torch.float32, device=dev)
-    mean = torch.empty(D, dtype=torch.float32, device=dev)
-    rstd = torch.empty(D, dtype=torch.float32, device=dev)
-    _call(dev, "upp_prop_res_pool_fwd", _abi.ptr(x2), _abi.ptr(m), _abi.ptr(mbias), _abi.ptr(u_dp), float(keep_dp), _abi.ptr(i1), _abi.ptr(u),
+    pooled, amax, part, mean, rstd = _prop_fwd_outputs(B * G2, D, x2.device)
+    _call(x2.device, "upp_prop_res_pool_fwd", _abi.ptr(x2), _abi.ptr(m), _abi.ptr(mbias), _abi.ptr(u_dp), float(keep_dp), _abi.ptr(i1), _abi.ptr(u),
           float(keep), _abi.ptr(running_mean), _abi.ptr(running_var), float(momentum), float(eps), int(bool(training)), _abi.ptr(pooled),
           _abi.ptr(amax), _abi.ptr(part), _abi.ptr(mean), _abi.ptr(rstd), B, Lp, int(G2), D)
     return pooled, amax, part, mean, rstd
@@ -2027,17 +2027,10 @@ def prop_res_pool_fwd(x2, m, mbias, u_dp, keep_dp, i1, u, keep, running_mean, ru
 
 def prop_res_bwd(g_out, pooled, amax, mean, rstd, gamma, u, keep, w8, csr1, csr2, csr8, training, u_dp, keep_dp, B, Lp, T, G2):
     """prop_bwd with the gradient of x3 leaving as the residual's two gradients -> (g_x2, g_m, g_gamma, g_beta); upp_prop_res_bwd."""
-    D = g_out.shape[-1]
-    _need_f32(g_out, "g_out", (B, Lp, D))
-    _need_f32(u_dp, "u_dp", (B,), optional=True)
-    groups = B * G2
-    dev = g_out.device
-    g_c2 = torch.empty((groups, D), dtype=torch.float32, device=dev)
-    part = torch.empty(_abi.load().upp_prop_part_floats(groups, D), dtype=torch.float32, device=dev)
-    g_gamma = torch.empty(D, dtype=torch.float32, device=dev)
-    g_beta = torch.empty(D, dtype=torch.float32, device=dev)
-    g_x2 = torch.empty_like(g_out)
-    g_m = torch.empty_like(g_out)
+    D, dev = g_out.shape[-1], g_out.device
+    _prop_args(B, Lp, D, (("g_out", g_out),), (("mean", mean), ("rstd", rstd), ("gamma", gamma)), u=u, groups=B * G2, u_dp=u_dp)
+    g_c2, part, g_gamma, g_beta = _prop_bwd_outputs(B * G2, D, dev)
+    g_x2, g_m = torch.empty_like(g_out), torch.empty_like(g_out)
     _call(dev, "upp_prop_res_bwd", _abi.ptr(g_out), _abi.ptr(pooled), _abi.ptr(amax), _abi.ptr(mean), _abi.ptr(rstd), _abi.ptr(gamma),
           _abi.ptr(u), float(keep), _abi.ptr(w8), _abi.ptr(csr1[0]), _abi.ptr(csr1[1]), _abi.ptr(csr2[0]), _abi.ptr(csr2[1]),
           _abi.ptr(csr8[0]), _abi.ptr(csr8[1]), int(bool(training)), _abi.ptr(u_dp), float(keep_dp), _abi.ptr(g_c2), _abi.ptr(part),
@@ -2714,7 +2707,7 @@ def ln_adapter_prop_fwd(x2, m, mbias, u_dp, keep_dp, mode, P, pooled, bn_mean, b
     B, Lin, D = x2.shape
     H = W1.shape[0]
     dev = x2.device
-    _prop_res_args(x2, m, mbias, u_dp, B, Lin, D)
+    _prop_args(B, Lin, D, (("x2", x2), ("m", m)), mbias=mbias, u_dp=u_dp)
     for t_, n_, shp in ((gamma, "gamma", (D,)), (beta, "beta", (D,)), (W1, "W1", (H, D)), (b1, "b1", (H,)), (W2, "W2", (D, H)), (b2, "b2", (D,)),
                         (bn_mean, "bn_mean", (D,)), (bn_rstd, "bn_rstd", (D,)), (bn_gamma, "bn_gamma", (D,)), (bn_beta, "bn_beta", (D,))):
         _need_f32(t_, n_, shp)

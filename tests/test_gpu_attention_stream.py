@@ -242,12 +242,14 @@ def test_a_192_group_model_trains_on_the_fused_path(monkeypatch):
         return loss.item(), {n: p.grad.clone() for n, p in m.named_parameters() if p.requires_grad and p.grad is not None}
 
     choices, flipped = [], []
-    prop_fwd, group_max_fwd = ops.prop_fwd, ops.group_max_fwd
+    group_max_fwd = ops.group_max_fwd
 
-    def recording_prop_fwd(*a, **k):
-        out = prop_fwd(*a, **k)
-        choices.append(out[2].clone())                  # arg-max (B * G2, D) of the fused propagation's pool
-        return out
+    def recording(fwd, amax_at):
+        def wrapped(*a, **k):
+            out = fwd(*a, **k)
+            choices.append(out[amax_at].clone())        # arg-max (B * G2, D) of the fused propagation's pool
+            return out
+        return wrapped
 
     def replaying_group_max_fwd(xg, *a, **k):
         out, amax = group_max_fwd(xg, *a, **k)
@@ -258,10 +260,11 @@ def test_a_192_group_model_trains_on_the_fused_path(monkeypatch):
         return out, amax
 
     HF._declined.clear()
-    monkeypatch.setattr(ops, "prop_fwd", recording_prop_fwd)
-    loss, grads = step()
+    with monkeypatch.context() as mp:                   # the pool of the fused step, and of its residual / tail form
+        mp.setattr(ops, "prop_fwd", recording(ops.prop_fwd, 2))
+        mp.setattr(ops, "prop_res_pool_fwd", recording(ops.prop_res_pool_fwd, 1))
+        loss, grads = step()
     declined = set(HF._declined)
-    monkeypatch.setattr(ops, "prop_fwd", prop_fwd)
     assert len(choices) == 6                           # the six prompted blocks
     per_pool = choices[0].numel()
     _no_fused_paths(monkeypatch)
