@@ -26,21 +26,9 @@ class get_loss(nn.Module):
         return F.nll_loss(pred, target)
 
 
-@MODELS.register_module()
-class Point_MAE_unify_seg(PromptedBackbone):
-    def __init__(self, config):
-        super().__init__()
-        D = self._build_backbone(config)
-        self.label_conv = nn.Sequential(nn.Conv1d(16, 64, kernel_size=1, bias=True), nn.BatchNorm1d(64), nn.LeakyReLU(0.2),
-                                        nn.Conv1d(64, 128, kernel_size=1, bias=True), nn.BatchNorm1d(128), nn.LeakyReLU(0.2))
-        self.positional_embedding = PositionalEmbedding(12)
-        self.propagation_0 = PointNetFeaturePropagation(in_channel=D * 3 + 3, mlp=[D * 4, 1024], interpolate_neighbors=3)
-        self.group_divider1 = Group(num_group=self.num_group * 4, group_size=self.group_size // 2)
-        self.seg_head = nn.Sequential(
-            nn.Conv1d(1024 + 128 + D * 6, 512, 1), nn.BatchNorm1d(512), nn.ReLU(), nn.Dropout(0.5),
-            nn.Conv1d(512, 256, 1), nn.BatchNorm1d(256), nn.ReLU(),
-            nn.Conv1d(256, self.cls_dim, 1))
-        self.get_loss = get_loss()
+class SegTail:
+    """What the segmentation models share behind their backbones (Point_MAE_unify_seg here, PointTransformer_seg in
+    models/Point_MAE_segment.py): the label branch and the per-point head, over the members `label_conv` and `seg_head`."""
 
     def _label_feature(self, cls_label):
         """label_conv on the (B,16) one-hot object class -> (B,128); BatchNorm over the batch."""
@@ -75,6 +63,23 @@ class Point_MAE_unify_seg(PromptedBackbone):
             return HF.log_softmax_rows(ypad, c3.bias, w3.shape[0]).view(B, N, -1)
         h = HF.linear(h, w3, c3.bias)
         return F.log_softmax(h, dim=-1).view(B, N, -1)
+
+
+@MODELS.register_module()
+class Point_MAE_unify_seg(PromptedBackbone, SegTail):
+    def __init__(self, config):
+        super().__init__()
+        D = self._build_backbone(config)
+        self.label_conv = nn.Sequential(nn.Conv1d(16, 64, kernel_size=1, bias=True), nn.BatchNorm1d(64), nn.LeakyReLU(0.2),
+                                        nn.Conv1d(64, 128, kernel_size=1, bias=True), nn.BatchNorm1d(128), nn.LeakyReLU(0.2))
+        self.positional_embedding = PositionalEmbedding(12)
+        self.propagation_0 = PointNetFeaturePropagation(in_channel=D * 3 + 3, mlp=[D * 4, 1024], interpolate_neighbors=3)
+        self.group_divider1 = Group(num_group=self.num_group * 4, group_size=self.group_size // 2)
+        self.seg_head = nn.Sequential(
+            nn.Conv1d(1024 + 128 + D * 6, 512, 1), nn.BatchNorm1d(512), nn.ReLU(), nn.Dropout(0.5),
+            nn.Conv1d(512, 256, 1), nn.BatchNorm1d(256), nn.ReLU(),
+            nn.Conv1d(256, self.cls_dim, 1))
+        self.get_loss = get_loss()
 
     def forward(self, pts, cls_label, label_points=None, completion_prompt=True, denoise=True, point_num=1024, **kwargs):
         L.begin_forward(pts.device, self.training)

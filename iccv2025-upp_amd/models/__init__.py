@@ -5,3 +5,5 @@ from . import Point_MAE_unify_segment  # noqa: F401,E402  (registers Point_MAE_u
 from . import Point_MAE  # noqa: F401,E402  (registers Point_MAE)
 from . import Point_MAE_pretask_dev  # noqa: F401,E402  (registers Point_MAE_pretask_dev)
 from . import PoinTr  # noqa: F401,E402  (registers PoinTr)
+from . import Point_MAE_finetune  # noqa: F401,E402  (registers PointTransformer)
+from . import Point_MAE_segment  # noqa: F401,E402  (registers PointTransformer_seg)

@@ -1199,6 +1199,10 @@ class PointNetFeaturePropagation(nn.Module):
     # at the 1e-7 level (the sum over k and the product with W are re-associated).
     commute_first_layer = True
 
+    def _add_first_columns(self, y, p1, w1):
+        """y + p1 . w1^T: the concat's first C1 columns as a separate small-K product (forward, data and weight gradient on our kernels)"""
+        return y + HF.linear(p1, w1) if y.is_cuda else torch.addmm(y, p1, w1.t())
+
     def _forward_commuted(self, xyz1, xyz2, points1, points2):
         B, N = xyz1.shape[0], xyz1.shape[1]
         conv, bn = self.mlp_convs[0], self.mlp_bns[0]
@@ -1214,8 +1218,7 @@ class PointNetFeaturePropagation(nn.Module):
         else:
             y = _inverse_distance_interp(xyz1, xyz2, z, k, 1e-4).reshape(B * N, -1)
             if C1:
-                # (the concat's first C1 columns as a separate small-K product: forward, data and weight gradient on our kernels)
-                y = y + HF.linear(points1.reshape(B * N, C1), w[:, :C1]) if y.is_cuda else torch.addmm(y, points1.reshape(B * N, C1), w[:, :C1].t())
+                y = self._add_first_columns(y, points1.reshape(B * N, C1), w[:, :C1])
         if self.training and bn.track_running_stats:
             bump_counter(bn.num_batches_tracked)
         x = _bn_rows(y, bn, self.training, relu=True)

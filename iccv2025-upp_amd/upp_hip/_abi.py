@@ -103,6 +103,10 @@ SIGNATURES = {
     "upp_batched_sum": (_c_i, [ctypes.POINTER(ctypes.c_void_p)] * 2 + [ctypes.POINTER(ctypes.c_int)] * 6 + [_c_i, _c_f]),
     "upp_cls_pool_fwd": (_c_i, [_c_f] * 3 + [ctypes.c_float] + [_c_f] * 4 + [_c_i] * 3 + [_c_f]),
     "upp_cls_pool_bwd": (_c_i, [_c_f] * 7 + [_c_i] * 3 + [_c_f]),
+    "upp_cls_pool_bwd_ln": (_c_i, [_c_f] * 9 + [_c_i] * 3 + [_c_f]),
+    "upp_tap_pool_fwd": (_c_i, [_c_f] * 5 + [ctypes.c_float] + [_c_f] * 6 + [_c_i] * 3 + [_c_f]),
+    "upp_tap_pool_part_floats": (ctypes.c_longlong, [_c_i] * 3),
+    "upp_tap_pool_bwd": (_c_i, [_c_f] * 16 + [_c_i] * 3 + [_c_f]),
     "upp_ce_acc": (_c_i, [_c_f] * 4 + [_c_i] * 2 + [_c_f]),
     "upp_logsoftmax_rows_fwd": (_c_i, [_c_f, ctypes.c_longlong, _c_f, ctypes.c_longlong, _c_i, _c_f, _c_f]),
     "upp_logsoftmax_rows_bwd": (_c_i, [_c_f, _c_f, ctypes.c_longlong, _c_i, _c_f, ctypes.c_longlong, _c_i, _c_f]),

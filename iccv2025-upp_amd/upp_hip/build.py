@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libupp_hip.so")
-SOURCES = ["abi.hip", "fps.hip", "ragged.hip", "knn.hip", "knn_points.hip", "edge_conv.hip", "expand.hip", "query_select.hip", "deform_attn.hip", "interp_max.hip", "region_attn.hip", "group.hip", "pointnet2.hip", "chamfer.hip", "emd.hip", "dense.hip", "linear.hip", "linear_sb.hip", "linear_rt.hip", "wgrad_sb.hip", "smallk.hip", "block.hip", "prop.hip", "optim.hip", "attn_flash16.hip", "attn_long.hip", "attn_stream.hip", "adapter.hip", "pointwise.hip", "head.hip", "eval.hip", "seg_eval.hip", "completion_eval.hip"]
+SOURCES = ["abi.hip", "fps.hip", "ragged.hip", "knn.hip", "knn_points.hip", "edge_conv.hip", "expand.hip", "query_select.hip", "deform_attn.hip", "interp_max.hip", "region_attn.hip", "group.hip", "pointnet2.hip", "chamfer.hip", "emd.hip", "dense.hip", "linear.hip", "linear_sb.hip", "linear_rt.hip", "wgrad_sb.hip", "smallk.hip", "block.hip", "prop.hip", "optim.hip", "attn_flash16.hip", "attn_long.hip", "attn_stream.hip", "adapter.hip", "pointwise.hip", "head.hip", "norm_pool.hip", "eval.hip", "seg_eval.hip", "completion_eval.hip"]
 # -ffp-contract=off: every fma in the kernels is written explicitly so that the
 # arithmetic matches the oracle bit for bit (see csrc/common.h sumsq3()).
 # -target-feature -packed-fp32-ops: no v_pk_add/mul/fma_f32 in any kernel.  Measured on MI355X (tools/micro/src/lds_canary.cpp, round 4):

@@ -18,10 +18,11 @@
 //    the saved log-sum-exp and accumulates dK / dV in registers (lane = channel).
 // All arithmetic f32 (parity bar 1e-5 rel against the reference's unfused ops).
 #include "common.h"
+#include "rowln_core.h"
 
 namespace {
 
-constexpr int kMaxE = 8;  // elements per lane in a row kernel -> D <= 512
+constexpr int kMaxE = kRowE;  // elements per lane in a row kernel -> D <= 512
 
 __device__ __forceinline__ float wave_sum(float v) { return wave_sum_f32(v); }
 
@@ -105,29 +106,24 @@ __global__ __launch_bounds__(256) void rowln_fwd_kernel(RowLnArgs a) {
     }
     const float sc = has_y ? dp_scale(a.u, a.keep, b) : 0.0f;
     float v[kMaxE];
-    float s = 0.0f;
 #pragma unroll
     for (int e = 0; e < kMaxE; ++e) {
         float val = xv[e];
         if (has_ad) val += av[e];
         if (has_y) val = __builtin_fmaf(yv[e], sc, val);
         v[e] = lane + 64 * e < D ? val : 0.0f;
-        s += v[e];
     }
     if (a.xo) {
 #pragma unroll
         for (int e = 0; e < kMaxE; ++e) { const int c = lane + 64 * e; if (c < D) a.xo[(size_t)row * D + c] = v[e]; }
     }
     if (!has_ln) return;
-    const float mean = wave_sum(s) / (float)D;
-    float q = 0.0f;
-#pragma unroll
-    for (int e = 0; e < kMaxE; ++e) { const int c = lane + 64 * e; const float dv = c < D ? v[e] - mean : 0.0f; q = __builtin_fmaf(dv, dv, q); }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + a.eps);
+    float mean, rstd;
+    rowln_stats(v, lane, D, a.eps, mean, rstd);
 #pragma unroll
     for (int e = 0; e < kMaxE; ++e) {
         const int c = lane + 64 * e;
-        if (c < D) a.h[(size_t)row * D + c] = __builtin_fmaf((v[e] - mean) * rstd, gv[e], bv[e]);
+        if (c < D) a.h[(size_t)row * D + c] = rowln_affine(v[e], mean, rstd, gv[e], bv[e]);
     }
     if (lane == 0) { a.mean[row] = mean; a.rstd[row] = rstd; }
 }
@@ -215,22 +211,15 @@ __global__ __launch_bounds__(256) void rowln_bwd_kernel(RowLnBwdArgs a) {
 #pragma unroll
         for (int e = 0; e < kMaxE; ++e) d[e] = (has_gxo && lane + 64 * e < D) ? d[e] : 0.0f;
         if (has_ln) {
-            // dx = rstd * (dy - mean(dy) - xhat * mean(dy * xhat)),  dy = g_h * gamma
-            float dy[kMaxE], xh[kMaxE], s1 = 0.0f, s2 = 0.0f;
+            float dx[kMaxE], xh[kMaxE];
+            rowln_bwd_row(gh, gm, xo, mean, rstd, lane, D, dx, xh);      // (rowln_core.h)
 #pragma unroll
             for (int e = 0; e < kMaxE; ++e) {
                 const bool ok = lane + 64 * e < D;
-                dy[e] = ok ? gh[e] * gm[e] : 0.0f;
-                xh[e] = ok ? (xo[e] - mean) * rstd : 0.0f;
                 pgam[e] = ok ? gh[e] * xh[e] : 0.0f;
                 pbet[e] = ok ? gh[e] : 0.0f;
-                s1 += dy[e];
-                s2 = __builtin_fmaf(dy[e], xh[e], s2);
+                d[e] += dx[e];
             }
-            s1 = wave_sum(s1) / (float)D;
-            s2 = wave_sum(s2) / (float)D;
-#pragma unroll
-            for (int e = 0; e < kMaxE; ++e) d[e] += rstd * (dy[e] - s1 - xh[e] * s2);
         }
 #pragma unroll
         for (int e = 0; e < kMaxE; ++e) {

@@ -2216,9 +2216,80 @@ class _ClsPool(Function):
         return ops.cls_pool_bwd(g_feat.contiguous(), x, mean, rstd, gamma, amax), None, None, None
 
 
+class _ClsPoolLN(Function):
+    """_ClsPool for a LayerNorm that trains: the same forward, the same g_x (upp_cls_pool_bwd's kernel) and g_gamma / g_beta from the
+    rows that carry a gradient (upp_cls_pool_bwd_ln)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps):
+        x = x.contiguous()
+        feat, amax, mean, rstd = ops.cls_pool_fwd(x, gamma, beta, eps)
+        ctx.save_for_backward(x, mean, rstd, gamma, amax)
+        return feat
+
+    @staticmethod
+    def backward(ctx, g_feat):
+        x, mean, rstd, gamma, amax = ctx.saved_tensors
+        g_x, g_gamma, g_beta = ops.cls_pool_bwd_ln(g_feat.contiguous(), x, mean, rstd, gamma, amax)
+        need = ctx.needs_input_grad
+        return g_x if need[0] else None, g_gamma if need[1] else None, g_beta if need[2] else None, None
+
+
 def cls_pool(x, norm):
-    """torch.cat([norm(x)[:, 0], norm(x)[:, 1:].max(1)[0]], -1) for a frozen nn.LayerNorm `norm`."""
+    """torch.cat([norm(x)[:, 0], norm(x)[:, 1:].max(1)[0]], -1) for an nn.LayerNorm `norm`: the node of the frozen LayerNorm (and its
+    bits) when neither parameter needs a gradient, the node with the parameter gradients otherwise."""
+    if torch.is_grad_enabled() and (norm.weight.requires_grad or norm.bias.requires_grad):
+        return _ClsPoolLN.apply(x, norm.weight, norm.bias, float(norm.eps))
     return _ClsPool.apply(x, norm.weight, norm.bias, float(norm.eps))
+
+
+# ------------------------------------------------------------------ LayerNorm of three feature taps + token pooling (csrc/norm_pool.hip)
+class _TapPool(Function):
+    """(x, gmax, gmean) of include/upp_hip.h upp_tap_pool_fwd: one launch forward, two backward (upp_tap_pool_bwd)."""
+
+    @staticmethod
+    def forward(ctx, f0, f1, f2, gamma, beta, eps):
+        f0, f1, f2 = f0.contiguous(), f1.contiguous(), f2.contiguous()
+        x, gmax, arg, gmean, mean, rstd = ops.tap_pool_fwd(f0, f1, f2, gamma, beta, eps)
+        ctx.save_for_backward(f0, f1, f2, mean, rstd, gamma, arg)
+        return x, gmax, gmean
+
+    @staticmethod
+    def backward(ctx, d_x, d_gmax, d_gmean):
+        f0, f1, f2, mean, rstd, gamma, arg = ctx.saved_tensors
+        d0, d1, d2, d_gamma, d_beta = ops.tap_pool_bwd(d_x.contiguous(), d_gmax.contiguous(), d_gmean.contiguous(), f0, f1, f2, mean, rstd,
+                                                       gamma, arg)
+        need = ctx.needs_input_grad
+        return (d0 if need[0] else None, d1 if need[1] else None, d2 if need[2] else None, d_gamma if need[3] else None,
+                d_beta if need[4] else None, None)
+
+
+def tap_pool_usable(f0, f1, f2, norm):
+    """The served range of upp_tap_pool_fwd / bwd: three f32 HIP (B,G,C) tensors of one shape, 1 <= B <= 65535, 1 <= G <= 2048 (UPP_ATTN_MAX_L),
+    C % 4 == 0, 4 <= C <= 512, and an affine nn.LayerNorm(C) with f32 parameters on the same device."""
+    ts = (f0, f1, f2)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 for t in ts):
+        return False
+    if not (f0.shape == f1.shape == f2.shape and f0.device == f1.device == f2.device):
+        return False
+    B, G, C = f0.shape
+    if not (isinstance(norm, torch.nn.LayerNorm) and tuple(norm.normalized_shape) == (C,) and norm.elementwise_affine and norm.bias is not None
+            and norm.weight.dtype == torch.float32 and norm.weight.device == f0.device):
+        return False
+    return 1 <= B <= 65535 and 1 <= G <= 2048 and C % 4 == 0 and 4 <= C <= 512
+
+
+def tap_pool(f0, f1, f2, norm):
+    """-> (x (B,G,3C) = [norm(f0) | norm(f1) | norm(f2)], gmax (B,3C) = x.max(1)[0], gmean (B,3C) = the mean over the tokens summed in
+    token order) for one shared nn.LayerNorm `norm` (reference models/Point_MAE_segment.py:413-424).  HIP tensors of the served range
+    (tap_pool_usable) take the kernels; a HIP tensor outside it is recorded by note_declined and, like a CPU tensor, takes the torch
+    formulation upp_hip.torch_cpu.tap_pool."""
+    if tap_pool_usable(f0, f1, f2, norm):
+        return _TapPool.apply(f0, f1, f2, norm.weight, norm.bias, float(norm.eps))
+    from . import torch_cpu
+    if isinstance(f0, torch.Tensor) and f0.is_cuda:
+        note_declined("tap_pool taps %s %s" % (tuple(f0.shape), f0.dtype), "outside the served range")
+    return torch_cpu.tap_pool(f0, f1, f2, norm)
 
 
 class _CrossEntropyAcc(Function):

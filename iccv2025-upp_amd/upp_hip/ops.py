@@ -2280,6 +2280,76 @@ def cls_pool_bwd(g_feat, x, mean, rstd, gamma, amax):
     return g_x
 
 
+def cls_pool_bwd_ln(g_feat, x, mean, rstd, gamma, amax):
+    """cls_pool_bwd with the LayerNorm's parameter gradients: -> (g_x, g_gamma (D), g_beta (D)); upp_cls_pool_bwd_ln."""
+    _need(x, "x", torch.float32, ndim=3)
+    B, L, D = x.shape
+    _need_f32(g_feat, "g_feat", (B, 2 * D))
+    _need_f32(mean, "mean", (B * L,))
+    _need_f32(rstd, "rstd", (B * L,))
+    _need_f32(gamma, "gamma", (D,))
+    _need(amax, "amax", torch.int32)
+    if tuple(amax.shape) != (B, D):
+        raise RuntimeError(f"cls_pool_bwd_ln: amax must be ({B}, {D}), got {tuple(amax.shape)}")
+    _same_device(x, g_feat, mean, rstd, gamma, amax)
+    g_x = torch.empty_like(x)
+    g_par = torch.empty((2, D), dtype=torch.float32, device=x.device)
+    _call(x.device, "upp_cls_pool_bwd_ln", _abi.ptr(g_feat), _abi.ptr(x), _abi.ptr(mean), _abi.ptr(rstd), _abi.ptr(gamma), _abi.ptr(amax),
+          _abi.ptr(g_x), _abi.ptr(g_par[0]), _abi.ptr(g_par[1]), B, L, D)
+    return g_x, g_par[0], g_par[1]
+
+
+# ------------------------------------------------------------------ LayerNorm of three feature taps + token pooling (csrc/norm_pool.hip)
+def tap_pool_fwd(f0, f1, f2, gamma, beta, eps):
+    """-> x (B,G,3C) = [LN(f0) | LN(f1) | LN(f2)], gmax (B,3C), arg (B,3C) int32, gmean (B,3C), mean (B,G,3), rstd (B,G,3); upp_tap_pool_fwd."""
+    _need(f0, "f0", torch.float32, ndim=3)
+    B, G, C = f0.shape
+    dev = f0.device
+    _need_f32(f1, "f1", (B, G, C))
+    _need_f32(f2, "f2", (B, G, C))
+    _need_f32(gamma, "gamma", (C,))
+    _need_f32(beta, "beta", (C,))
+    _same_device(f0, f1, f2, gamma, beta)
+    x = torch.empty((B, G, 3 * C), dtype=torch.float32, device=dev)
+    gmax = torch.empty((B, 3 * C), dtype=torch.float32, device=dev)
+    arg = torch.empty((B, 3 * C), dtype=torch.int32, device=dev)
+    gmean = torch.empty((B, 3 * C), dtype=torch.float32, device=dev)
+    mean = torch.empty((B, G, 3), dtype=torch.float32, device=dev)
+    rstd = torch.empty((B, G, 3), dtype=torch.float32, device=dev)
+    _call(dev, "upp_tap_pool_fwd", _abi.ptr(f0), _abi.ptr(f1), _abi.ptr(f2), _abi.ptr(gamma), _abi.ptr(beta), float(eps), _abi.ptr(x),
+          _abi.ptr(gmax), _abi.ptr(arg), _abi.ptr(gmean), _abi.ptr(mean), _abi.ptr(rstd), B, G, C)
+    return x, gmax, arg, gmean, mean, rstd
+
+
+def tap_pool_bwd(d_x, d_gmax, d_gmean, f0, f1, f2, mean, rstd, gamma, arg):
+    """-> (d_f0, d_f1, d_f2 (B,G,C), d_gamma (C), d_beta (C)); upp_tap_pool_bwd (two launches, fixed-order sums)."""
+    _need(f0, "f0", torch.float32, ndim=3)
+    B, G, C = f0.shape
+    dev = f0.device
+    _need_f32(f1, "f1", (B, G, C))
+    _need_f32(f2, "f2", (B, G, C))
+    _need_f32(d_x, "d_x", (B, G, 3 * C))
+    _need_f32(d_gmax, "d_gmax", (B, 3 * C))
+    _need_f32(d_gmean, "d_gmean", (B, 3 * C))
+    _need_f32(mean, "mean", (B, G, 3))
+    _need_f32(rstd, "rstd", (B, G, 3))
+    _need_f32(gamma, "gamma", (C,))
+    _need(arg, "arg", torch.int32)
+    if tuple(arg.shape) != (B, 3 * C):
+        raise RuntimeError(f"tap_pool_bwd: arg must be ({B}, {3 * C}), got {tuple(arg.shape)}")
+    _same_device(f0, f1, f2, d_x, d_gmax, d_gmean, mean, rstd, gamma, arg)
+    n = int(_abi.load().upp_tap_pool_part_floats(B, G, C))
+    if n < 1:
+        _abi.check(-2 if min(B, G, C) >= 1 else -1)
+    part = torch.empty(n, dtype=torch.float32, device=dev)
+    d_f = torch.empty((3, B, G, C), dtype=torch.float32, device=dev)
+    d_par = torch.empty((2, C), dtype=torch.float32, device=dev)
+    _call(dev, "upp_tap_pool_bwd", _abi.ptr(d_x), _abi.ptr(d_gmax), _abi.ptr(d_gmean), _abi.ptr(f0), _abi.ptr(f1), _abi.ptr(f2), _abi.ptr(mean),
+          _abi.ptr(rstd), _abi.ptr(gamma), _abi.ptr(arg), _abi.ptr(part), _abi.ptr(d_f[0]), _abi.ptr(d_f[1]), _abi.ptr(d_f[2]),
+          _abi.ptr(d_par[0]), _abi.ptr(d_par[1]), B, G, C)
+    return d_f[0], d_f[1], d_f[2], d_par[0], d_par[1]
+
+
 def ce_acc(logits, labels):
     _need(logits, "logits", torch.float32, ndim=2)
     _need(labels, "labels", torch.int64, ndim=1)

@@ -344,6 +344,19 @@ def region_attention(q, idx, PK, PV, bk, bv, idx3, w3, num_heads, scale, drop=No
     return ctx.max(dim=2)[0] if pool is None else pool(ctx)
 
 
+def tap_pool(f0, f1, f2, norm, pool=None):
+    """include/upp_hip.h upp_tap_pool_fwd as torch operators (any device and dtype; differentiable in the taps and the LayerNorm's
+    parameters): f0, f1, f2 (B,G,C), norm an nn.LayerNorm(C) -> x (B,G,3C) = [norm(f0) | norm(f1) | norm(f2)], gmax (B,3C) = x.max(1)[0],
+    gmean (B,3C) = (((x[:,0] + x[:,1]) + x[:,2]) + ...) / G -- the kernel's order, one rounded addition per token, not torch.mean's.
+    pool: None, or a callable x (B,G,3C) -> (B,3C) that takes the place of x.max(1)[0] (the modules' arg-max instrument)."""
+    x = torch.cat([norm(f) for f in (f0, f1, f2)], dim=-1)
+    gmax = x.max(dim=1)[0] if pool is None else pool(x)
+    s = x[:, 0]
+    for g in range(1, x.shape[1]):
+        s = s + x[:, g]
+    return x, gmax, s / float(x.shape[1])
+
+
 def chamfer(xyz1, xyz2):
     """-> (dist1 (B,N), dist2 (B,M)) squared nearest-neighbour distances, differentiable (reference extensions/chamfer_dist)."""
     d = ((xyz1.unsqueeze(2) - xyz2.unsqueeze(1)) ** 2).sum(-1)

@@ -911,7 +911,7 @@ int upp_posenc_fwd(const float *x, const float *freqs, int F, float *out, int ld
  *   upp_cls_pool_fwd : h = LayerNorm(x) (B,L,D) with gamma / beta / eps (self.norm); feat (B,2D) = [h[:,0] | max over rows 1..L-1 of h]
  *                      (first maximum); amax (B,D) int32 = the arg-max row; mean / rstd (B*L) saved.  h itself is not stored.
  *   upp_cls_pool_bwd : g_x (B,L,D) from g_feat (B,2D) (dense: every row is written).  gamma / beta gradients are not
- *                      produced (self.norm is frozen under PEFT; the caller falls back to torch ops otherwise).
+ *                      produced (self.norm is frozen under PEFT; upp_cls_pool_bwd_ln below produces them when it trains).
  *   upp_ce_acc       : out2[0] = mean cross-entropy of logits (B,C) against labels (B) int64, out2[1] = top-1 accuracy * 100,
  *                      dlogits (B,C) = (softmax - onehot) / B.  C <= 512.  Deterministic. */
 int upp_cls_pool_fwd(const float *x, const float *gamma, const float *beta, float eps, float *feat, int32_t *amax, float *mean,
@@ -919,6 +919,35 @@ int upp_cls_pool_fwd(const float *x, const float *gamma, const float *beta, floa
 int upp_cls_pool_bwd(const float *g_feat, const float *x, const float *mean, const float *rstd, const float *gamma,
                      const int32_t *amax, float *g_x, int B, int L, int D, void *stream);
 int upp_ce_acc(const float *logits, const int64_t *labels, float *out2, float *dlogits, int B, int C, void *stream);
+/* ---- LayerNorm + token pooling with parameter gradients: the full fine-tuning models (csrc/norm_pool.hip) ---------------
+ * Reference models/Point_MAE_cp.py:582-587 (PointTransformer: a trainable self.norm in front of [cls | max]) and
+ * models/Point_MAE_segment.py:413-424 (PointTransformer_seg: one shared trainable self.norm on the outputs of blocks 3 / 7 / 11, their
+ * concatenation, its max and mean over the tokens).  Every sum has an order fixed by the sizes; no atomics, no memset; every output
+ * element is written by a kernel; arguments are checked before the first launch (UPP_E_BADARG: null pointer / size < 1, L < 2;
+ * UPP_E_RANGE: outside the served range).
+ *   upp_cls_pool_bwd_ln : upp_cls_pool_bwd (the same kernel: g_x has its bits) + g_gamma (D), g_beta (D).  With g_h[b][0][d] =
+ *                         g_feat[b][d] and g_h[b][amax[b][d]][d] += g_feat[b][D + d]:  g_beta[d] = sum g_h,  g_gamma[d] = sum g_h * xhat
+ *                         (acc = fma(g_h, xhat, acc)), xhat = (x - mean) * rstd from the saved statistics, both over (b, l) ascending and
+ *                         over the 2 B rows that carry a gradient only.  Two launches.  D <= 512.
+ *   upp_tap_pool_fwd    : f0, f1, f2 (B,G,C) -> x (B,G,3C) = [LN(f0) | LN(f1) | LN(f2)] (the bits of upp_rowln_fwd per row), gmax (B,3C) =
+ *                         max over g of x, arg (B,3C) int32 = the LOWEST g that attains it, gmean (B,3C) = (((x[0] + x[1]) + x[2]) + ...) /
+ *                         float(G) (f32, g ascending, one rounded addition at a time, one division), mean / rstd (B,G,3).  NaN: as
+ *                         upp_group_max_fwd and upp_cls_pool_fwd (torch.max over a dimension) -- a NaN beats every number, the first NaN
+ *                         of a column is its maximum, and it stays in its own row's tap (LayerNorm) and its own column (pooling).  One launch.
+ *   upp_tap_pool_bwd    : t = (d_x + d_gmean / float(G)) + (g == arg ? d_gmax : 0) per element, then the row-LayerNorm backward of
+ *                         upp_rowln_bwd per (row, tap) -> d_f0, d_f1, d_f2 (B,G,C);  d_gamma / d_beta (C): per row the three taps' terms
+ *                         t * xhat / t added in tap order, rows (b, g) ascending in groups of 4 ((r0 + r1) + (r2 + r3)) into `part`,
+ *                         the ceil(B G / 4) partials in 16 consecutive runs, each ascending, the run sums ascending.  `part`:
+ *                         upp_tap_pool_part_floats(B, G, C) floats of scratch (0: sizes not served).  Two launches.
+ *   Served: 1 <= B <= 65535, 1 <= G <= UPP_ATTN_MAX_L, C % 4 == 0, 4 <= C <= 512; exactly three taps. */
+int upp_cls_pool_bwd_ln(const float *g_feat, const float *x, const float *mean, const float *rstd, const float *gamma,
+                        const int32_t *amax, float *g_x, float *g_gamma, float *g_beta, int B, int L, int D, void *stream);
+int upp_tap_pool_fwd(const float *f0, const float *f1, const float *f2, const float *gamma, const float *beta, float eps,
+                     float *x, float *gmax, int32_t *arg, float *gmean, float *mean, float *rstd, int B, int G, int C, void *stream);
+long long upp_tap_pool_part_floats(int B, int G, int C);
+int upp_tap_pool_bwd(const float *d_x, const float *d_gmax, const float *d_gmean, const float *f0, const float *f1, const float *f2,
+                     const float *mean, const float *rstd, const float *gamma, const int32_t *arg, float *part, float *d_f0,
+                     float *d_f1, float *d_f2, float *d_gamma, float *d_beta, int B, int G, int C, void *stream);
 /* ---- per-point log-softmax + NLL of the segmentation head (round 6) ---------------------------------------------------
  * Replaces `F.log_softmax(x, dim=-1)` (reference models/Point_MAE_unify_segment.py:433) and `F.nll_loss(pred, target)`
  * (:20-25 get_loss) over R = B * N point rows of C <= 64 classes, and the torch glue around them (gather, mean, neg, div, zero-fill +
